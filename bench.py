@@ -10,6 +10,7 @@ region starts.
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
     python bench.py --workload glyph256          # BASELINE configs[3]: the glyph ResNet alone on 256 x 128 glyph stacks
+    python bench.py --dump-outputs DIR           # also write the last timed step's outputs as DIR/*.npy (same inputs every run)
 
 Rank 0 prints ONE JSON line.
 * `value`            whole-job train sentences/s (max over ranks of the timed region).
@@ -306,6 +307,28 @@ def dump_launches(lib, sampled, path):
         json.dump(out, f, indent=0)
 
 
+DUMP_SAMPLE = 1 << 22      # elements per sampled array: three 16 MB float32 samples keep a dump under 64 MB
+
+
+def dump_outputs(path, loss, opt, model):
+    """--dump-outputs: what the last timed step handed its caller, as float32 .npy files - the loss, the global gradient norm that
+    clip_grad_norm_ measured, and the updated parameters and AdamW moments (the moments carry that step's gradients) at the same
+    fixed, seeded positions of the flat arena, so two builds can be compared output for output"""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    flat = opt.state_dict()["realise_flat"]           # (syncs a pipelined optimizer sweep before anything is read)
+    arrays = {"parameters": model.flat_parameters(), "adam_m": flat["m"], "adam_v": flat["v"]}
+    n = arrays["parameters"].numel()
+    idx = None
+    if n > DUMP_SAMPLE:
+        idx = torch.randint(n, (DUMP_SAMPLE,), generator=torch.Generator().manual_seed(0)).sort().values.to(arrays["parameters"].device)
+    out = {"loss": loss.reshape(1), "grad_norm": opt.grad_norm().reshape(1)}
+    for name, t in arrays.items():
+        out[name] = t.detach().reshape(-1) if idx is None else t.detach().reshape(-1)[idx]
+    for name, t in out.items():
+        np.save(os.path.join(path, name + ".npy"), t.float().cpu().numpy())
+
+
 def timed_loop(fn, steps, world, dev):
     if world > 1:
         dist.barrier()
@@ -362,7 +385,14 @@ def main():
     ap.add_argument("--no-overlap", action="store_true", help="run the bert / pho / glyph branches serially on one stream")
     ap.add_argument("--knob", action="append", default=[], help="diagnostic knob as name:key=value, e.g. engine:0=1 (realise_set_engine(0, 1)); names: engine, ln, nt8p; "
                                                                     "opt:fused=0 steps with the arena-level AdamW kernels + full operand refresh")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last one computed as DIR/<name>.npy (float32): loss, grad_norm, and a fixed "
+                         "seeded sample of the updated parameters and AdamW moments; train workload only")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    if args.dump_outputs and args.workload != "train":
+        ap.error("--dump-outputs covers the train workload only")
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
@@ -463,11 +493,13 @@ def main():
         if k in batch:
             batch[k] = batch[k].to(dev)
     tr_loss = torch.zeros((), device=dev)
+    last_loss = [None]
 
     def step(i=0):
         loss = wrapped(batch)[0]
         loss.backward()
-        tr_loss.add_(loss.detach())
+        last_loss[0] = loss.detach()
+        tr_loss.add_(last_loss[0])
         opt.step()
         sched.step()
         model.zero_grad()
@@ -497,6 +529,8 @@ def main():
     elapsed = timed_loop(prof_step, args.steps, world, dev)
     lib.realise_set_branch_overlap(overlap)
     lib.realise_set_wgrad_overlap(overlap)
+    if args.dump_outputs and rank == 0:                     # before the sub-measurements below step the same model further
+        dump_outputs(args.dump_outputs, last_loss[0], opt, model)
     final_loss = float(tr_loss.item()) / max(1, args.steps + args.warmup)
     fams = {}
     if profile:

@@ -5,9 +5,8 @@ TEST INFRASTRUCTURE - never imported by the product path (realise_amd/).
 Puts /root/reference on sys.path (so the vendored transformers 2.2.2 shadows
 site-packages) and stubs the six third-party modules the reference imports but
 never touches on the hot path.  Used only by
-oracle/make_golden.py and by the CPU tests that pin the restatement when
-/root/reference is present.  Nothing here travels to the GPU box in a usable
-form: /root/reference does not exist there and the callers skip.
+the oracle/make_golden*.py generators; the tests read what they committed under
+tests/golden/ and never import the reference.
 """
 import os
 import sys

@@ -158,23 +158,27 @@ def test_save_pretrained_from_pretrained_round_trip(tmp_path):
     assert m2.config.num_fonts == 3 and m2.config.num_hidden_layers == 2
 
 
-def test_from_pretrained_loads_a_reference_written_checkpoint(tmp_path):
-    """a pytorch_model.bin written by the REFERENCE's save_pretrained (transformers/modeling_utils.py:236-251) loads unchanged"""
-    from _ref_import import import_reference, reference_available
-    if not reference_available():
-        pytest.skip("reference tree not present")
-    models, BertConfig = import_reference()
-    bc = BertConfig(vocab_size_or_config_json_file=21128)
-    bc.num_hidden_layers = 1
-    bc.image_model_type = 0
-    bc.num_fonts = 3
-    torch.manual_seed(5)
-    ref = models.SpellBertPho2ResArch3(bc)
-    ref.tie_cls_weight()
-    ref.save_pretrained(str(tmp_path))
+def test_from_pretrained_loads_a_reference_written_checkpoint(tmp_path, golden_dir):
+    """a checkpoint as the REFERENCE's save_pretrained (transformers/modeling_utils.py:236-251) writes it loads unchanged: its
+    config.json verbatim and a pytorch_model.bin with the reference's entry names, order, shapes, dtypes and tied storage
+    (tests/golden/reference_checkpoint.json, oracle/make_golden_restatement.py), filled with seeded values"""
+    with open(os.path.join(golden_dir, "reference_checkpoint.json")) as f:
+        layout = json.load(f)
+    with open(tmp_path / "config.json", "w") as f:
+        json.dump(layout["config"], f)
+    g = torch.Generator().manual_seed(5)
+    rsd = {}
+    for e in layout["state_dict"]:
+        if e["same_as"] is not None:
+            rsd[e["name"]] = rsd[e["same_as"]]
+        elif e["dtype"] == "float32":
+            rsd[e["name"]] = torch.randn(e["shape"], generator=g) * 0.02
+        else:
+            rsd[e["name"]] = torch.randint(0, 100, e["shape"], generator=g, dtype=getattr(torch, e["dtype"]))
+    torch.save(rsd, tmp_path / "pytorch_model.bin")
     cfg = RealiseConfig(num_hidden_layers=1)
     ours = SpellBertPho2ResArch3.from_pretrained(str(tmp_path), config=cfg)
-    rsd, osd = ref.state_dict(), ours.state_dict()
+    osd = ours.state_dict()
     assert set(rsd.keys()) == set(osd.keys())
     for k, v in rsd.items():
         assert torch.equal(v, osd[k]), k
