@@ -220,9 +220,7 @@ void realise_engine_set_grads_fresh(realise_engine* e, int fresh);
  * pho_idx into its workspace with out-of-range ids replaced by 0 and sets *flag = 1 (sticky; device memory or host-mapped pinned
  * memory, nullable) when it replaced one.  The caller reads the flag when it next touches the host (the Python module: at the
  * next forward / backward / decode) and raises; results of a flagged step are meaningless, but no memory outside the tables was read.
- * `flag` points to TWO int32: flag[0] = the id-range flag above; flag[1] = set to 1 if a workgroup of the fused dense + LayerNorm
- * launch gave up waiting for the other column tiles of its rows (never observed; the wait is bounded so that a scheduling surprise
- * cannot hang the device - the step's results are meaningless then). */
+ * Only flag[0] is read or written, so a caller may pass a longer array. */
 void realise_engine_set_id_flag(realise_engine* e, int32_t* flag);
 /* The gradient arriving at the loss (`grad_output` of loss.backward(): 1, or 1 / gradient_accumulation_steps, src/run.py:197-200) as
  * a DEVICE fp32 scalar that realise_engine_backward reads when it runs (NULL = 1, the default).  It scales the three gradients that

@@ -1,4 +1,4 @@
-/* realise_hip_debug.h - diagnostics of librealise_hip.so: A/B knobs, probe modes, per-launch timing hooks.
+/* realise_hip_debug.h - diagnostics of librealise_hip.so: A/B knobs and per-launch timing hooks.
  *
  * NOT part of the operator boundary (include/realise_hip.h): nothing here changes results unless its comment says so, the
  * defaults are the production configuration, and a drop-in user never needs to call any of it.  tools/*.cpp, bench.py
@@ -15,10 +15,9 @@ extern "C" {
 void realise_set_tn_transpose_read(int enable);
 /* A/B knob: allow the 128x96 NT tile chosen by the chip-balance heuristic (default 1) */
 void realise_set_nt_allow_n96(int on);
-/* Diagnostics only (tools/nt_probe.cpp; results are WRONG when != 0): 1 every tile fetches tile 0's operands (cache-hot),
- * 2 no operand fetches, 3 no MFMA work - separates the memory, issue and compute shares of the NT kernel's time. */
-void realise_set_nt_probe(int mode);
-/* Diagnostics: force an experimental NT tile shape for dense bf16 GEMMs (0 = production heuristic). */
+/* Diagnostics: force one NT kernel for dense bf16 GEMMs - 9 the 4-wave kernel, 12 / 14 / 16 the 8-wave 256 x 192 / 128 x 192 three-stage /
+ * 128 x 192 two-per-CU tiles, 50 the persistent 256 x 192 kernel wherever it applies, 51 never the persistent kernel; 0 (default) and
+ * any other value: chosen from the shape. */
 void realise_set_nt_variant(int v);
 /* step engine: key 0 = enqueue order of the three forward branches (0: bert stack first, 1: the shorter pinyin / glyph branches first);
  * keys 1 / 2 / 3 = priority class of the pinyin-branch / glyph-branch / weight-gradient stream (-1 highest, 0 device default, +1 lowest),
@@ -26,24 +25,17 @@ void realise_set_nt_variant(int v);
  * enter the loss only (1, default) or over all rows (0); key 5 = the backward skips the rows of padding tokens, whose gradient rows are
  * exact zeros (LayerNorm backward rows, blocks of the weight-gradient reductions; 1 default: live 16-row blocks packed four to a
  * reduction tile in bf16, 2: whole 64-row tiles only - bit-identical to 0 -, 0 off); key 6 = K-ranges of the split-K classifier data
- * gradient (bf16; default 3, 0 / 1 = one launch over the whole K = 21184); key 7 = grouped weight gradients of the transformer layers on
- * the 4-wave 128 x 128 kernel, two workgroups per CU (0, default) or on the 8-wave 256 x 128 kernel, one tile per CU (1: measured, slower); key 8 = BertSelfOutput /
- * BertOutput as GEMM + LayerNorm launches (0, default) or as one launch (dense + bias + dropout + residual + LayerNorm: 1 - correct, measured
- * 0.3 ms/step slower; 2 = the same without the cross-tile hand-off, diagnostics only: wrong statistics); key 9 = a GRU
- * time step as one launch (recurrent GEMM with the gate math in its epilogue: 1, default) or as GEMM + gate kernel (0); key 10 = bf16
- * training steps run the layer GEMMs of the transformer stacks (forward and data gradients) and the attention forward over the live
- * 16-row blocks of the padded batch only (1, default: loss, live-row logits and gradients bit-identical to the dense step; the rows
- * behind a sentence's last attended / loss position keep stale activations) or over all rows (0); key 11 = the layer GEMMs with enough
- * K-tiles to share out (qkv, FFN-up / -down and their data gradients) on the stream-K 256 x 192 kernel (1) or on the 128 x 192 two-per-CU
- * kernels (0, default: measured faster on every layer shape, and their live-row results are bit-identical to the dense step's - a tile that
- * stream-K cuts sums its K range in two or three chains); key 12 = the least K-tiles per workgroup of a launch that select the stream-K
- * kernel under key 11 (default 10; 0: every shape it supports; keys 11 / 12 act in the probe build only - round 6); key 13 = K7, the
- * glyph lookup fused into the loaders of block 1's forward convolutions (1, default: no gathered image batch in the forward; a
- * training step gathers it at the head of the backward for the two weight-gradient reductions) or gather_images + dense loaders (0);
- * key 14 = K9 in evaluation mode: BatchNorm on its running statistics applied in the glyph convolutions' epilogues (1, default: per
- * block three launches, shortcut first, its normalised output added in the second convolution's epilogue) or as separate scale / shift
- * and apply kernels over the raw convolution outputs (0, the round-5 form); key 15 = realise_engine_adamw_pipelined runs pipelined (1,
- * default) or as the plain sweep on the caller's stream (0) */
+ * gradient (bf16; default 3, 0 / 1 = one launch over the whole K = 21184); key 9 = a GRU time step as one launch (recurrent GEMM with
+ * the gate math in its epilogue: 1, default) or as GEMM + gate kernel (0); key 10 = bf16 training steps run the layer GEMMs of the
+ * transformer stacks (forward and data gradients) and the attention forward over the live rows of the padded batch only (2, default:
+ * a list of live rows; 1: a list of live 16-row blocks; loss, live-row logits and gradients bit-identical to the dense step; the rows
+ * behind a sentence's last attended / loss position keep stale activations) or over all rows (0); key 13 = K7, the glyph lookup fused
+ * into the loaders of block 1's forward convolutions (1, default: no gathered image batch in the forward; a training step gathers it
+ * at the head of the backward for the two weight-gradient reductions) or gather_images + dense loaders (0); key 14 = K9 in evaluation
+ * mode: BatchNorm on its running statistics applied in the glyph convolutions' epilogues (1, default: per block three launches,
+ * shortcut first, its normalised output added in the second convolution's epilogue) or as separate scale / shift and apply kernels
+ * over the raw convolution outputs (0, the round-5 form); key 15 = realise_engine_adamw_pipelined runs pipelined (1, default) or as
+ * the plain sweep on the caller's stream (0).  Other keys are ignored. */
 void realise_set_engine(int key, int value);
 /* realise_gemm_tn_grouped over a list of live reduction blocks, as the engine's backward calls it: live[k] (device, ascending) = index
  * of the k-th block of `list_rows` rows that holds anything but exact zeros in the A operands, *n_live (device) = how many; the other
@@ -65,15 +57,6 @@ int realise_gemm_nt_live(void* stream, const void* A, int64_t lda, const void* B
  * 128 t + 127], so no tile row is spent on rows that merely complete a 16-row block.  Listed rows: bit-identical to the dense launch. */
 int realise_gemm_nt_live_rows(void* stream, const void* A, int64_t lda, const void* B, int64_t ldb, int M, int N, int K,
                               const realise_epilogue* ep, const int* row_list, const int* row_count);
-/* The stream-K form of the layer GEMMs (bf16, K % 128 == 0; gemm_nt8s.hip): ONE round of 256 workgroups over 256 x 192 tiles, the
- * (tile, K-tile) space cut into 256 equal ranges, tiles that a cut splits folded in-kernel in workgroup order.  live_list / live_count
- * as realise_gemm_nt_live, or both NULL (all rows).  part: exchange buffer of 256 * 24 * 512 * 16 bytes; flags: 256 x 64 ints (a flag every 256 bytes), zero before the
- * first launch; tag: never 0, different from the previous launch's on the same buffers; timeout (nullable): set to 1 if a workgroup gave
- * up waiting for a partial tile.  Reproducible bit for bit for given (shape, live count); differs in the last bits from
- * realise_gemm_nt / realise_gemm_nt_live where a tile's K range is cut (two or three accumulation chains instead of one). */
-int realise_gemm_nt_streamk(void* stream, const void* A, int64_t lda, const void* B, int64_t ldb, int M, int N, int K,
-                            const realise_epilogue* ep, const int* live_list, const int* live_count, float* part, int* flags, int tag,
-                            int* timeout);
 /* Split-K form of the 8-wave NT GEMM as the classifier's data gradient uses it (bf16, K % 64 == 0): slab[s][m][n] (fp32, row pitch N,
  * plane pitch slab_stride floats) = A[m, K-range s] . B[n, K-range s]^T; rows at or beyond *m_dev (device, nullable) are not computed. */
 int realise_gemm_nt_splitk(void* stream, const void* A, int64_t lda, const void* B, int64_t ldb, int M, int N, int K, int nsplit,
@@ -115,26 +98,13 @@ int realise_batchnorm_bwd_ex(void* stream, const void* dy, const void* relu_src,
                              const void* xb, const float* mean_b, const float* rstd_b, const float* gamma_b, void* dxb, float* dgamma_b, float* dbeta_b,
                              float* sums, float* slots);
 /* persistent NT kernel (gemm_nt8p.hip): key 0 = tile walk (1 default: every XCD owns a band of tile rows, 0: chunked tile ids),
- * key 1 = workgroups launched (default 256 = one per CU); key 2 = one-round outputs (at most one 128 x 192 tile per CU) on the
- * three-stage one-per-CU shape (1) or the two-per-CU shape (0, default: faster inside a step) of gemm_nt8.hip; key 3 = column groups of
- * the XCD split of the live-row layer GEMMs (0 default: from the shape - 2 for the wide K = 768 outputs, 1 otherwise; 1 / 2 / 4 / 8 forced);
- * key 4 = the 8-wave kernels add alpha / bias to the accumulators before the epilogue's transposes (1, default: one bias fetch per wave and no
- * per-item waits in the bias-only epilogues) or per item (0, the round-4 form) - same bits */
+ * key 1 = workgroups launched (default 256 = one per CU); key 3 = column groups of the XCD split of the live-row layer GEMMs (0 default:
+ * from the shape - 2 for the wide K = 768 outputs, 1 otherwise; 1 / 2 / 4 / 8 forced).  Other keys are ignored. */
 void realise_set_nt8p(int key, int value);
 void realise_set_nt_group_m(int g);        /* tile order of the 8-wave NT GEMM: 0 row-major, g: g tile rows per column step (L2 blocking) */
-/* Diagnostics for the TN kernel: 2 no operand fetches, 3 no MFMA work, 4 skip the slab fold pass. */
-void realise_set_tn_probe(int mode);
 /* Diagnostics: force the number of reduction splits of the TN kernel (0 = heuristic). */
 void realise_set_tn_split(int n);
-/* weight-gradient kernel selection: 0 production (8-wave 256x128-tile kernel for the big dense bf16 shapes), 9 force the 4-wave kernel */
-void realise_set_tn_variant(int v);
 void realise_set_conv_c64(int on);         /* 1 (default): the 64->64 channel 3x3 conv on 16x16 maps (forward, input and weight gradient) runs the LDS-resident kernels */
-void realise_set_tn_group_ring(int on);    /* grouped weight gradients: 0 (default) two LDS stages of 64-row K-tiles, 1 four stages of 32 rows (measured 11 % slower) */
-/* Diagnostics for the attention forward kernel: 1 stop after operand staging, 2 skip the softmax (results WRONG). */
-void realise_set_attn_probe(int mode);
-/* A/B knob: 1 (default) the NT epilogue goes through a per-wave LDS transpose so every global access is 16 B per lane over
- * whole 128-byte row segments; 0 stores the MFMA fragments directly (8 B per lane). Identical results. */
-void realise_set_nt_wide_epilogue(int on);
 /* A/B knob: 1 (default) run the glyph ResNet once per distinct token id with multiplicity-weighted BatchNorm;
  * 0 run it densely over all B*S tokens like the reference (identical results) */
 void realise_set_glyph_dedup(int on);
@@ -171,11 +141,8 @@ int realise_profile_dump(int kernel_family, int max_records, float* ms_out, doub
 int realise_profile_read_ex(int kernel_family, long long* count, double* total_ms, double* total_work, double* total_work_executed);
 int realise_profile_dump_ex(int kernel_family, int max_records, float* ms_out, double* work_out, double* work_executed_out);
 
-/* Host-side support predicates of the weight-gradient kernels, exported so that a CPU test can pin them (a comment
- * once swallowed half of the first one's conditions).  realise_debug_tn8_supported: 1 when the 8-wave TN kernel takes the problem
- * (plain epilogue, no live-block list), 0 when the caller must fall back to the 4-wave kernel.  realise_debug_tn_list_lds: bytes of
- * LDS a listed TN launch reserves for `entries` live blocks, -1 when the list does not fit (the engine then runs dense reductions). */
-int realise_debug_tn8_supported(int64_t lda, int64_t ldb, int P, int I, int J, int64_t ldo);
+/* Host-side support predicate of the listed weight-gradient launches, exported so that a CPU test can pin it: bytes of LDS a listed
+ * TN launch reserves for `entries` live blocks, -1 when the list does not fit (the engine then runs dense reductions). */
 int realise_debug_tn_list_lds(int64_t entries);
 
 /* how many workspace plans the engine has installed (= whole-workspace zero fills) since it was created: a loop that alternates

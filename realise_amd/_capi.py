@@ -79,13 +79,11 @@ SYMBOLS = {
     "realise_gemm_nt_rows": (_I, [_P, _I, _P, _L, _P, _L, _I, _I, _I, C.POINTER(Epilogue), _P]),
     "realise_gemm_nt_live": (_I, [_P, _P, _L, _P, _L, _I, _I, _I, C.POINTER(Epilogue), _P, _P]),
     "realise_gemm_nt_live_rows": (_I, [_P, _P, _L, _P, _L, _I, _I, _I, C.POINTER(Epilogue), _P, _P]),
-    "realise_gemm_nt_streamk": (_I, [_P, _P, _L, _P, _L, _I, _I, _I, C.POINTER(Epilogue), _P, _P, _P, _P, _I, _P]),
     "realise_gemm_nt_splitk": (_I, [_P, _P, _L, _P, _L, _I, _I, _I, _I, _P, _L, _P]),
     "realise_gemm_tn_grouped_live": (_I, [_P, _I, _I, C.POINTER(TnProblem), _I, _P, _P, _I, _I]),
     "realise_conv_tn": (_I, [_P, _I, _P, _L, C.POINTER(ConvGeom), _I, _I, _I, _P, _P, _L]),
     "realise_set_tn_transpose_read": (None, [_I]),
     "realise_set_nt_allow_n96": (None, [_I]),
-    "realise_set_nt_probe": (None, [_I]),
     "realise_set_nt_variant": (None, [_I]),
     "realise_set_nt_group_m": (None, [_I]),
     "realise_set_nt8p": (None, [_I, _I]),
@@ -96,14 +94,9 @@ SYMBOLS = {
     "realise_layernorm_bwd_live": (_I, [_P, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_float, _P, _P, _P, _P, _I, _I]),
     "realise_batchnorm_stats_ex": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P, C.c_float, C.c_float] + [_P] * 9),
     "realise_batchnorm_bwd_ex": (_I, [_P, _P, _P, _I, _I, _I, _P, _I] + [_P] * 7 + [_P] * 7 + [_P, _P]),
-    "realise_set_tn_probe": (None, [_I]),
     "realise_set_tn_split": (None, [_I]),
-    "realise_set_tn_variant": (None, [_I]),
-    "realise_set_tn_group_ring": (None, [_I]),
     "realise_set_conv_c64": (None, [_I]),
-    "realise_set_attn_probe": (None, [_I]),
     "realise_set_branch_overlap": (None, [_I]),
-    "realise_set_nt_wide_epilogue": (None, [_I]),
     "realise_set_glyph_dedup": (None, [_I]),
     "realise_set_wgrad_overlap": (None, [_I]),
     "realise_set_wgrad_group": (None, [_I]),
@@ -137,7 +130,6 @@ SYMBOLS = {
     "realise_engine_workspace_bytes": (_L, [_P, _I, _I, _I]),
     "realise_engine_forget_workspace": (None, [_P, _P]),
     "realise_engine_plan_installs": (_L, [_P]),
-    "realise_debug_tn8_supported": (_I, [_L, _L, _I, _I, _I, _L]),
     "realise_debug_tn_list_lds": (_I, [_L]),
     "realise_engine_bind": (_I, [_P, _P, _P, _L]),
     "realise_engine_refresh_shadows": (_I, [_P, _P]),
@@ -188,8 +180,6 @@ def load():
     # streams / kernels do not mix: every launch on a torch stream then fails).
     import torch  # noqa: F401
     path = LIB_PATH
-    if os.environ.get("REALISE_HIP_PROBES") == "1":      # measurement sessions: the probe build (python -m realise_amd.build --probes)
-        path = LIB_PATH.replace(".so", "_probes.so")
     if not os.path.exists(path):
         raise RealiseHipError(
             "%s is missing. Build it with `python -m realise_amd.build` "
@@ -200,7 +190,7 @@ def load():
         fn.restype = res
         fn.argtypes = args
     # A/B knobs for measurements (defaults are the production settings)
-    for env, fn in (("REALISE_WGRAD_OVERLAP", lib.realise_set_wgrad_overlap), ("REALISE_WGRAD_GROUP", lib.realise_set_wgrad_group), ("REALISE_TN_GROUP_RING", lib.realise_set_tn_group_ring), ("REALISE_CONV_C64", lib.realise_set_conv_c64), ("REALISE_DGRAD_PARITY", lib.realise_set_dgrad_parity), ("REALISE_GLYPH_DEDUP", lib.realise_set_glyph_dedup),
+    for env, fn in (("REALISE_WGRAD_OVERLAP", lib.realise_set_wgrad_overlap), ("REALISE_WGRAD_GROUP", lib.realise_set_wgrad_group), ("REALISE_CONV_C64", lib.realise_set_conv_c64), ("REALISE_DGRAD_PARITY", lib.realise_set_dgrad_parity), ("REALISE_GLYPH_DEDUP", lib.realise_set_glyph_dedup),
                     ("REALISE_NT_VARIANT", lib.realise_set_nt_variant), ("REALISE_NT_GROUP_M", lib.realise_set_nt_group_m)):
         if os.environ.get(env) is not None:
             fn(int(os.environ[env]))

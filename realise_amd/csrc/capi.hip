@@ -72,7 +72,7 @@ static int tn_grouped(hipStream_t st, int n, const realise_tn_problem* pr, int P
 
 extern "C" {
 
-const char* realise_version(void) { return RL_PROBES ? "realise_hip 0.3 (gfx950) +probes" : "realise_hip 0.3 (gfx950)"; }
+const char* realise_version(void) { return "realise_hip 0.3 (gfx950)"; }
 
 int realise_gemm_nt(void* stream, int dtype, const void* A, int64_t lda, const void* B, int64_t ldb, int M, int N, int K,
                     const realise_epilogue* ep) {
@@ -134,20 +134,6 @@ int realise_gemm_nt_live_rows(void* stream, const void* A, int64_t lda, const vo
   e.live_list = row_list; e.live_count = row_count; e.live_unit = 1;
   return gemm_nt8_live((hipStream_t)stream, (const bf16_t*)A, lda, (const bf16_t*)B, ldb, M, N, K, e);
 }
-int realise_gemm_nt_streamk(void* stream, const void* A, int64_t lda, const void* B, int64_t ldb, int M, int N, int K,
-                            const realise_epilogue* ep, const int* live_list, const int* live_count, float* part, int* flags, int tag, int* timeout) {
-#if RL_PROBES
-  if (!ep || !ep->out || !part || !flags) return RL_ERR_ARG;
-  EpiParams<bf16_t> e = to_epi<bf16_t>(ep);
-  e.live_list = live_list; e.live_count = live_count;
-  e.sk_part = part; e.sk_flag = flags; e.sk_tag = tag; e.sk_timeout = timeout;
-  return gemm_nt8s((hipStream_t)stream, (const bf16_t*)A, lda, (const bf16_t*)B, ldb, M, N, K, e);
-#else
-  // the stream-K kernel (measured slower on every layer shape) ships in the probe build only
-  (void)stream; (void)A; (void)lda; (void)B; (void)ldb; (void)M; (void)N; (void)K; (void)ep; (void)live_list; (void)live_count; (void)part; (void)flags; (void)tag; (void)timeout;
-  return RL_ERR_ARG;
-#endif
-}
 int realise_gemm_nt_splitk(void* stream, const void* A, int64_t lda, const void* B, int64_t ldb, int M, int N, int K, int nsplit,
                            float* slab, int64_t slab_stride, const int* m_dev) {
   return gemm_nt8_splitk((hipStream_t)stream, (const bf16_t*)A, lda, (const bf16_t*)B, ldb, M, N, K, nsplit, slab, slab_stride, m_dev);
@@ -173,23 +159,17 @@ int realise_conv_tn(void* stream, int dtype, const void* A, int64_t lda, const r
 }
 void realise_set_tn_transpose_read(int enable) { set_tn_transpose_read(enable); }
 void realise_set_nt_allow_n96(int on) { set_nt_allow_n96(on); }
-void realise_set_nt_probe(int mode) { set_nt_probe(mode); }
 void realise_set_nt_variant(int v) { set_nt_variant(v); }
 void realise_set_nt_group_m(int g) { set_nt8_group_m(g); }
 void realise_set_ln(int key, int value) {
   if (key == 0) set_ln_fast(value); else if (key == 1) set_ln_bwd_blocks(value); else if (key == 2) set_bn_fast(value); else if (key == 3) set_bn_chunks(value); else if (key == 4) set_ce_fast(value); else if (key == 5) set_ln_v2(value); else if (key == 6) set_adamw_reg(value);
 }
-void realise_set_engine(int key, int value) { if (key == 0) set_fwd_order(value); else if (key >= 1 && key <= 3) set_stream_priority(key - 1, value); else if (key == 4) set_cls_compact(value); else if (key == 5) set_skip_dead(value); else if (key == 6) set_cls_splitk(value); else if (key == 7) set_tn_group8(value); else if (key == 8) set_ln_fuse(value); else if (key == 9) set_gru_fuse(value); else if (key == 10) set_live_rows(value); else if (key == 11) set_streamk(value); else if (key == 12) set_streamk_min(value); else if (key == 13) set_glyph_fuse(value); else if (key == 14) set_bn_fold(value); else if (key == 15) set_opt_pipe(value); }
-void realise_set_nt8p(int key, int value) { if (key == 0) set_nt8p_order(value); else if (key == 1) set_nt8p_wgs(value); else if (key == 2) set_nt8_single_round(value); else if (key == 3) set_nt8_live_gc(value); else if (key == 4) set_nt8_epi_pre(value); else if (key == 5) set_nt8_live_big(value); else if (key == 6) set_tn_jmajor(value); else if (key == 7) set_nt8_cu_pair(value); else if (key == 8) set_nt8_l2_prefetch(value); }
-void realise_set_tn_probe(int mode) { set_tn_probe(mode); }
-void realise_set_attn_probe(int mode) { set_attn_probe(mode); }
+void realise_set_engine(int key, int value) { if (key == 0) set_fwd_order(value); else if (key >= 1 && key <= 3) set_stream_priority(key - 1, value); else if (key == 4) set_cls_compact(value); else if (key == 5) set_skip_dead(value); else if (key == 6) set_cls_splitk(value); else if (key == 9) set_gru_fuse(value); else if (key == 10) set_live_rows(value); else if (key == 13) set_glyph_fuse(value); else if (key == 14) set_bn_fold(value); else if (key == 15) set_opt_pipe(value); }
+void realise_set_nt8p(int key, int value) { if (key == 0) set_nt8p_order(value); else if (key == 1) set_nt8p_wgs(value); else if (key == 3) set_nt8_live_gc(value); }
 void realise_set_tn_split(int n) { set_tn_split(n); }
 void realise_set_wgrad_group(int on) { set_wgrad_group(on); }
 void realise_set_dgrad_parity(int on) { set_dgrad_parity(on); }
-void realise_set_tn_variant(int v) { set_tn_variant(v); }
-void realise_set_tn_group_ring(int on) { set_tn_group_ring(on); }
 void realise_set_conv_c64(int on) { set_conv_c64(on); }
-void realise_set_nt_wide_epilogue(int on) { set_nt_wide_epilogue(on); }
 void realise_set_glyph_dedup(int on) { set_glyph_dedup(on); }
 void realise_set_wgrad_overlap(int on) { set_wgrad_overlap(on); }
 void realise_set_branch_overlap(int on) { set_branch_overlap(on); }
@@ -466,10 +446,6 @@ int64_t realise_engine_shadow_bytes(const realise_engine* e) { return e ? e->imp
 int64_t realise_engine_workspace_bytes(const realise_engine* e, int B, int S, int Tp) { return e ? e->impl->workspace_bytes(B, S, Tp) : -1; }
 int realise_engine_bind(realise_engine* e, void* shadow, void* workspace, int64_t workspace_bytes) {
   return e ? e->impl->bind(shadow, workspace, workspace_bytes) : RL_ERR_ARG;
-}
-int realise_debug_tn8_supported(int64_t lda, int64_t ldb, int P, int I, int J, int64_t ldo) {
-  TnEpi te; te.ldo = ldo;
-  return tn8_supported(lda, ldb, P, I, J, te) ? 1 : 0;
 }
 int realise_debug_tn_list_lds(int64_t entries) { return tn_list_lds_bytes(entries); }
 int64_t realise_engine_plan_installs(const realise_engine* e) { return e ? e->impl->plan_install_count() : -1; }

@@ -12,13 +12,10 @@ void set_dgrad_parity(int on);    // stride-2 conv data gradients by input-pixel
 void set_fwd_order(int o);        // enqueue order of the forward branches: 0 bert first, 1 bert last
 void set_skip_dead(int on);        // backward skips padding rows (default 1)
 void set_cls_compact(int on);      // classifier backward over the loss rows only (default 1)
-void set_ln_fuse(int on);          // dense + dropout + residual + LayerNorm as one launch (default 0: see engine.hip)
 void set_gru_fuse(int on);         // GRU time step as one launch: recurrent GEMM + gate math (default 1)
 void set_glyph_fuse(int on);       // K7: glyph lookup fused into block 1's forward conv loaders (default 1)
 void set_opt_pipe(int on);         // realise_engine_adamw_pipelined as such (1, default) or as the plain sweep on the caller's stream (0)
 void set_bn_fold(int on);          // K9 (evaluation): BatchNorm on running statistics applied in the convolutions' epilogues (default 1)
-void set_streamk(int v);           // 1: layer GEMMs on the stream-K 256 x 192 kernel (gemm_nt8s.hip; measured slower: default 0)
-void set_streamk_min(int n);       // the least K-tiles per workgroup of a launch that select it (default 10)
 void set_live_rows(int on);        // bf16 training steps: layer GEMMs / attention forward over the live 16-row blocks only (default 1)
 void set_cls_splitk(int n);        // K-ranges of the classifier's data gradient (default 3, 0 / 1: one launch over the whole K)
 void set_stream_priority(int which, int pri);   // 0 pinyin branch, 1 glyph branch, 2 weight-gradient stream; -1 high, 0 default, +1 low (read at stream creation)

@@ -55,15 +55,6 @@ void set_cls_compact(int on) { g_cls_compact = on; }
 // Split-K of the classifier's data gradient (realise_set_engine key 6; bf16, compacted rows): K = 21184 vocabulary columns, N = 768,
 // ~4.9 k live rows are 156 tiles of 128 x 192 on 512 workgroup slots - three K-ranges fill them (468), the fp32 partial planes are
 // folded in plane order by the scatter that follows anyway.  0 = off (one launch over the whole K).
-// K4 (realise_set_engine key 8): BertSelfOutput / BertOutput as ONE launch - dense + bias + dropout + residual + LayerNorm (bf16,
-// the 128 x 192 two-per-CU kernel: the four column tiles of a row band exchange their LayerNorm partial sums through self-validating
-// device-scope slots).  0 (DEFAULT) = the GEMM and the LayerNorm as two launches; 1 = fused; 2 = fused without the hand-off (diagnostics).
-// Measured and left OFF (profiles/round4_ab.log, round4_repro_probe.log): the first form (normalise by re-reading the tile from LDS) was
-// perf-neutral (17.50 vs 17.55 ms; alone 53 us against 41 + 9) but one launch in ~2000 left that re-read with a wrong element in one
-// aligned 16-lane group; the shipped form normalises from registers - 1400 forwards bit-identical - but its 96-byte-per-thread store
-// pattern makes the step 0.3 ms SLOWER than the two launches (17.69 vs 17.40 ms).  Passes every parity test either way.
-static int g_ln_fuse = 0;
-void set_ln_fuse(int on) { g_ln_fuse = on; }
 // K6 (realise_set_engine key 9): a GRU time step t > 0 as ONE launch - the recurrent projection with the gate math in its epilogue
 // (bf16; gemm_nt8_gru).  0 = GEMM + gru_step_fwd.
 static int g_gru_fuse = 1;
@@ -87,16 +78,6 @@ void set_cls_splitk(int n) { g_cls_splitk = n < 0 ? 0 : (n > 4 ? 4 : n); }
 // 1 = the round-4 / 5 form (16-row blocks), 0 = dense.
 static int g_live_rows = 2;
 void set_live_rows(int on) { g_live_rows = on; }
-// realise_set_engine(11, v): 1 = the layer GEMMs of the transformer stacks on the stream-K 256 x 192 kernel (gemm_nt8s.hip) where its
-// one-round launch has at least g_streamk_min (realise_set_engine(12, n), default 10) K-tiles per workgroup to share out; 0 (default): the
-// 128 x 192 two-per-CU kernels only.  Measured (tools/streamk_probe.py, profiles/round5_streamk_probe.log): correct, reproducible,
-// and slower than the two-per-CU kernel on every layer shape - DESIGN.md section 6.6.
-// Round 6: the kernel lives in the PROBE build only (librealise_hip_probes.so, python -m realise_amd.build --probes), like every other
-// measured-and-rejected variant; in the production library the knob stays 0 and no exchange buffers are planned.
-static int g_streamk = 0;
-static int g_streamk_min = 10;
-void set_streamk(int v) { g_streamk = (RL_PROBES && v > 0) ? 1 : 0; }
-void set_streamk_min(int n) { g_streamk_min = n > 0 ? n : 0; }
 // K7 (realise_set_engine key 13, default 1; models.py:831-834): the glyph lookup `char_images_multifonts.index_select(0, ids)` is fused
 // into the loaders of block 1's two forward convolutions - they gather the 3x3 / 1x1 taps straight from the NHWC glyph table through
 // the list of distinct ids (ConvLoader::img_index: one index load per 8-row piece in the tile prologue, nothing in the K loop) - so
@@ -177,8 +158,6 @@ template <typename T> struct Engine : EngineBase {
     BlockAct blk[5];
     int64_t mask_add, out_d, dlogits, count, loss_internal;
     int64_t cls_act, cls_inv, cls_nact, cls_xc, cls_gc, cls_slab;
-    int64_t sk_part[3] = {0, 0, 0}, sk_flag[3] = {0, 0, 0};       // stream-K GEMMs: exchange buffer + workgroup flags, one set per stack (= stream)
-    int64_t ln_part[3] = {0, 0, 0}, ln_flag[3] = {0, 0, 0};       // fused GEMM + LayerNorm: per-row tile partials + arrival counters, one set per stack (= stream)
     int64_t live_rows = 0;                // ascending list of the live rows (row-granular layer GEMMs)
     int64_t row_live, live_t64, live_t32, live_t16, live_n, live_rlen;          // padding rows: exact-zero gradient rows the backward skips (row_liveness)     // classifier backward over the rows that enter the loss only (stage_head)
     int64_t ids_clean = 0, pho_clean = 0;                 // range-checked copies of src_idx / pho_idx (sanitize_ids)
@@ -268,8 +247,6 @@ template <typename T> struct Engine : EngineBase {
   int live_list_rows() const { return sizeof(T) == 2 ? (live16() ? 16 : 64) : 32; }
   bool rows_live = false;                  // the last forward ran its layer GEMMs over the live 16-row blocks (g_live_rows); the backward follows
   // a layer GEMM over the token rows: the live blocks of a live-row step (no dense fall-back: the dead rows of its operands are stale)
-  int nt_sid = -1;                         // stack whose layers are being enqueued (stack_forward / layers_backward): selects the stream-K buffers
-  unsigned sk_epoch[3] = {0, 0, 0};
   // whole_blocks: the output is the dY operand of a weight-gradient reduction, which walks whole live 16-row BLOCKS - its rows behind a
   // sentence's last live row inside such a block must be (re)computed (exact zeros: their dY inputs are LayerNorm-backward zeros), not
   // left stale, so that launch keeps the block list (the GELU' data gradient of BertOutput, one of a layer's eight GEMMs).
@@ -278,20 +255,6 @@ template <typename T> struct Engine : EngineBase {
       EpiParams<T> e2 = ep;
       if (rows_live && g_live_rows == 2 && !whole_blocks) { e2.live_list = wp<int>(pl.live_rows); e2.live_count = wp<int>(pl.live_n) + 3; e2.live_unit = 1; }
       else if (rows_live) { e2.live_list = wp<int>(pl.live_t16); e2.live_count = wp<int>(pl.live_n) + 2; }
-      // one round of 256 workgroups over 256 x 192 tiles (stream-K) where there is enough to share out; a stack's launches are
-      // serialised by its stream, so one exchange buffer per stack does
-#if RL_PROBES
-      if (g_streamk && nt_sid >= 0 && nt_sid < 3 && pl.sk_part[nt_sid] != 0 &&
-          (int64_t)((M + 255) / 256) * ((N + 191) / 192) * (K / 64) >= (int64_t)g_streamk_min * NT8S_GRID) {
-        e2.sk_part = wp<float>(pl.sk_part[nt_sid]); e2.sk_flag = wp<int>(pl.sk_flag[nt_sid]);
-        e2.sk_tag = (int)(sk_epoch[nt_sid] % 0x7FFFFFF0u) + 1;
-        e2.sk_timeout = id_flag != nullptr ? id_flag + 1 : nullptr;
-        const int rc = gemm_nt8s(st, A, lda, B, ldb, M, N, K, e2);
-        if (rc == RL_OK) { ++sk_epoch[nt_sid]; return RL_OK; }
-        if (rc != RL_ERR_ARG) return rc;
-        e2.sk_part = nullptr; e2.sk_flag = nullptr; e2.sk_tag = 0; e2.sk_timeout = nullptr;
-      }
-#endif
       if (rows_live) return gemm_nt8_live(st, A, lda, B, ldb, M, N, K, e2);
     }
     return gemm_nt<T>(st, A, lda, B, ldb, M, N, K, ep);
@@ -612,16 +575,6 @@ template <typename T> struct Engine : EngineBase {
     p.cls_xc = b.take(Tk * H * e); p.cls_gc = b.take(Tk * H * e);
     p.zero_once.push_back({p.cls_xc, Tk * H * e}); p.zero_once.push_back({p.cls_gc, Tk * H * e});
     p.cls_slab = (!glyph_only && sizeof(T) == 2) ? b.take(4 * Tk * H * 4) : 0;      // fp32 planes of the split-K classifier data gradient
-    if (!glyph_only && sizeof(T) == 2) {
-      for (int k = 0; k < 3; ++k) {
-        if (g_streamk) {       // (default off, DESIGN 6.6: 150 MB of exchange buffers are planned only for a plan built with the knob set)
-          p.sk_part[k] = b.take(NT8S_PART_BYTES); p.sk_flag[k] = b.take((int64_t)NT8S_GRID * NT8S_FLAG_STRIDE * 4 + 256);      // (flags: zero with the workspace; tags are never 0)
-        }
-        p.ln_part[k] = b.take(Tk * 8 * 2 * 8);
-        p.ln_flag[k] = 0;
-        p.zero_once.push_back({p.ln_part[k], Tk * 8 * 2 * 8});
-      }
-    }
     // shared backward scratch
     p.gA = b.take(Tk * H * e); p.gB = b.take(Tk * H * e); p.gC = b.take(Tk * H * e); p.gE = b.take(Tk * H * e);
     const int64_t Tw = glyph_only ? 1 : Tk;               // the wide BERT scratch is not needed by the glyph-only plan
@@ -723,7 +676,7 @@ template <typename T> struct Engine : EngineBase {
   // there.  A caller that keeps one buffer per (B, S, Tp) key - modeling.py: train batch, eval batch, the short last batch, the
   // glyph-only plan - pays the zero fill of install_plan ONCE per key; re-binding a remembered buffer restores its plan as it was.
   // forget_workspace() before the caller frees a buffer (an allocator may hand the same address out again).
-  struct Slot { char* ws; int64_t bytes; Plan pl; std::map<std::string, std::pair<int64_t, int64_t>> taps; int ln_epoch[3]; unsigned sk_epoch[3]; uint64_t stamp; };
+  struct Slot { char* ws; int64_t bytes; Plan pl; std::map<std::string, std::pair<int64_t, int64_t>> taps; uint64_t stamp; };
   std::vector<Slot> slots;
   uint64_t slot_clock = 0;
   static constexpr size_t MAX_SLOTS = 8;
@@ -741,7 +694,6 @@ template <typename T> struct Engine : EngineBase {
       s = &slots.back();
     }
     s->ws = ws; s->bytes = ws_bytes; s->pl = pl; s->taps = taps; s->stamp = ++slot_clock;
-    for (int k = 0; k < 3; ++k) { s->ln_epoch[k] = ln_epoch[k]; s->sk_epoch[k] = sk_epoch[k]; }
   }
   int bind(void* shadow, void* workspace, int64_t bytes) override {
     // everything the engine keeps inside the caller's shadow buffer (operand copies, the cast descriptor table, the chunk table of the
@@ -749,11 +701,9 @@ template <typename T> struct Engine : EngineBase {
     if (shadow != (void*)sh) { glyph_built = false; descs_built = false; fill_built = false; n_fill = 0; skip_built = false; }
     stash_current();
     sh = (char*)shadow; ws = (char*)workspace; ws_bytes = bytes; pl = Plan(); have_fwd = false; have_glyph_fwd = false;
-    ln_epoch[0] = ln_epoch[1] = ln_epoch[2] = 0;
     for (Slot& x : slots)
       if (x.ws == ws && x.bytes == bytes) {
         pl = x.pl; taps = x.taps; x.stamp = ++slot_clock;
-        for (int k = 0; k < 3; ++k) { ln_epoch[k] = x.ln_epoch[k]; sk_epoch[k] = x.sk_epoch[k]; }
         break;
       }
     return RL_OK;
@@ -787,7 +737,6 @@ template <typename T> struct Engine : EngineBase {
   int stack_forward(hipStream_t st, int sid, const StackOff& so, const std::vector<LayerSh>& shs, StackAct& a,
                     const int64_t* ids, const T* embeds, int pos_zero, const T** out) {
     const int B = pl.B, S = pl.S, Tk = B * S;
-    nt_sid = sid;
     {
       LnFwdArgs<T> ln;
       ln.rows = Tk; ln.H = H; ln.S = S;
@@ -821,7 +770,7 @@ template <typename T> struct Engine : EngineBase {
                            d.seed, d.thresh, d.scale, rows_live ? live_rlen() : nullptr));
       }
       // BertSelfOutput: dense -> dropout -> + input -> LayerNorm (modeling_bert.py:273-277)
-      RL_TRY(dense_resid_ln(st, sid, wp<T>(t.ctx), H, sp<T>(w.ao_w), pp(o.ao_b), x, site(sid * 1000 + (int)l * 10 + 2, cfg.hidden_dropout),
+      RL_TRY(dense_resid_ln(st, wp<T>(t.ctx), H, sp<T>(w.ao_w), pp(o.ao_b), x, site(sid * 1000 + (int)l * 10 + 2, cfg.hidden_dropout),
                             pp(o.ao_ln_g), pp(o.ao_ln_b), wp<T>(t.s1), wp<float>(t.rstd1), wp<T>(t.y1)));
       {  // BertIntermediate (modeling_bert.py:326-329)
         // (the pre-activation is what the backward's GELU' reads: a forward nothing differentiates - evaluation, no_grad - does not store it)
@@ -829,7 +778,7 @@ template <typename T> struct Engine : EngineBase {
         RL_TRY(nt_rows(st, wp<T>(t.y1), H, sp<T>(w.in_w), H, Tk, I, H, ep));
       }
       // BertOutput (modeling_bert.py:339-343)
-      RL_TRY(dense_resid_ln(st, sid, wp<T>(t.post), I, sp<T>(w.out_w), pp(o.out_b), wp<T>(t.y1), site(sid * 1000 + (int)l * 10 + 3, cfg.hidden_dropout),
+      RL_TRY(dense_resid_ln(st, wp<T>(t.post), I, sp<T>(w.out_w), pp(o.out_b), wp<T>(t.y1), site(sid * 1000 + (int)l * 10 + 3, cfg.hidden_dropout),
                             pp(o.out_ln_g), pp(o.out_ln_b), wp<T>(t.s2), wp<float>(t.rstd2), wp<T>(t.y2)));
       x = wp<T>(t.y2);
     }
@@ -867,7 +816,6 @@ template <typename T> struct Engine : EngineBase {
   int layers_backward(hipStream_t st, int sid, const StackOff& so, const std::vector<LayerSh>& shs, StackAct& a, int hi, int lo,
                       T* gA) {
     const int B = pl.B, S = pl.S, Tk = B * S;
-    nt_sid = sid;
     const typename Plan::Scratch& sc = pl.sc[cs];
     T* gB = wp<T>(sc.gB); T* gE = wp<T>(sc.gE);
     const bool ov = g_wgrad_overlap && (!branch_mode || cs == 0) && side_ok();      // under branch overlap only the bert branch owns two dY sets
@@ -1254,28 +1202,13 @@ template <typename T> struct Engine : EngineBase {
   }
 
   // ---------------------------------------------------------------- forward
-  // a freshly planned workspace: the self-cleaning LayerNorm-backward accumulators start at zero
-  int ln_epoch[3] = {0, 0, 0};
-  // dense -> dropout -> + residual -> LayerNorm (modeling_bert.py:273-277, 339-343): one launch when the fused form applies
+  // dense -> dropout -> + residual -> LayerNorm (modeling_bert.py:273-277, 339-343)
   // the forward being enqueued is one a backward can follow (realise_engine_backward checks the same): it must leave what that pass reads
   bool bwd_follows() const { return last.training && last.tgt_idx != nullptr && last.want_dlogits; }
-  int dense_resid_ln(hipStream_t st, int sid, const T* a, int K, const T* w, const float* bias, const T* resid, const DropParams& drop,
+  int dense_resid_ln(hipStream_t st, const T* a, int K, const T* w, const float* bias, const T* resid, const DropParams& drop,
                      const float* gamma, const float* beta, T* s_xhat, float* rstd, T* y) {
     const int Tk = pl.B * pl.S;
     EpiParams<T> ep; ep.mode = EPI_DROP_RESID; ep.out = s_xhat; ep.ldo = H; ep.bias = bias; ep.aux = resid; ep.ldaux = H; set_drop(ep, drop);
-    if constexpr (sizeof(T) == 2) {
-      if (g_ln_fuse && !rows_live && sid >= 0 && sid < 3 && pl.ln_part[sid] != 0 && (Tk % 128) == 0 && (H % 192) == 0) {
-        EpiParams<T> e2 = ep;
-        e2.ln_gamma = gamma; e2.ln_beta = beta; e2.ln_eps = cfg.ln_eps; e2.ln_y = y; e2.ln_rstd = rstd;
-        e2.ln_part = wp<float>(pl.ln_part[sid]);
-        if (g_ln_fuse == 2) e2.ln_flag = (int*)e2.ln_part;       // diagnostics: no cross-tile hand-off (see nt8_ln_epilogue)
-        e2.ln_target = (ln_epoch[sid] % 0x7FFFFFF0) + 1;          // launch tag: never 0 (the zero-filled buffer), != the previous launch's
-        e2.ln_timeout = id_flag != nullptr ? id_flag + 1 : nullptr;
-        const int rc = gemm_nt8_ln(st, a, K, w, K, Tk, H, K, e2);
-        if (rc == RL_OK) { ++ln_epoch[sid]; return RL_OK; }
-        if (rc != RL_ERR_ARG) return rc;
-      }
-    }
     RL_TRY(nt_rows(st, a, K, w, K, Tk, H, K, ep));
     LnFwdArgs<T> ln; ln.rows = Tk; ln.H = H; ln.x = s_xhat; ln.gamma = gamma; ln.beta = beta;
     ln.eps = cfg.ln_eps; ln.y = y; ln.xhat = bwd_follows() ? s_xhat : nullptr; ln.rstd = rstd;      // (a forward nothing differentiates does not store the normalised rows)
@@ -1288,7 +1221,6 @@ template <typename T> struct Engine : EngineBase {
     if (p.total > ws_bytes) { fprintf(stderr, "[realise_hip] workspace too small: need %lld have %lld\n", (long long)p.total, (long long)ws_bytes); return RL_ERR_ARG; }
     pl = p;
     ++plan_installs;
-    ln_epoch[0] = ln_epoch[1] = ln_epoch[2] = 0;           // (the arrival counters are zero-filled below)
     // The whole workspace starts at zero (once per plan): the self-cleaning accumulators need it (zero_once), and a live-row step
     // leaves the activation rows of padding tokens as they are - what they hold must be finite wherever a later pass multiplies it by
     // an exact zero (masked mean, gate gradients).

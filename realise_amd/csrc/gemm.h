@@ -29,7 +29,6 @@ template <typename T> struct EpiParams {
   // (n, 2*yy + py, 2*xx + px) of an [N][2^(hw-w)][2^w] map, r = (n, yy, xx) over the half-resolution grid; rm_hw_shift < 0: identity
   int rm_hw_shift = -1, rm_w_shift = 0, rm_par = 0;
   int wide = 0;                 // set by the launcher: rows are 8-element aligned -> LDS-staged epilogue, 16 B per lane
-  int probe = 0;                // diagnostics (tools/nt_probe.cpp): 1 all tiles fetch tile 0, 2 no fetches, 3 no MFMA
   // optional device-side count of the rows that matter (the 8-wave kernel skips tiles that start at or beyond it; rows of a partly
   // live tile beyond the count are still computed and stored: for outputs whose dead rows nobody reads - the compacted classifier
   // data gradient, engine.hip stage_head)
@@ -72,24 +71,7 @@ template <typename T> struct EpiParams {
   // 256 x 192 kernel only: gemm_nt8p; every other launch form refuses it)
   float* out_f32 = nullptr;
   int64_t ldo_f32 = 0;
-  int l2_prefetch = 0;          // set by the launcher (realise_set_nt8p key 8, probe): surplus workgroups of a narrow row-list launch prefetch their XCD's operand lines into the L2
-  int cu_pair = 0;              // set by the launcher (realise_set_nt8p key 7): tile order that puts two column tiles of a tile row on one CU (common.h cu_pair_local)
-  int bias_first = 0;           // set by the launcher (realise_set_nt8p key 4): alpha / bias go into the accumulators before the epilogue's LDS transposes
-  // K4 (BertSelfOutput / BertOutput, modeling_bert.py:273-277, 339-343): EPI_DROP_RESID followed by the LayerNorm of the row in the SAME
-  // launch (8-wave 128 x 192 kernel, M % 128 == 0, N % 192 == 0, N / 192 <= 8).  A row spans N / 192 column tiles = workgroups: each
-  // leaves (sum, M2) of its 192 columns in ln_part[row][tile] as two self-validating 64-bit words {value, tag = ln_target} and polls
-  // the other tiles' slots until they carry this launch's tag (the caller passes a tag that differs from the previous launch's on the
-  // same buffer, never 0); then every workgroup combines the partials (Chan), normalises its own columns from LDS and writes
-  // xhat -> out, y -> ln_y, rstd -> ln_rstd.
-  const float* ln_gamma = nullptr;
-  const float* ln_beta = nullptr;
-  float ln_eps = 0.f;
-  T* ln_y = nullptr;
-  float* ln_rstd = nullptr;
-  float* ln_part = nullptr;       // [M][N / 192][2] 64-bit words (16 B per row and tile), zero-filled once
-  int* ln_flag = nullptr;         // (unused)
-  int ln_target = 0;              // launch tag
-  int* ln_timeout = nullptr;      // nullable: set to 1 if a wait gave up (a workgroup of the band never arrived)
+  int bias_first = 0;           // set by the launcher from the shape: alpha / bias go into the accumulators before the epilogue's LDS transposes
   // K6 (models.py:818-826, one time step of nn.GRU): the recurrent projection gh = h_prev . W_hh^T + b_hh with the gate math in its
   // epilogue (8-wave 128 x 192 kernel, N = 3H).  The B rows of a column tile are gathered gate-interleaved - [r | z | n] of 32 hidden
   // units per wave - so that a wave's staged tile holds all three gates of its units: r = sigmoid(gi_r + gh_r), z = sigmoid(gi_z +
@@ -104,17 +86,7 @@ template <typename T> struct EpiParams {
   T* gru_gh = nullptr;                  // [M][3H]: only the n third is written
   T* gru_out = nullptr;                 // [N tokens][H], original order
   int gru_Tp = 0, gru_t = 0;
-  // Stream-K form (gemm_nt8s): the exchange buffer of the launch (NT8S_PART_BYTES, private to the stream while the launch runs), one
-  // flag per workgroup (NT8S_GRID x NT8S_FLAG_STRIDE ints, zero-filled once), the launch tag (never 0, different from the previous launch's on the same
-  // buffers) and an optional word that is set to 1 if a finisher gave up waiting for a partial
-  float* sk_part = nullptr;
-  int* sk_flag = nullptr;
-  int sk_tag = 0;
-  int* sk_timeout = nullptr;
 };
-constexpr int NT8S_GRID = 256;                                    // one workgroup per CU
-constexpr int NT8S_FLAG_STRIDE = 64;                              // ints between two workgroups' flags (256 B: different memory channels)
-constexpr int64_t NT8S_PART_BYTES = (int64_t)NT8S_GRID * 24 * 512 * 16;      // 256 x 192 fp32 per workgroup
 
 // ---- operand loaders ---------------------------------------------------------------------------
 // A loader maps (row, k) of a logical K-contiguous operand to the global address of a 16-byte chunk
@@ -379,7 +351,6 @@ struct TnEpi {
   float* colsum = nullptr;
   int overwrite = 0;        // TN_OUT_DIRECT only: out = result instead of out += result (the caller knows `out` holds nothing yet:
                             // no read of the old value, no zero-fill before the pass)
-  int probe = 0;            // diagnostics (tools/nt_probe.cpp): 2 no fetches, 3 no MFMA, 4 no fold pass
   // Optional list of the LIVE reduction tiles (unsplit dense reductions only): tile_list[t] = index of the t-th BP-row block of the
   // reduction rows that holds anything but exact zeros in A (BP = 64 bf16 / 32 fp32 rows, P % BP == 0), *n_tiles = how many.  The
   // rows of the other blocks are skipped - the gradient rows of padding tokens are exact zeros (engine.hip row_liveness).
@@ -399,11 +370,10 @@ template <typename T> struct TnGroupProblem {
   float* out = nullptr; int64_t ldo = 0;        // fp32 [I, ldo], accumulated; ldo % 4 == 0
   float* colsum = nullptr;                      // nullable: += column sums of A (bias gradient)
   int tiles_j = 0, ntiles = 0, tile_begin = 0;  // filled by gemm_tn_group
-  int jmajor = 0;                               // filled by gemm_tn_group: tiles walked j-panel by j-panel (the B operand is the larger one)
 };
 template <typename T> struct TnGroup {
   TnGroupProblem<T> p[TN_GROUP_MAX];
-  int n = 0, total_tiles = 0, probe = 0, overwrite = 0;
+  int n = 0, total_tiles = 0, overwrite = 0;
   float alpha = 1.0f;
   const int* tile_list = nullptr;      // live reduction tiles (see TnEpi)
   const int* n_tiles = nullptr;
@@ -413,8 +383,6 @@ template <typename T>
 int gemm_tn_group(hipStream_t st, int n, const TnGroupProblem<T>* probs, int P, float alpha = 1.0f, int overwrite = 0,
                   const int* tile_list = nullptr, const int* n_tiles = nullptr, int list_rows = 0);
 
-// K4: GEMM + bias + dropout + residual + LayerNorm in one launch (gemm_nt8.hip, see EpiParams::ln_*); RL_ERR_ARG = shape not supported
-int gemm_nt8_ln(hipStream_t st, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, int M, int N, int K, const EpiParams<bf16_t>& ep);
 // K6: one GRU time step = recurrent GEMM + gate math in one launch (EpiParams::gru_*); H = N / 3 must be a multiple of 64
 int gemm_nt8_gru(hipStream_t st, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, int M, int N, int K, const EpiParams<bf16_t>& ep);
 // Split-K NT GEMM (bf16, K % 64 == 0, nsplit <= K / 64): slab[s][m][n] (fp32, row pitch N, plane pitch slab_stride) = A[m, Ks] . B[n, Ks]^T
@@ -438,51 +406,28 @@ int gemm_tn(hipStream_t st, const T* A, int64_t lda, const T* B, int64_t ldb, in
 template <typename T>
 int gemm_tn_conv(hipStream_t st, const T* A, int64_t lda, const ConvLoader<T>& lb, int P, int I, int J, const TnEpi& ep);
 
-// Ping-pong 8-wave kernel (gemm_nt8.hip): bf16, dense operands, K % 64 == 0.  tile: 0 heuristic, 1 256x256, 2 256x192,
-// 3 256x128, 4 128x192.
+// Ping-pong 8-wave kernel (gemm_nt8.hip): bf16, dense operands, K % 8 == 0.  tile: 0 from the shape, 2 256x192, 4 128x192,
+// 6 128x192 two workgroups per CU.
 bool nt8_supported(int M, int N, int K, const EpiParams<bf16_t>& ep, int64_t lda, int64_t ldb);
 // persistent 256 x 192 kernel with the LDS-free epilogue (gemm_nt8p.hip): EPI_STORE / EPI_GELU / EPI_GELU_BWD, K % 64 == 0
 bool nt8p_supported(int M, int N, int K, const EpiParams<bf16_t>& ep, int64_t lda, int64_t ldb);
 int gemm_nt8p(hipStream_t st, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, int M, int N, int K, const EpiParams<bf16_t>& ep);
-// stream-K persistent 256 x 192 kernel (gemm_nt8s.hip): one round of NT8S_GRID workgroups over equal K-tile ranges, partial tiles folded
-// in-kernel in a fixed order; optional live-block list; EPI_STORE (+ accumulate) / EPI_GELU / EPI_GELU_BWD / EPI_DROP_RESID, K % 128 == 0
-bool nt8s_supported(int M, int N, int K, const EpiParams<bf16_t>& ep, int64_t lda, int64_t ldb);
-int gemm_nt8s(hipStream_t st, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, int M, int N, int K, const EpiParams<bf16_t>& ep);
 void set_nt8p_wgs(int n);
-void set_nt8_epi_pre(int on);      // 1 (default): alpha / bias into the accumulators before the 8-wave kernels' epilogue transposes (one bias fetch per wave, no per-item waits)
-void set_nt8_l2_prefetch(int v);  // realise_set_nt8p key 8 (probe): see gemm_nt8.hip nt8_l2_prefetch
-void set_nt8_cu_pair(int on);    // realise_set_nt8p key 7 (probe): two-per-CU 8-wave kernels pair the column tiles of a tile row on one CU
-void set_tn_jmajor(int on);       // realise_set_nt8p key 6: grouped weight gradients walk a problem's tiles along its LARGER operand's panels (1; default 0: measured level)
-void set_nt8_live_big(int v);     // measurement knob (realise_set_nt8p key 5): wide row-list launches on 256 x 256 one-per-CU tiles
 void set_nt8_live_gc(int gc);      // live-row GEMMs: 0 (default) column groups of the XCD split from the shape, 1 / 2 / 4 / 8 forced
 void set_nt8p_order(int o);
-void set_nt8_single_round(int on);   // outputs of at most one 128 x 192 tile per CU: 1 the three-stage one-per-CU shape, 0 (default) the two-per-CU shape
 int gemm_nt8(hipStream_t st, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, int M, int N, int K,
              const EpiParams<bf16_t>& ep, int tile);
-void set_nt8_probe(int mode);
-void set_nt8_group_m(int g);       // tile order of the 8-wave NT kernels: 0/1 row-major, g > 1: g tile rows per column step (L2 blocking)             // 2 no fetches, 3 no MFMA / fragment reads (results wrong)
+void set_nt8_group_m(int g);       // tile order of the 8-wave NT kernels: 0/1 row-major, g > 1: g tile rows per column step (L2 blocking)
 
-// Ping-pong 8-wave weight-gradient kernel (gemm_tn8.hip): bf16, dense operands, 256 x 128 output tiles, split reduction + fold
-bool tn8_supported(int64_t lda, int64_t ldb, int P, int I, int J, const TnEpi& ep);
-// grouped 8-wave form (gemm_tn8.hip): 256 x 128 tiles, one per CU, unsplit, optional list of live 16-row blocks; RL_ERR_ARG = not applicable
-int gemm_tn8_group(hipStream_t st, int n, const TnGroupProblem<bf16_t>* probs, int P, float alpha, int overwrite, const int* tile_list,
-                   const int* n_tiles, int list_rows);
-void set_tn_group8(int on);      // transformer-layer weight gradients through gemm_tn8_group (default 0: measured slower)
-int gemm_tn8(hipStream_t st, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, int P, int I, int J, const TnEpi& ep, int force_split);
 void tn_fold_launch(hipStream_t st, const TnEpi& ep, int nsplit, int I, int J);     // out += alpha * sum of the split slabs, fixed order
-void set_tn_variant(int v);
 void set_conv_c64(int on);          // 1 (default): 64-channel 3x3 s1 conv forward / dgrad / wgrad on 16x16 maps via the LDS-resident kernels
 int conv_c64_nt(hipStream_t st, const bf16_t* X, const bf16_t* Wt, bf16_t* out, int rows, const int* rows_dev, int flip,
                 const float* col_scale = nullptr, const float* col_shift = nullptr, const bf16_t* aux = nullptr, int relu = 0);         // conv_c64_nt.hip
 int conv_wgrad_c64(hipStream_t st, const bf16_t* dY, const bf16_t* X, int rows, const int* rows_dev, const TnEpi& te);   // conv_wgrad_c64.hip
-void set_tn_group_ring(int on);     // grouped TN: 0 two full stages (default), 1 four stages of half-height K-tiles (measured 11 % slower)               // 0 production, 9 force the 4-wave TN kernel
 
 void set_tn_transpose_read(int use_tr);
-void set_nt_wide_epilogue(int on);        // A/B knob: LDS-staged 16-B-per-lane epilogue (default on)
-void set_tn_probe(int mode);
 void set_tn_split(int n);                 // force the reduction split of the TN kernel (0 = heuristic)
-void set_nt_variant(int v);               // experimental NT tile shapes, 0 = production heuristic
-void set_nt_probe(int mode);              // bottleneck probe of the NT kernel, 0 = off (results are wrong when on)
+void set_nt_variant(int v);               // force one of the shipped NT kernels (0, 9, 12, 14, 16, 50, 51), 0 = from the shape
 void set_nt_allow_n96(int on);            // allow the 128x96 NT tile (chip-balance heuristic), default on
 
 }  // namespace rl

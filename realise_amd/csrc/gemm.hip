@@ -78,18 +78,17 @@ gemm_nt_kernel(ALoader la, DenseLoader<T> lb, int M, int N, int K, int tiles_n, 
   constexpr bool kDenseA = sizeof(typename ALoader::KPos) == sizeof(typename DenseLoader<T>::KPos);
   typename ALoader::Ctx actx[kDenseA ? NA : 1];
   typename DenseLoader<T>::Ctx bctx[NB];
-  const int m0f = (RL_PROBES && ep.probe == 1) ? 0 : m0, n0f = (RL_PROBES && ep.probe == 1) ? 0 : n0;
   if constexpr (kDenseA) {
 #pragma unroll
-    for (int j = 0; j < NA; ++j) actx[j] = la.prepare(m0f + (wave * NA + j) * 8 + lrow);
+    for (int j = 0; j < NA; ++j) actx[j] = la.prepare(m0 + (wave * NA + j) * 8 + lrow);
   }
 #pragma unroll
-  for (int j = 0; j < NB; ++j) bctx[j] = lb.prepare(n0f + (wave * NB + j) * 8 + lrow);
+  for (int j = 0; j < NB; ++j) bctx[j] = lb.prepare(n0 + (wave * NB + j) * 8 + lrow);
   typename ALoader::KPos aq = la.kpos(kchunk);
   typename DenseLoader<T>::KPos bq = lb.kpos(kchunk);
   // gathered (implicit-im2col) A operand: 32-bit buffer addressing, see ConvLoader::Row32 / Tap32
   ConvRows<ALoader, NA> crow;
-  if constexpr (!kDenseA) crow.init(la, m0f + wave * NA * 8 + lrow, kchunk);
+  if constexpr (!kDenseA) crow.init(la, m0 + wave * NA * 8 + lrow, kchunk);
   const int nk = (K + G::BK - 1) / G::BK;
   // Fast addressing for the K-tiles that lie completely inside K: each lane keeps one 64-bit source pointer per
   // wave-instruction and just adds the K-tile stride (0 for lanes parked on the zero page).  A ragged last tile
@@ -122,7 +121,6 @@ gemm_nt_kernel(ALoader la, DenseLoader<T> lb, int M, int N, int K, int tiles_n, 
     for (int j = 0; j < NF; ++j) acc[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
 
   auto issue = [&](int stage) {                      // fetch the next K-tile, then advance the positions
-    if (RL_PROBES && ep.probe == 2) return;
     char* base = smem + stage * STAGE;
     const bool f = kt_issue < nfast;                 // this tile is addressed by pointer stepping
     if constexpr (!kDenseA) {
@@ -181,11 +179,10 @@ gemm_nt_kernel(ALoader la, DenseLoader<T> lb, int M, int N, int K, int tiles_n, 
     const bool more = kt + NSTAGE - 1 < nk;
     const int nstage = (kt + NSTAGE - 1) % NSTAGE;
     constexpr bool kSpread = SPREAD && kDenseA && sizeof(T) == 2;
-    const bool spread = kSpread && fast_all && (!RL_PROBES || ep.probe == 0);
+    const bool spread = kSpread && fast_all;
     if (more && !spread) issue(nstage);
     const char* As = smem + (kt % NSTAGE) * STAGE;
     const char* Bs = As + A_BYTES;
-    if (RL_PROBES && ep.probe == 3) continue;
 #pragma unroll
     for (int ks = 0; ks < G::KSTEPS; ++ks) {
       typename Mma::Frag a[4], b[NF];
@@ -233,164 +230,15 @@ gemm_nt_kernel(ALoader la, DenseLoader<T> lb, int M, int N, int K, int tiles_n, 
       epilogue4<T>(ep, M, N, m0 + wm * 64 + i * 16 + l15, n0 + wn * 16 * NF + j * 16 + 4 * g, acc[i][j]);
 }
 
-static int g_tn_jmajor = 0;      // (measured: family 2.585 against 2.545 ms/step i-major, three pairs - fewer HBM bytes, not faster: off)
-void set_tn_jmajor(int on) { g_tn_jmajor = on; }
 static int g_nt_n96 = 1;             // allow 128x96 tiles (tuning / A-B knob)
 void set_nt_allow_n96(int on) { g_nt_n96 = on; }
-static int g_nt_probe = 0, g_nt_wide = 1, g_nt_variant = 0;
+static int g_nt_variant = 0;
 static int g_conv_c64 = 1;          // block-1 conv2 (64 channels, 16x16 maps) through the LDS-resident kernels conv_c64_nt.hip / conv_wgrad_c64.hip
 void set_conv_c64(int on) { g_conv_c64 = on; }
-void set_nt_variant(int v) { g_nt_variant = (RL_PROBES || v == 0 || v == 9 || v == 12 || v == 14 || v == 16 || v >= 50) ? v : 0; }     // production: 0, 9 (4-wave), 12 / 14 / 16 (the three shipped 8-wave tiles), 50 / 51 (persistent on / off)
-static int g_tn_probe = 0, g_tn_split = 0;
+// 0 (from the shape), 9 (4-wave), 12 / 14 / 16 (the three 8-wave tiles), 50 / 51 (persistent on / off); anything else: 0
+void set_nt_variant(int v) { g_nt_variant = (v == 9 || v == 12 || v == 14 || v == 16 || v == 50 || v == 51) ? v : 0; }
+static int g_tn_split = 0;
 void set_tn_split(int n) { g_tn_split = n; }
-void set_tn_probe(int mode) { g_tn_probe = RL_PROBES ? mode : 0; }
-void set_nt_wide_epilogue(int on) { g_nt_wide = on; }
-void set_nt_probe(int mode) { g_nt_probe = RL_PROBES ? mode : 0; set_nt8_probe(RL_PROBES ? mode : 0); }
-
-
-#if RL_PROBES
-// =================================================================================================
-// Phase-shifted 8-wave NT kernel (EXPERIMENTAL, variant 8 of realise_set_nt_variant): 256 x 128 tile, waves
-// 0-3 (group A) and 4-7 (group B) share the SIMDs pairwise and run half a K-tile out of phase - one group's MFMA phase
-// (32 MFMAs on register-resident fragments) covers the other's memory phase (fragment reads of a whole K-tile + its share
-// of the LDS-DMA fetches of tile t+2).  bf16, dense operands, K % 64 == 0.
-// =================================================================================================
-__global__ void __launch_bounds__(512, 1)
-gemm_nt_pp_kernel(DenseLoader<bf16_t> la, DenseLoader<bf16_t> lb, int M, int N, int K, int tiles_n, int ntiles, EpiParams<bf16_t> ep) {
-  typedef bf16_t T;
-  typedef MmaBF16 Mma;
-  constexpr int BM_ = 256, BN_ = 128, BK = 64, NST = 3;
-  constexpr int A_BYTES = BM_ * 128, B_BYTES = BN_ * 128, STAGE = A_BYTES + B_BYTES;
-  constexpr int NA = 4, NB = 2;                       // 1-KiB pieces per wave per tile (8 waves)
-  extern __shared__ __attribute__((aligned(16))) char smem[];
-  const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, l15 = lane & 15;
-  const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
-  const int grp = wave >> 2, wm = wave & 3, wn = grp;
-  const int tile = xcd_remap(blockIdx.x, ntiles);
-  const int tm = tile / tiles_n, tn = tile - tm * tiles_n;
-  const int m0 = tm * BM_, n0 = tn * BN_;
-  const void* zero = (const void*)g_zero16;
-  const int lrow = lane >> 3;
-  const int kchunk = ((lane & 7) ^ lrow) * 8;
-  const char* pa[NA];
-  const char* pb[NB];
-  int inca[NA], incb[NB];
-#pragma unroll
-  for (int j = 0; j < NA; ++j) {
-    const void* p0 = la.addr(la.prepare(m0 + (wave * NA + j) * 8 + lrow), la.kpos(kchunk), zero);
-    pa[j] = (const char*)p0; inca[j] = (p0 != zero) ? BK * 2 : 0;
-  }
-#pragma unroll
-  for (int j = 0; j < NB; ++j) {
-    const void* p0 = lb.addr(lb.prepare(n0 + (wave * NB + j) * 8 + lrow), lb.kpos(kchunk), zero);
-    pb[j] = (const char*)p0; incb[j] = (p0 != zero) ? BK * 2 : 0;
-  }
-  floatx4 acc[4][4];
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) acc[i][j] = floatx4{0.f, 0.f, 0.f, 0.f};
-  bf16x8_t fa[2][4], fb[2][4];
-
-  auto issue_tile = [&](int stage) {
-    char* base = smem + stage * STAGE;
-#pragma unroll
-    for (int j = 0; j < NA; ++j) { glds16(pa[j], base + (wave * NA + j) * 1024); pa[j] += inca[j]; }
-#pragma unroll
-    for (int j = 0; j < NB; ++j) { glds16(pb[j], base + A_BYTES + (wave * NB + j) * 1024); pb[j] += incb[j]; }
-  };
-  auto read_frags = [&](int stage) {
-    const char* As = smem + stage * STAGE;
-    const char* Bs = As + A_BYTES;
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-#pragma unroll
-      for (int i = 0; i < 4; ++i) fa[ks][i] = ktile_frag<T, 64>(As, wm * 64 + i * 16 + l15, ks, g);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) fb[ks][j] = ktile_frag<T, 64>(Bs, wn * 64 + j * 16 + l15, ks, g);
-    }
-  };
-  auto mma_all = [&]() {
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-      for (int i = 0; i < 4; ++i)
-#pragma unroll
-        for (int j = 0; j < 4; ++j) acc[i][j] = Mma::mma(fb[ks][j], fa[ks][i], acc[i][j]);
-  };
-#define RL_PP_BARRIER() do { __builtin_amdgcn_s_barrier(); asm volatile("" ::: "memory"); } while (0)
-
-  const int nk = K / BK;
-  issue_tile(0);
-  if (nk > 1) { issue_tile(1); asm volatile("s_waitcnt vmcnt(6)" ::: "memory"); }
-  else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-  RL_PP_BARRIER();                                   // tile 0 landed for every wave
-  if (grp == 0) {                                    // half 1(0): group A's first memory phase
-    read_frags(0);
-    if (2 < nk) issue_tile(2 % NST);
-    asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-  }
-  RL_PP_BARRIER();
-  for (int t = 0; t < nk; ++t) {
-    // half 2(t): A multiplies tile t, B reads its fragments of tile t and fetches its share of tile t+2
-    if (grp == 0) {
-      mma_all();
-    } else {
-      read_frags(t % NST);
-      if (t + 2 < nk) issue_tile((t + 2) % NST);
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    }
-    if (t + 2 < nk) asm volatile("s_waitcnt vmcnt(6)" ::: "memory");     // own pieces of tile t+1 done (t+2 may fly)
-    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    RL_PP_BARRIER();
-    // half 1(t+1): A reads tile t+1 and fetches its share of tile t+3, B multiplies tile t
-    if (grp == 0) {
-      if (t + 1 < nk) {
-        read_frags((t + 1) % NST);
-        if (t + 3 < nk) issue_tile((t + 3) % NST);
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-      }
-    } else {
-      mma_all();
-    }
-    RL_PP_BARRIER();
-  }
-#undef RL_PP_BARRIER
-  if (ep.wide) {
-    constexpr int RS = 68, ITEMS = 8;
-    __syncthreads();
-    float* et = (float*)smem + wave * (64 * RS);
-#pragma unroll
-    for (int i = 0; i < 4; ++i)
-#pragma unroll
-      for (int j = 0; j < 4; ++j) *(floatx4*)(et + (i * 16 + l15) * RS + j * 16 + 4 * g) = acc[i][j];
-#pragma unroll
-    for (int t = 0; t < ITEMS; ++t) {
-      const int e = lane + 64 * t, r = e / ITEMS, c8 = e - r * ITEMS;
-      const floatx4 v0 = *(const floatx4*)(et + r * RS + c8 * 8), v1 = *(const floatx4*)(et + r * RS + c8 * 8 + 4);
-      epilogue8<T>(ep, M, N, m0 + wm * 64 + r, n0 + wn * 64 + c8 * 8, v0, v1);
-    }
-    return;
-  }
-#pragma unroll
-  for (int i = 0; i < 4; ++i)
-#pragma unroll
-    for (int j = 0; j < 4; ++j) epilogue4<T>(ep, M, N, m0 + wm * 64 + i * 16 + l15, n0 + wn * 64 + j * 16 + 4 * g, acc[i][j]);
-}
-static int launch_nt_pp(hipStream_t st, const DenseLoader<bf16_t>& la, const DenseLoader<bf16_t>& lb, int M, int N, int K,
-                        const EpiParams<bf16_t>& ep) {
-  const int tiles_m = (M + 255) / 256, tiles_n = (N + 127) / 128, ntiles = tiles_m * tiles_n;
-  const size_t lds = 3 * (size_t)(256 + 128) * 128;      // 144 KB ring >= 8 x 64 x 68 x 4 epilogue tiles
-  static bool attr_set = false;
-  if (!attr_set) { (void)hipFuncSetAttribute((const void*)gemm_nt_pp_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds); attr_set = true; }
-  ProfScope ps(st, PK_GEMM_NT, 2.0 * M * N * K);
-  EpiParams<bf16_t> epp = ep;
-  epp.wide = g_nt_wide && (N % 8 == 0) && (ep.ldo % 8 == 0) && (ep.aux == nullptr || ep.ldaux % 8 == 0);
-  RL_LAUNCH(gemm_nt_pp_kernel, dim3(ntiles), dim3(512), lds, st, la, lb, M, N, K, tiles_n, ntiles, epp);
-  return hipGetLastError() == hipSuccess ? RL_OK : RL_ERR_LAUNCH;
-}
-
-#endif  // RL_PROBES
 
 template <typename T, typename ALoader, int WM, int WN, int NSTAGE = 2, int NF = 4, bool SPREAD = false>
 static int launch_nt_tile(hipStream_t st, const ALoader& la, const DenseLoader<T>& lb, int M, int N, int K, const EpiParams<T>& ep) {
@@ -398,9 +246,7 @@ static int launch_nt_tile(hipStream_t st, const ALoader& la, const DenseLoader<T
   const int tiles_m = (M + BM_ - 1) / BM_, tiles_n = (N + BN_ - 1) / BN_;
   const int ntiles = tiles_m * tiles_n;
   const size_t ring = NSTAGE * (size_t)(BM_ + BN_) * 128, etile = (size_t)WM * WN * 64 * (16 * NF + 4) * 4;
-  // (NF = 6, round 6 probe: 128 x 192 on FOUR waves of 64 x 96 - the ring alone, 80 KB, so that two workgroups share a CU as the 8-wave
-  // 128 x 192 kernel's do; its epilogue then stores straight from the accumulator layout)
-  const size_t lds = (NF == 6 || ring > etile) ? ring : etile;        // the epilogue re-uses the ring as per-wave transpose tiles
+  const size_t lds = ring > etile ? ring : etile;        // the epilogue re-uses the ring as per-wave transpose tiles
   static bool attr_set = false;
   if (!attr_set) {
     (void)hipFuncSetAttribute((const void*)gemm_nt_kernel<T, ALoader, WM, WN, NSTAGE, NF, SPREAD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
@@ -410,8 +256,7 @@ static int launch_nt_tile(hipStream_t st, const ALoader& la, const DenseLoader<T
   if constexpr (sizeof(typename ALoader::KPos) == sizeof(typename DenseLoader<T>::KPos))      // (the conv families are scaled by the live-glyph fraction in bench.py)
     if (la.rows_dev != nullptr) prof_set_exec(la.rows_dev, 2.0 * N * K, BM_, M);   // device-side row bound: surplus tiles exit at once
   EpiParams<T> epp = ep;
-  epp.probe = g_nt_probe;
-  epp.wide = NF != 6 && g_nt_wide && (N % 8 == 0) && (ep.ldo % 8 == 0) && (ep.aux == nullptr || ep.ldaux % 8 == 0);
+  epp.wide = (N % 8 == 0) && (ep.ldo % 8 == 0) && (ep.aux == nullptr || ep.ldaux % 8 == 0);
   RL_LAUNCH((gemm_nt_kernel<T, ALoader, WM, WN, NSTAGE, NF, SPREAD>), dim3(ntiles), dim3(64 * WM * WN), lds, st, la, lb, M, N, K, tiles_n, ntiles, epp);
   return hipGetLastError() == hipSuccess ? RL_OK : RL_ERR_LAUNCH;
 }
@@ -432,21 +277,21 @@ static int launch_nt(hipStream_t st, const ALoader& la, const T* B, int64_t ldb,
     return bn * (tpc == 1 ? 1.0 : 0.75 * (double)tpc);
   };
   if constexpr (sizeof(typename ALoader::KPos) == sizeof(typename DenseLoader<T>::KPos) && sizeof(T) == 2) {
-    // Production path for the big dense GEMMs: the ping-pong 8-wave kernel (gemm_nt8.hip), tile by chip fill.  Variants 10..34
-    // force one of its tiles / issue flavours, variant 9 forces the 4-wave kernel below (tools/nt8_probe.cpp).
+    // Production path for the big dense GEMMs: the ping-pong 8-wave kernel (gemm_nt8.hip), tile by chip fill.  Variants 12 / 14 / 16
+    // force one of its tiles, variant 9 forces the 4-wave kernel below (tools/nt8_probe.cpp).
     // Wide outputs (qkv, FFN-up + GELU, FFN-down data gradient + GELU', the classifier: >= 1.5 tiles of 256 x 192 per CU): the persistent
     // kernel, whose register epilogue and next-tile prologue overlap what the one-tile kernels leave exposed (gemm_nt8p.hip).
     // Variant 50 forces it wherever it is supported, variant 51 keeps it off.
-    if (la.rows_dev == nullptr && g_nt_probe == 0 && (g_nt_variant == 50 || ((g_nt_variant == 0 || (g_nt_variant == 53 && ep.mode != EPI_GELU_BWD)) && M >= 1024 && (long)((M + 255) / 256) * ((N + 191) / 192) >= 384)) &&
+    if (la.rows_dev == nullptr && (g_nt_variant == 50 || (g_nt_variant == 0 && M >= 1024 && (long)((M + 255) / 256) * ((N + 191) / 192) >= 384)) &&
         nt8p_supported(M, N, K, ep, la.ld, ldb))
       return gemm_nt8p(st, la.base, la.ld, B, ldb, M, N, K, ep);
     if (ep.out_f32 != nullptr) return RL_ERR_ARG;        // (the fp32 copy exists in the persistent kernel's epilogue only: the caller casts)
-    if (la.rows_dev == nullptr && g_nt_probe != 1 && ((g_nt_variant == 0 && M >= 1024 && N >= 256) || (g_nt_variant >= 10 && g_nt_variant <= 44) || (g_nt_variant >= 50 && g_nt_variant < 60))) {
-      if (nt8_supported(M, N, K, ep, la.ld, ldb)) return gemm_nt8(st, la.base, la.ld, B, ldb, M, N, K, ep, (g_nt_variant >= 10 && g_nt_variant < 50) ? g_nt_variant - 10 : 0);
+    if (la.rows_dev == nullptr && ((g_nt_variant == 0 && M >= 1024 && N >= 256) || (g_nt_variant != 0 && g_nt_variant != 9))) {
+      if (nt8_supported(M, N, K, ep, la.ld, ldb)) return gemm_nt8(st, la.base, la.ld, B, ldb, M, N, K, ep, (g_nt_variant >= 12 && g_nt_variant <= 16) ? g_nt_variant - 10 : 0);
     }
     // a device-side row bound on a wide output (round 6: the training classifier over the loss rows): the persistent kernel, which
     // shrinks its tile walk to the live tile rows on the device
-    if (la.rows_dev != nullptr && ep.m_dev == nullptr && g_nt_probe == 0 && g_nt_variant == 0 && M >= 1024 &&
+    if (la.rows_dev != nullptr && ep.m_dev == nullptr && g_nt_variant == 0 && M >= 1024 &&
         (long)((M + 255) / 256) * ((N + 191) / 192) >= 384 && nt8p_supported(M, N, K, ep, la.ld, ldb)) {
       EpiParams<T> e2 = ep;
       e2.m_dev = la.rows_dev;
@@ -454,31 +299,12 @@ static int launch_nt(hipStream_t st, const ALoader& la, const T* B, int64_t ldb,
     }
     // a device-side row bound (the GRU steps of a device-built batch: nominal M = B*S, the alive count lives on the device): the
     // 8-wave kernel with exact row masking - tiles beyond the count leave at once, rows beyond it inside the last live tile read zeros
-    if (la.rows_dev != nullptr && ep.m_dev == nullptr && g_nt_probe == 0 && g_nt_variant == 0 && M >= 1024 && N >= 256 && (K % 64) == 0 &&
+    if (la.rows_dev != nullptr && ep.m_dev == nullptr && g_nt_variant == 0 && M >= 1024 && N >= 256 && (K % 64) == 0 &&
         nt8_supported(M, N, K, ep, la.ld, ldb)) {
       EpiParams<T> e2 = ep;
       e2.m_dev = la.rows_dev; e2.m_exact = 1;
       return gemm_nt8(st, la.base, la.ld, B, ldb, M, N, K, e2, 0);
     }
-#if RL_PROBES
-    switch (g_nt_variant) {       // experimental tile shapes (tools/nt_probe.cpp)
-      case 1: return launch_nt_tile<T, ALoader, 2, 4, 2, 3>(st, la, lb, M, N, K, ep);     // 128 x 192, 8 waves, 2 stages
-      case 2: return launch_nt_tile<T, ALoader, 2, 4, 3, 3>(st, la, lb, M, N, K, ep);     // 128 x 192, 3 stages
-      case 3: return launch_nt_tile<T, ALoader, 4, 2, 2, 4>(st, la, lb, M, N, K, ep);     // 256 x 128, 2 stages
-      case 4: return launch_nt_tile<T, ALoader, 4, 2, 3, 4>(st, la, lb, M, N, K, ep);     // 256 x 128, 3 stages
-      case 5: if (g_nt_n96 && cost(96) < cost(128)) return launch_nt_tile<T, ALoader, 2, 2, 2, 3, true>(st, la, lb, M, N, K, ep);
-              return launch_nt_tile<T, ALoader, 2, 2, 2, 4, true>(st, la, lb, M, N, K, ep);   // production tiles, spread fetch issue
-      case 6: return launch_nt_tile<T, ALoader, 4, 2, 3, 4, true>(st, la, lb, M, N, K, ep);     // 256 x 128, 3 stages, spread
-      case 7: return launch_nt_tile<T, ALoader, 2, 4, 3, 3, true>(st, la, lb, M, N, K, ep);     // 128 x 192, 3 stages, spread
-      // round 6: 128 x 192 on four waves of 64 x 96, two workgroups per CU - 37 % fewer fragment bytes read
-      // from LDS per K-tile than the 8-wave 128 x 192 kernel (80 against 128 KB); 60 = fetches behind the barrier, 61 = spread
-      case 60: return launch_nt_tile<T, ALoader, 2, 2, 2, 6>(st, la, lb, M, N, K, ep);
-      case 61: return launch_nt_tile<T, ALoader, 2, 2, 2, 6, true>(st, la, lb, M, N, K, ep);
-      case 8: if ((K % 64) == 0 && la.rows_dev == nullptr) return launch_nt_pp(st, la, lb, M, N, K, ep);     // phase-shifted 256 x 128
-              break;
-      default: break;
-    }
-#endif
     // very wide outputs (the 21128-column classifier: > 20 rounds of 128x128 tiles): 8-wave 256x128 tiles cut the
     // operand traffic per flop by a third; three stages and the fetches spread between the MFMA groups keep the single
     // resident workgroup fed (730 vs 644 TF, tools/nt_probe.cpp).  Below ~8 rounds the 4-wave tiles win.
@@ -508,7 +334,7 @@ int gemm_nt_conv(hipStream_t st, const ConvLoader<T>& la_, const T* B, int64_t l
   if (la.par >= 0 && (la.par > 3 || la.mode != 1 || la.stride != 2 || la.hw_shift < 2 || la.w_shift < 1 || la.img_index != nullptr)) return RL_ERR_ARG;
   if constexpr (sizeof(T) == 2) {
     // 64 -> 64 channels, 3x3 / stride 1 / pad 1 on 16x16 maps (glyph ResNet block 1), plain store: the LDS-resident image + weights kernel
-    if (g_conv_c64 && g_nt_probe == 0 && la.par < 0 && la.C == 64 && la.KH == 3 && la.KW == 3 && la.stride == 1 && la.pad == 1 && la.mode <= 1 &&
+    if (g_conv_c64 && la.par < 0 && la.C == 64 && la.KH == 3 && la.KW == 3 && la.stride == 1 && la.pad == 1 && la.mode <= 1 &&
         la.Hr == 16 && la.Wr == 16 && la.Hs == 16 && la.Ws == 16 && la.img_index == nullptr && N == 64 && K == 576 && ldb == 576 &&
         M == la.rows && (M % 256) == 0 && (int64_t)M * 128 < 0xFFFFFE00ll && ep.out2 == nullptr && ep.alpha == 1.0f && ep.ldo == 64 && ep.rm_hw_shift < 0) {
       if (ep.mode == EPI_STORE && ep.accumulate == 0 && ep.bias == nullptr && ep.col_scale == nullptr)
@@ -567,15 +393,13 @@ template <typename L, typename T, int NB> struct ConvTapsImpl {      // L = Conv
 template <typename T, int NB> struct ConvTaps<ConvLoader<T>, NB> : ConvTapsImpl<ConvLoader<T>, T, NB> {};
 template <typename T, int NB> struct ConvTaps<ConvLoaderDirect<T>, NB> : ConvTapsImpl<ConvLoaderDirect<T>, T, NB> {};
 
-// One (split, tile) of a TN problem; `logical` = split * ntiles + tile.
-// NST LDS stages of BP = TnGeo::BP / BPD reduction rows each (default: 2 stages of full tiles; the grouped kernel runs 4 stages of half
-// tiles in the same 64 KB: three tiles in flight per workgroup instead of one).
-template <typename T, typename BLoader, bool TR, int WI, int WJ, int NST = 2, int BPD = 1>
+// One (split, tile) of a TN problem; `logical` = split * ntiles + tile.  Two LDS stages of BP reduction rows.
+template <typename T, typename BLoader, bool TR, int WI, int WJ>
 __device__ __forceinline__ void tn_tile_body(const T* __restrict__ A, int64_t lda, BLoader lb, int P, int I, int J, int tiles_j, int ntiles,
-                                             int nsplit, int pchunk, int how, TnEpi ep, int logical, int jmajor = 0) {
+                                             int nsplit, int pchunk, int how, TnEpi ep, int logical) {
   typedef typename MmaOf<T>::type Mma;
   typedef TnGeo<T> G;
-  constexpr int BP = G::BP / BPD, KST = G::KSTEPS / BPD;
+  constexpr int BP = G::BP, KST = G::KSTEPS, NST = 2;
   constexpr int BI = 64 * WI, BJ = 64 * WJ;
   constexpr int RPA = BI * (int)sizeof(T), RPB = BJ * (int)sizeof(T);         // row pitches (bytes)
   constexpr int A_BYTES = BP * RPA, B_BYTES = BP * RPB, STAGE = A_BYTES + B_BYTES;
@@ -585,12 +409,7 @@ __device__ __forceinline__ void tn_tile_body(const T* __restrict__ A, int64_t ld
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int wi = wave / WJ, wj = wave - wi * WJ;
   const int split = logical / ntiles, tile = logical - split * ntiles;
-  // Tile order inside a problem.  The XCD remap hands every XCD a contiguous run of tiles; i-major (default) a run shares few dY panels
-  // and streams the WHOLE B operand through its L2, j-major the other way round.  The grouped launch picks the order that streams the
-  // smaller operand whole (round 6: FFN-down's weight gradient, I = 768, J = 3072, re-read its 33 MB `post` operand on three XCDs).
-  int ti, tj;
-  if (jmajor) { const int tiles_i = ntiles / tiles_j; tj = tile / tiles_i; ti = tile - tj * tiles_i; }
-  else { ti = tile / tiles_j; tj = tile - ti * tiles_j; }
+  const int ti = tile / tiles_j, tj = tile - ti * tiles_j;
   const int i0 = ti * BI, j0 = tj * BJ;
   lb.clamp_rows();
   const int Pe = min(P, lb.rows);                      // device-side row bound (glyph dedup): re-split the live rows evenly
@@ -603,7 +422,7 @@ __device__ __forceinline__ void tn_tile_body(const T* __restrict__ A, int64_t ld
   const bool listed = kDenseB0 && ep.tile_list != nullptr && nsplit == 1;
   // 16-row form of the list (bf16, 128 x 128 tiles: wave w fetches rows 16w .. 16w + 15 of both operand tiles): a reduction tile is
   // any FOUR live 16-row blocks, wave w takes block list[4 t + w] - 68 % instead of 84 % of the rows of a SIGHAN-shaped batch
-  const bool sub16 = listed && ep.list_rows == 16 && sizeof(T) == 2 && WI == 2 && WJ == 2 && BPD == 1;
+  const bool sub16 = listed && ep.list_rows == 16 && sizeof(T) == 2 && WI == 2 && WJ == 2;
 
   // per-lane chunk coordinates are the same for every reduction tile: only the row base moves
   constexpr bool kDenseB = sizeof(typename BLoader::KPos) == sizeof(typename DenseLoader<T>::KPos);
@@ -675,7 +494,6 @@ __device__ __forceinline__ void tn_tile_body(const T* __restrict__ A, int64_t ld
   int ptr_sub = 0;                       // sub16: the 16-row block this wave's pointers stand on
   bool sub_ok = true;                    // sub16: this wave has a block in the tile being issued (the last tile may hold fewer than four)
   auto issue = [&](int pt, int stage) {
-    if (RL_PROBES && ep.probe == 2) return;
     char* base = smem + stage * STAGE;
     const bool full = sub16 || pt + BP <= p_end;
     if (sub16) {
@@ -764,19 +582,14 @@ __device__ __forceinline__ void tn_tile_body(const T* __restrict__ A, int64_t ld
 #pragma unroll
   for (int q = 0; q < NST - 1; ++q) issue_next();
   for (int t = 0; t < nt; ++t) {
-    // tile t has landed once at most the (issued - 1 - t) younger tiles' fetches are outstanding (counted vmcnt; raw barrier:
-    // __syncthreads() would drain vmcnt to 0)
-    const int younger = issued - 1 - t;
-    if (NST == 2 || younger <= 0) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    else if (NST == 3 || younger == 1) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(NL) : "memory");
-    else asm volatile("s_waitcnt vmcnt(%0)" ::"n"(2 * NL) : "memory");
+    // tile t is the only one in flight: wait for it, then a raw barrier (__syncthreads() would add nothing but the drain)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
     issue_next();                                      // into the stage every wave finished reading before this barrier
     const int cur = t % NST;
     const char* At = smem + cur * STAGE;
     const char* Bt = At + A_BYTES;
-    if (RL_PROBES && ep.probe == 3) continue;
 #pragma unroll
     for (int ks = 0; ks < KST; ++ks) {
       typename Mma::Frag a[4], b[4];
@@ -829,7 +642,7 @@ gemm_tn_kernel(const T* __restrict__ A, int64_t lda, BLoader lb, int P, int I, i
 // 128x128 tile of one problem over the whole reduction (no split: nothing to fold).  The four weight gradients of a transformer
 // layer are 432 such tiles - one round of the chip's 512 workgroup slots - where launched one by one each needs a 3-4 way
 // reduction split (slab write + fold pass) to fill the chip: 8 launches and ~75 MB of slab traffic per layer become 1 launch.
-template <typename T, bool TR, int NST, int BPD>
+template <typename T, bool TR>
 __global__ void __launch_bounds__(256, 2)
 gemm_tn_group_kernel(TnGroup<T> grp, int P, int pchunk) {
   const int logical = xcd_remap(blockIdx.x, grp.total_tiles);
@@ -839,10 +652,10 @@ gemm_tn_group_kernel(TnGroup<T> grp, int P, int pchunk) {
   const TnGroupProblem<T>& pr = grp.p[k];
   DenseLoader<T> lb{pr.B, pr.ldb, P, pr.J};
   TnEpi ep;
-  ep.out = pr.out; ep.ldo = pr.ldo; ep.colsum = pr.colsum; ep.alpha = grp.alpha; ep.probe = grp.probe; ep.overwrite = grp.overwrite;
+  ep.out = pr.out; ep.ldo = pr.ldo; ep.colsum = pr.colsum; ep.alpha = grp.alpha; ep.overwrite = grp.overwrite;
   ep.tile_list = grp.tile_list; ep.n_tiles = grp.n_tiles; ep.list_rows = grp.list_rows;
-  tn_tile_body<T, DenseLoader<T>, TR, 2, 2, NST, BPD>(pr.A, pr.lda, lb, P, pr.I, pr.J, pr.tiles_j, pr.ntiles, 1, pchunk, TN_OUT_DIRECT, ep,
-                                                      logical - pr.tile_begin, pr.jmajor);
+  tn_tile_body<T, DenseLoader<T>, TR, 2, 2>(pr.A, pr.lda, lb, P, pr.I, pr.J, pr.tiles_j, pr.ntiles, 1, pchunk, TN_OUT_DIRECT, ep,
+                                            logical - pr.tile_begin);
 }
 
 // out(mapped) += alpha * sum_s slab[s][i][j], in a fixed order (bitwise reproducible).
@@ -947,8 +760,7 @@ void set_tn_transpose_read(int use_tr) { g_tn_tr = use_tr; }
 template <typename T, typename BLoader, int WI, int WJ>
 static int launch_tn_tile(hipStream_t st, const T* A, int64_t lda, const BLoader& lb, int P, int I, int J, const TnEpi& ep_) {
   typedef TnGeo<T> G;
-  TnEpi ep = ep_;
-  ep.probe = g_tn_probe;
+  const TnEpi& ep = ep_;
   constexpr int BI = 64 * WI, BJ = 64 * WJ;
   const int tiles_i = (I + BI - 1) / BI, tiles_j = (J + BJ - 1) / BJ, ntiles = tiles_i * tiles_j;
   // Reduction split: the chip holds 512 workgroups (256 CUs x 2).  Pick the split count that minimises
@@ -991,7 +803,7 @@ static int launch_tn_tile(hipStream_t st, const T* A, int64_t lda, const BLoader
       if (!a2) { (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<T, BLoader, false, WI, WJ>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr); a2 = true; }
       RL_LAUNCH((gemm_tn_kernel<T, BLoader, false, WI, WJ>), grid, dim3(256), lds, st, A, lda, lb, P, I, J, tiles_j, ntiles, nsplit, pchunk, how, ep);
     }
-    if (how == TN_OUT_SLAB && ep.probe != 4) tn_fold_launch(st, ep, nsplit, I, J);
+    if (how == TN_OUT_SLAB) tn_fold_launch(st, ep, nsplit, I, J);
   }
   return hipGetLastError() == hipSuccess ? RL_OK : RL_ERR_LAUNCH;
 }
@@ -1005,34 +817,18 @@ static int launch_tn(hipStream_t st, const T* A, int64_t lda, const BLoader& lb,
   return launch_tn_tile<T, BLoader, 2, 2>(st, A, lda, lb, P, I, J, ep);
 }
 
-static int g_tn_variant = 0;      // 0 production (the 4-wave kernel), 8 the experimental 8-wave ping-pong kernel (gemm_tn8.hip: correct, 7-16 % slower)
-void set_tn_variant(int v) { g_tn_variant = RL_PROBES ? v : 0; }
-
-static int g_tn_group8 = 0;          // grouped weight gradients on the 8-wave 256 x 128 kernel (gemm_tn8_group): measured, not faster (see gemm_tn8.hip)
-void set_tn_group8(int on) { g_tn_group8 = on; }
-static int g_tn_group_ring = 0;      // measured: 4 x 32-row stages 3.76 ms/step vs 3.39 for 2 x 64-row stages (more barriers, smaller DMA batches)
-void set_tn_group_ring(int on) { g_tn_group_ring = on; }
-
 template <typename T>
 int gemm_tn_group(hipStream_t st, int n, const TnGroupProblem<T>* probs, int P, float alpha, int overwrite, const int* tile_list,
                   const int* n_tiles, int list_rows) {
   typedef TnGeo<T> G;
   if (n < 1 || n > TN_GROUP_MAX || P <= 0) return RL_ERR_ARG;
-  if constexpr (sizeof(T) == 2) {
-    if (g_tn_group8 && g_tn_tr && !g_tn_group_ring && g_tn_probe == 0 && (tile_list == nullptr || list_rows == 16)) {
-      const int rc = gemm_tn8_group(st, n, probs, P, alpha, overwrite, tile_list, n_tiles, list_rows);
-      if (rc != RL_ERR_ARG) return rc;
-    }
-  }
   TnGroup<T> grp;
-  grp.n = n; grp.alpha = alpha; grp.probe = g_tn_probe; grp.overwrite = overwrite;
+  grp.n = n; grp.alpha = alpha; grp.overwrite = overwrite;
   if (list_rows != 0 && list_rows != G::BP && !(list_rows == 16 && sizeof(T) == 2)) return RL_ERR_ARG;
   // A caller that hands over a live-block list may rely on it (a live-row step leaves stale values in the rows of unlisted blocks):
-  // the list is honoured or the call fails - it is never silently dropped.  The four-stage ring has no list form, so a listed call
-  // runs on the default two-stage ring whatever the knob says.
+  // the list is honoured or the call fails - it is never silently dropped.
   const bool listed_call = tile_list != nullptr;
   if (listed_call && (n_tiles == nullptr || (P % G::BP) != 0)) return RL_ERR_ARG;
-  const bool ring4 = g_tn_group_ring && !listed_call;
   if (listed_call) { grp.tile_list = tile_list; grp.n_tiles = n_tiles; grp.list_rows = list_rows ? list_rows : G::BP; }
   int total = 0;
   double flops = 0.0;
@@ -1041,7 +837,6 @@ int gemm_tn_group(hipStream_t st, int n, const TnGroupProblem<T>* probs, int P, 
     if (pr.I <= 0 || pr.J <= 0 || (pr.lda % G::VEC) || (pr.ldb % G::VEC) || (pr.I % G::VEC) || (pr.J % G::VEC) || (pr.ldo & 3)) return RL_ERR_ARG;
     pr.tiles_j = (pr.J + 127) / 128;
     pr.ntiles = ((pr.I + 127) / 128) * pr.tiles_j;
-    pr.jmajor = (g_tn_jmajor && pr.J > pr.I) ? 1 : 0;
     pr.tile_begin = total;
     total += pr.ntiles;
     flops += 2.0 * P * pr.I * pr.J;
@@ -1056,15 +851,11 @@ int gemm_tn_group(hipStream_t st, int n, const TnGroupProblem<T>* probs, int P, 
   const int lds_attr = (int)(2 * (size_t)G::BP * 256 * sizeof(T)) + TN_LIST_LDS_MAX;
   ProfScope ps(st, PK_GEMM_TN, flops);
   if (grp.tile_list != nullptr) prof_set_exec(grp.n_tiles, flops / P * grp.list_rows, sizeof(T) == 2 && grp.list_rows == 16 ? 4 : 1, P / grp.list_rows);   // live blocks only
-  // ring: the 2 full stages of the single-problem kernel (default) or 4 stages of half tiles (three tiles in flight per workgroup,
-  // g_tn_group_ring = 1: built to test the fetch-latency hypothesis - 11 % slower)
-#define RL_TN_GROUP(TRV, NSTV, BPDV) do { \
+#define RL_TN_GROUP(TRV) do { \
     static bool attr = false; \
-    if (!attr) { (void)hipFuncSetAttribute((const void*)gemm_tn_group_kernel<T, TRV, NSTV, BPDV>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr); attr = true; } \
-    RL_LAUNCH((gemm_tn_group_kernel<T, TRV, NSTV, BPDV>), dim3(total), dim3(256), lds, st, grp, P, pchunk); } while (0)
-  const bool tr = sizeof(T) == 2 && g_tn_tr;
-  if (ring4) { if (tr) RL_TN_GROUP(true, 4, 2); else RL_TN_GROUP(false, 4, 2); }
-  else { if (tr) RL_TN_GROUP(true, 2, 1); else RL_TN_GROUP(false, 2, 1); }
+    if (!attr) { (void)hipFuncSetAttribute((const void*)gemm_tn_group_kernel<T, TRV>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr); attr = true; } \
+    RL_LAUNCH((gemm_tn_group_kernel<T, TRV>), dim3(total), dim3(256), lds, st, grp, P, pchunk); } while (0)
+  if (sizeof(T) == 2 && g_tn_tr) RL_TN_GROUP(true); else RL_TN_GROUP(false);
 #undef RL_TN_GROUP
   return hipGetLastError() == hipSuccess ? RL_OK : RL_ERR_LAUNCH;
 }
@@ -1075,12 +866,6 @@ template <typename T>
 int gemm_tn(hipStream_t st, const T* A, int64_t lda, const T* B, int64_t ldb, int P, int I, int J, const TnEpi& ep,
             const int* rows_dev) {
   if (ldb % TnGeo<T>::VEC) return RL_ERR_ARG;
-  if constexpr (sizeof(T) == 2) {
-#if RL_PROBES
-    if (rows_dev == nullptr && g_tn_variant == 8 && g_tn_probe == 0 && tn8_supported(lda, ldb, P, I, J, ep))
-      return gemm_tn8(st, A, lda, B, ldb, P, I, J, ep, g_tn_split);
-#endif
-  }
   DenseLoader<T> lb{B, ldb, P, J};
   lb.rows_dev = rows_dev;
   return launch_tn<T, DenseLoader<T>>(st, A, lda, lb, P, I, J, ep);
@@ -1093,7 +878,7 @@ int gemm_tn_conv(hipStream_t st, const T* A, int64_t lda, const ConvLoader<T>& l
   if (lb.K != J || !lb.span_ok()) return RL_ERR_ARG;
   if constexpr (sizeof(T) == 2) {
     // 64 -> 64 channels, 3x3 / stride 1 / pad 1 on 16x16 maps (glyph ResNet block 1): the LDS-resident-input kernel
-    if (g_conv_c64 && g_tn_probe == 0 && lb.C == 64 && lb.KH == 3 && lb.KW == 3 && lb.stride == 1 && lb.pad == 1 && lb.mode == 0 && lb.Hr == 16 &&
+    if (g_conv_c64 && lb.C == 64 && lb.KH == 3 && lb.KW == 3 && lb.stride == 1 && lb.pad == 1 && lb.mode == 0 && lb.Hr == 16 &&
         lb.Wr == 16 && lb.Hs == 16 && lb.Ws == 16 && lb.img_index == nullptr && I == 64 && lda == 64 && P == lb.rows && (P % 256) == 0 &&
         ep.mode == TN_CONVW && ep.Cin == 64 && ep.Cpad == 64 && ep.KHW == 9 && ep.tap0 == 0 && ep.alpha == 1.0f && ep.alpha_dev == nullptr && ep.slab != nullptr &&
         ep.slab_elems >= 64 * 576 && (int64_t)P * 128 < 0xFFFFFE00ll)

@@ -155,7 +155,7 @@ __device__ __forceinline__ void epilogue8_pre(const EpiParams<bf16_t>& ep, int M
   }
 }
 
-// ---- TN (weight-gradient) device helpers shared by gemm.hip and gemm_tn8.hip ---------------------------------------------
+// ---- TN (weight-gradient) device helpers of gemm.hip ---------------------------------------------
 template <typename T> struct TnGeo;
 template <> struct TnGeo<bf16_t> { static constexpr int BP = 64, KSTEPS = 2, VEC = 8; };
 template <> struct TnGeo<float> { static constexpr int BP = 32, KSTEPS = 8, VEC = 4; };

@@ -64,7 +64,7 @@ __device__ __forceinline__ void nt8p_body(const bf16_t* __restrict__ A, int64_t 
   }
   typedef MmaBF16 Mma;
   constexpr int NPW = C::NPW, NPH = C::NPH, NS = C::NS, LEAD = C::LEAD, SQ = C::SQ, HT = C::HT, MT = C::MT, NT = C::NT;
-  static_assert(!C::HOLD_B && C::ISSUE_AT == 0 && C::FW == 8 && (NT % 2) == 0, "persistent kernel: hold-A schedule, fetches at the end of the memory segment");
+  static_assert(!C::HOLD_B && (NT % 2) == 0, "persistent kernel: hold-A schedule");
   // EPI_STORE_F32X (this file only): EPI_STORE + the fp32 copy of every stored value (EpiParams::out_f32), one 16-byte store per
   // accumulator tile in the accumulator layout (a lane: 4 consecutive columns of one row)
   constexpr int NSTORE = MT * (NT / 2) * (EPI == EPI_GELU ? 2 : 1) + (EPI == EPI_STORE_F32X ? MT * NT : 0);      // 16-byte store instructions of one tile's epilogue, per wave

@@ -12,15 +12,11 @@ template <int... Is> struct SeqGen<0, Is...> {
 };
 template <int N, typename F> __device__ __forceinline__ void static_for(F&& f) { SeqGen<N>::run(f); }
 
-template <int BM_, int BN_, int WM_, int WN_, bool HOLD_B_, int SQ_, int NS_, int LEAD_, int ISSUE_AT_ = 0, int FW_ = 8, int WGS_ = 1>
+// Every wave fetches (8 of them) and issues its share of a phase's fetches at the end of the memory segment, after its fragment reads.
+template <int BM_, int BN_, int WM_, int WN_, bool HOLD_B_, int SQ_, int NS_, int LEAD_, int WGS_ = 1>
 struct Nt8Cfg {
   static constexpr int WGS = WGS_;               // workgroups meant to share a CU (2: <= 80 KB of LDS and <= 128 VGPRs each)
-  static constexpr int FW = FW_;                 // waves that issue the fetches: all 8 (they also multiply), or 4 dedicated loader waves
-  // where a phase issues its fetches: 0 end of the memory segment (after the fragment reads), 1 between the MFMAs, 2 head of the
-  // memory segment (the texture-address unit serialises the 4 waves' 1-KiB requests, ~29 clk each: issuing them FIRST lets that
-  // queueing run under the fragment reads instead of after them)
-  static constexpr int ISSUE_AT = ISSUE_AT_;
-  static constexpr bool ISSUE_C = ISSUE_AT_ == 1;
+  static constexpr int FW = 8;                   // waves that issue the fetches
   static constexpr int BM = BM_, BN = BN_, WM = WM_, WN = WN_, SQ = SQ_, NS = NS_, LEAD = LEAD_;
   static constexpr bool HOLD_B = HOLD_B_;
   static constexpr int RM = BM / WM, RN = BN / WN, MT = RM / 16, NT = RN / 16;        // per-wave tile, in rows / 16x16 tiles
@@ -43,10 +39,10 @@ struct Nt8Cfg {
   static constexpr int nmax(int q) { return HPW + (q + 1) * GPW - 1; }
   static constexpr bool valid() {
     for (int s = 0; s < NPW; ++s) {
-      // RAW: issued no later than the memory segment of the phase before its reader (MFMA-segment issue: one phase earlier)
-      if (qissue(s) - LEAD > need_q(s) - 1 - (ISSUE_C ? 1 : 0)) return false;
-      // WAR: >= 2 phases after the last reader of the region (MFMA-segment issue sits half a phase later: >= 1 phase)
-      if (qissue(s) - LEAD < need_q(s) - NS * NPH + 2 - (ISSUE_C ? 1 : 0)) return false;
+      // RAW: issued no later than the memory segment of the phase before its reader
+      if (qissue(s) - LEAD > need_q(s) - 1) return false;
+      // WAR: >= 2 phases after the last reader of the region
+      if (qissue(s) - LEAD < need_q(s) - NS * NPH + 2) return false;
     }
     return true;
   }
@@ -54,7 +50,7 @@ struct Nt8Cfg {
   // steady-state wait of phase q (after its own issues): everything phase q+1 reads has landed
   static constexpr int vm(int q) {
     const int q1 = (q + 1) % NPH, dt1 = (q + 1) / NPH;
-    const int slot = q + LEAD - (ISSUE_C ? 1 : 0);          // last issue slot completed when phase q waits
+    const int slot = q + LEAD;                              // last issue slot completed when phase q waits
     const int dt2 = slot / NPH, q2 = slot % NPH;
     return dt2 * NPW + cum(q2 + 1) - 1 - (dt1 * NPW + nmax(q1));
   }

@@ -1,5 +1,5 @@
-"""Where the conv weight-gradient time goes: each glyph-ResNet wgrad shape on 3740 distinct images (the dedup'd B=64 batch),
-normal / no fetches (probe 2) / no MFMA (probe 3) / no fold (probe 4), through the C ABI with HIP events."""
+"""Times the conv weight gradient of each glyph-ResNet shape on 3740 distinct images (the dedup'd B=64 batch), through the C ABI
+with HIP events."""
 import ctypes as C
 import os
 import sys
@@ -46,12 +46,8 @@ for name, Hin, Cp, Ci, Co, k, s, p in shapes:
     g = geom(x, Pn, Hout, Hin, Cp, k, s, p, 0)
     dw = torch.zeros(Co, Ci, k, k, device=dev)
     fn = lambda: lib.realise_conv_tn(st(), 1, dy.data_ptr(), Co, C.byref(g), Pn, Co, Ci, dw.data_ptr(), slab.data_ptr(), slab.numel())
-    res = []
-    for mode in (0, 2, 3, 4):
-        lib.realise_set_tn_probe(mode)
-        res.append(timeit(fn))
-    lib.realise_set_tn_probe(0)
+    us = timeit(fn)
     fl = 2.0 * Pn * Co * k * k * Cp
     mb = (Pn * Co * 2 + N * Hin * Hin * Cp * 2) / 1e6
-    print("%-9s P %7d I %4d J %5d | %7.1f us %6.1f TF | no-fetch %7.1f | no-mfma %7.1f | no-fold %7.1f | operands %6.1f MB -> %5.2f TB/s"
-          % (name, Pn, Co, k * k * Cp, res[0], fl / res[0] / 1e6, res[1], res[2], res[3], mb, mb / res[0] / 1e6 * 1e6 / 1e6), flush=True)
+    print("%-9s P %7d I %4d J %5d | %7.1f us %6.1f TF | operands %6.1f MB -> %5.2f TB/s"
+          % (name, Pn, Co, k * k * Cp, us, fl / us / 1e6, mb, mb / us / 1e6 * 1e6 / 1e6), flush=True)

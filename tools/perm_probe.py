@@ -14,7 +14,7 @@ lib = _capi.load()
 for kv in os.environ.get("KNOBS", "").split():
     name, rest = kv.split(":")
     k, v = rest.split("=")
-    getattr(lib, "realise_set_" + name)(*([int(k), int(v)] if name != "attn_probe" else [int(v)]))
+    getattr(lib, "realise_set_" + name)(int(k), int(v))
 cfg = RealiseConfig(hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0)
 m = SpellBertPho2ResArch3(cfg, compute_dtype="bf16", seed=3).to("cuda").train()
 batch = synthetic_batch(64, 128, seed=77)

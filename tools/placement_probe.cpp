@@ -1,7 +1,7 @@
 // Round 6 probe: where does the dispatcher put the workgroups of a two-per-CU launch?  A kernel with the layer GEMM's launch shape (512
 // threads, 80 KB of dynamic LDS, so two workgroups share a CU) records per workgroup its XCC, SE / SH / CU ids and start time and then
 // spins long enough that the whole first round is resident together.  Output: for every (XCC, SE, SH, CU) the block indices it held, in
-// start order - the pairing rule `cu_pair_local` (common.h) assumes local indices j and j + 32 of an XCD share a CU.
+// start order (local indices j and j + 32 of an XCD share a CU).
 //   hipcc --offload-arch=gfx950 -O2 tools/placement_probe.cpp -o tools/_bin/placement_probe && tools/_bin/placement_probe [grid]
 #include <hip/hip_runtime.h>
 #include <cstdio>
