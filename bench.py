@@ -9,10 +9,13 @@ region starts.
     python bench.py --gpus 1 --steps 20 --warmup 3
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+    python bench.py --full                       # also the sub-measurements that take runs of their own (below)
     python bench.py --workload glyph256          # BASELINE configs[3]: the glyph ResNet alone on 256 x 128 glyph stacks
     python bench.py --dump-outputs DIR           # also write the last timed step's outputs as DIR/*.npy (same inputs every run)
 
-Rank 0 prints ONE JSON line.
+Rank 0 prints ONE JSON line.  A plain run sets up, warms up, times the steps and prints what those steps measured; the
+sub-measurements that take runs of their own (`forward`, `dense_rows`, `fp32_parity`, `parity`, `glyph256`, `cpu_baseline`)
+run with --full only, and each --no-* option drops one of them from a --full run.
 * `value`            whole-job train sentences/s (max over ranks of the timed region).
 * `roofline`         the dominant kernel family - the bf16 MFMA NT GEMMs (every nn.Linear forward / data gradient, classifier,
                      GRU step) - timed per launch with HIP events recorded on the launch stream during the timed region;
@@ -362,12 +365,15 @@ def main():
                     help="N = 1: still initialise the process group and wrap the model in the data-parallel wrapper (RCCL initialisation, the "
                          "communication stream and the per-bucket events are exercised with a one-rank all-reduce)")
     ap.add_argument("--dist-timeout", type=int, default=300, help="seconds before a rendezvous / collective gives up")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps, also run the sub-measurements: forward-only timings, the dense-rows step, the fp32 parity "
+                         "mode and its measured band, glyph256 and the CPU baseline (the --no-* options below drop single ones)")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--cpu-sample", type=int, default=8)
     ap.add_argument("--no-profile", action="store_true")
     ap.add_argument("--profile-markers", action="store_true",
                     help="time launches with event markers recorded around them (round 1/2 form) instead of the dispatch's own timestamps")
-    ap.add_argument("--no-glyph256", action="store_true", help="skip the BASELINE configs[3] sub-measurement of the default run")
+    ap.add_argument("--no-glyph256", action="store_true", help="skip the BASELINE configs[3] sub-measurement of a --full run")
     ap.add_argument("--dump-launches", default=None, help="write the per-launch durations of the first sampled step to this JSON file")
     ap.add_argument("--no-forward", action="store_true", help="skip the forward-only measurements")
     ap.add_argument("--no-fp32-parity", action="store_true", help="skip the fp32 parity-mode throughput sub-measurement")
@@ -381,7 +387,7 @@ def main():
     ap.add_argument("--dense-rows", action="store_true",
                     help="compute the transformer stacks over ALL rows of the padded batch, as the reference does (realise_set_engine(10, 0)); "
                          "default: the live 16-row blocks only - loss, live-row logits and gradients bit-identical (tests/test_round4_gpu.py)")
-    ap.add_argument("--no-dense-rows-ab", action="store_true", help="skip the dense-rows sub-measurement of the default run")
+    ap.add_argument("--no-dense-rows-ab", action="store_true", help="skip the dense-rows sub-measurement of a --full run")
     ap.add_argument("--no-overlap", action="store_true", help="run the bert / pho / glyph branches serially on one stream")
     ap.add_argument("--knob", action="append", default=[], help="diagnostic knob as name:key=value, e.g. engine:0=1 (realise_set_engine(0, 1)); names: engine, ln, nt8p; "
                                                                     "opt:fused=0 steps with the arena-level AdamW kernels + full operand refresh")
@@ -393,6 +399,10 @@ def main():
         ap.error("--steps must be at least 1")
     if args.dump_outputs and args.workload != "train":
         ap.error("--dump-outputs covers the train workload only")
+    if not args.full:
+        # a plain run is the headline alone: none of the sub-measurements, which take runs of their own after the timed steps
+        args.no_cpu_baseline = args.no_dense_rows_ab = args.no_forward = True
+        args.no_fp32_parity = args.no_golden_parity = args.no_glyph256 = True
 
     world = int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
