@@ -128,15 +128,28 @@ int realise_gru_step_fwd(void* stream, int dtype, const realise_gru_step* a);
 int realise_gru_step_bwd(void* stream, int dtype, const realise_gru_step* a);
 /* Gated fusion (src/models.py:840-850): masked mean of the bert states per sentence, three sigmoid gates from
  * [bert | pho | res | mean] . W[3][4H] + bias, fused = g0 bert + g1 pho + g2 res.  Backward fills dbert / dpho / dres and
- * accumulates dW [3][4H], dbias [3]; mean [B][H], msum [B], g [B*S][4] are saved by the forward, dz [B*S][4] is scratch. */
+ * accumulates dW [3][4H], dbias [3]; mean [B][H], msum [B], g [B*S][4] are saved by the forward, dz [B*S][4] is scratch.
+ * nsrc (0 = 3): the gate of the ablation model (src/models_abla.py:239-275) over nsrc = G sources - bert, then pho and res in that
+ * order where present (a NULL pho / res is absent; nsrc = 2 takes exactly one of them): W [G][(G+1)H], bias [G], g / dz keep
+ * their row pitch of 4.  row_live (nullable, [B*S] bytes): 0 marks a padding row whose d fused is an exact zero - the backward
+ * writes its zeros without reading its forward activations. */
 typedef struct {
   int32_t B, S, H;
   const void* bert; const void* pho; const void* res; const int64_t* masks; const float* W; const float* bias;
   float* mean; float* msum; float* g; void* fused;
   const void* dfused; void* dbert; void* dpho; void* dres; float* dz; float* dW; float* dbias;
+  const uint8_t* row_live;
+  int32_t nsrc;
 } realise_gate;
 int realise_gate_fwd(void* stream, int dtype, const realise_gate* a);
 int realise_gate_bwd(void* stream, int dtype, const realise_gate* a);
+/* Sum fusion of the ablation model (src/models_abla.py:278-279, fusion == "sum"): fused = (bert + pho) + res over rows x H, in fp32,
+ * stored in `dtype`.  The backward hands the same d fused to each branch: dbert = dpho = dres = dfused (one launch, three copies -
+ * the branch backwards run concurrently and two of them write into their incoming gradient buffer).  row_live (nullable, [rows]
+ * bytes) as in realise_gate: a padding row gets exact zeros, its d fused row is not read. */
+int realise_sum_fuse_fwd(void* stream, int dtype, const void* bert, const void* pho, const void* res, void* fused, int rows, int H);
+int realise_sum_fuse_bwd(void* stream, int dtype, const void* dfused, void* dbert, void* dpho, void* dres, int rows, int H,
+                         const uint8_t* row_live);
 /* nn.BatchNorm2d over an NHWC activation viewed as [P = N*H*W][C] (src/char_cnn.py:17-28), optional fused ReLU.  training:
  * batch statistics (two passes: mean, then centred squares), running statistics updated with the unbiased variance and
  * `momentum`, num_batches_tracked += 1 (nullable), save_mean / save_rstd [C] for the backward.  scratch: 4*C floats.
@@ -167,13 +180,16 @@ int realise_argmax(void* stream, int dtype, const void* logits, int64_t ld, int 
  * (models.py:806-870) and their autograd (`loss.backward()`, run.py:200), one C call each.
  * ---------------------------------------------------------------------------------------- */
 typedef struct {
-  int32_t model_type;        /* 0 = SpellBert (BERT only), 1 = SpellBertPho2ResArch3 */
+  int32_t model_type;        /* 0 = SpellBert (BERT only), 1 = SpellBertPho2ResArch3, 2 = SpellBertPho2ResArch3Abla (models_abla.py:33-299) */
   int32_t dtype;
   int32_t hidden, heads, intermediate, vocab, max_pos, type_vocab;
   int32_t bert_layers, pho_layers, out_layers;
   int32_t num_fonts, glyph_size, pho_vocab;
   float hidden_dropout, attn_dropout, ln_eps;
   int32_t tie_classifier;    /* classifier.weight aliases bert word embeddings (models.py:700-701) */
+  /* model_type 2 only (ignored otherwise; run.py:373-375): 1 = the pinyin branch / the glyph branch is present; fusion 0 = gate over
+   * the G = 1 + with_pho + with_res sources (gate_net [G, (G+1)H]), 1 = sum (needs both branches) */
+  int32_t with_pho, with_res, fusion;
 } realise_config;
 
 /* Parameter layout: the library is the source of truth for where each state_dict tensor of the

@@ -26,7 +26,7 @@ class Gate(C.Structure):
                 ("bert", C.c_void_p), ("pho", C.c_void_p), ("res", C.c_void_p), ("masks", C.c_void_p), ("W", C.c_void_p), ("bias", C.c_void_p),
                 ("mean", C.c_void_p), ("msum", C.c_void_p), ("g", C.c_void_p), ("fused", C.c_void_p),
                 ("dfused", C.c_void_p), ("dbert", C.c_void_p), ("dpho", C.c_void_p), ("dres", C.c_void_p), ("dz", C.c_void_p), ("dW", C.c_void_p),
-                ("dbias", C.c_void_p)]
+                ("dbias", C.c_void_p), ("row_live", C.c_void_p), ("nsrc", C.c_int32)]
 
 
 class AdamwGroup(C.Structure):
@@ -55,7 +55,7 @@ class Config(C.Structure):
                                          "type_vocab", "bert_layers", "pho_layers", "out_layers", "num_fonts",
                                          "glyph_size", "pho_vocab")] + \
                [("hidden_dropout", C.c_float), ("attn_dropout", C.c_float), ("ln_eps", C.c_float),
-                ("tie_classifier", C.c_int32)]
+                ("tie_classifier", C.c_int32), ("with_pho", C.c_int32), ("with_res", C.c_int32), ("fusion", C.c_int32)]
 
 
 class Batch(C.Structure):
@@ -111,6 +111,8 @@ SYMBOLS = {
     "realise_gru_step_bwd": (_I, [_P, _I, C.POINTER(GruStep)]),
     "realise_gate_fwd": (_I, [_P, _I, C.POINTER(Gate)]),
     "realise_gate_bwd": (_I, [_P, _I, C.POINTER(Gate)]),
+    "realise_sum_fuse_fwd": (_I, [_P, _I, _P, _P, _P, _P, _I, _I]),
+    "realise_sum_fuse_bwd": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _P]),
     "realise_batchnorm_fwd": (_I, [_P, _I, _P, _I, _I, _P, _P, _F, _F, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "realise_batchnorm_bwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
     "realise_embedding_bwd": (_I, [_P, _I, _P, _P, _I, _I, _I, _P, _P, _I, _P]),
@@ -205,7 +207,7 @@ def check(rc, what):
 
 def make_config(cfg, model_type, dtype, tie=True):
     c = Config()
-    c.model_type = 1 if model_type == "arch3" else 0
+    c.model_type = {"bert": 0, "arch3": 1, "arch3-abla": 2}[model_type]
     c.dtype = dtype
     c.hidden, c.heads, c.intermediate = cfg["hidden_size"], cfg["num_attention_heads"], cfg["intermediate_size"]
     c.vocab, c.max_pos, c.type_vocab = cfg["vocab_size"], cfg["max_position_embeddings"], cfg["type_vocab_size"]
@@ -214,6 +216,10 @@ def make_config(cfg, model_type, dtype, tie=True):
     c.hidden_dropout, c.attn_dropout = cfg["hidden_dropout_prob"], cfg["attention_probs_dropout_prob"]
     c.ln_eps = cfg["layer_norm_eps"]
     c.tie_classifier = 1 if tie else 0
+    # the ablation switches (model_type 2 only; src/models_abla.py:37-39)
+    c.with_pho = 1 if cfg.get("with_pho", "yes") == "yes" else 0
+    c.with_res = 1 if cfg.get("with_res", "yes") == "yes" else 0
+    c.fusion = 1 if cfg.get("fusion", "gate") == "sum" else 0
     return c
 
 

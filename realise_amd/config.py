@@ -32,6 +32,11 @@ class RealiseConfig(dict):
         out_layers=3,
         pho_vocab_size=33,          # src/utils.py:61-67
         glyph_size=32,
+        # run.py:373-375, 422-425: the ablation switches every config carries; only SpellBertPho2ResArch3Abla reads them
+        # (src/models_abla.py:37-45), which also writes num_gates = 1 + [with_pho] + [with_res] onto the config
+        with_pho="yes",
+        with_res="yes",
+        fusion="gate",
     )
 
     def __init__(self, **kw):
@@ -56,6 +61,15 @@ class RealiseConfig(dict):
             raise ValueError("only the erf GELU of the reference path is implemented")
         if self["image_model_type"] != 0:
             raise NotImplementedError("invalid image_model_type %d" % self["image_model_type"])
+        for k in ("with_pho", "with_res"):
+            if self.get(k, "yes") not in ("yes", "no"):
+                raise ValueError("%s must be 'yes' or 'no' (run.py:373-374), got %r" % (k, self[k]))
+        if self.get("fusion", "gate") not in ("gate", "sum"):
+            raise ValueError("fusion must be 'gate' or 'sum' (run.py:375), got %r" % self["fusion"])
+        # the reference builds a sum-fusion model with a branch off and dies with a TypeError at its first forward
+        # (models_abla.py:279 adds None); here it is refused at construction
+        if self.get("fusion", "gate") == "sum" and (self.get("with_pho", "yes") != "yes" or self.get("with_res", "yes") != "yes"):
+            raise ValueError("fusion='sum' needs both branches (with_pho='yes', with_res='yes')")
 
     # config.json round trip (transformers/configuration_utils.py:204-227)
     def save_pretrained(self, d):
@@ -70,3 +84,8 @@ class RealiseConfig(dict):
             c = cls(**{k: v for k, v in json.load(f).items()})
         c.update(kw)
         return c
+
+
+def num_gates(cfg):
+    """1 + [with_pho] + [with_res] (src/models_abla.py:40-45)"""
+    return 1 + (cfg.get("with_pho", "yes") == "yes") + (cfg.get("with_res", "yes") == "yes")

@@ -292,6 +292,7 @@ template <typename T> GateArgs<T> to_gate(const realise_gate* g) {
   a.B = g->B; a.S = g->S; a.H = g->H; a.bert = (const T*)g->bert; a.pho = (const T*)g->pho; a.res = (const T*)g->res; a.masks = g->masks;
   a.W = g->W; a.bias = g->bias; a.mean = g->mean; a.msum = g->msum; a.g = g->g; a.fused = (T*)g->fused; a.dfused = (const T*)g->dfused;
   a.dbert = (T*)g->dbert; a.dpho = (T*)g->dpho; a.dres = (T*)g->dres; a.dz = g->dz; a.dW = g->dW; a.dbias = g->dbias;
+  a.row_live = g->row_live; a.nsrc = g->nsrc == 0 ? 3 : g->nsrc;
   return a;
 }
 template <typename T>
@@ -334,6 +335,17 @@ int realise_gate_fwd(void* stream, int dtype, const realise_gate* a) {
 int realise_gate_bwd(void* stream, int dtype, const realise_gate* a) {
   if (!a) return RL_ERR_ARG;
   RL_BY_DTYPE(gate_bwd<bf16_t>((hipStream_t)stream, to_gate<bf16_t>(a)), gate_bwd<float>((hipStream_t)stream, to_gate<float>(a)));
+}
+int realise_sum_fuse_fwd(void* stream, int dtype, const void* bert, const void* pho, const void* res, void* fused, int rows, int H) {
+  hipStream_t st = (hipStream_t)stream;
+  RL_BY_DTYPE(sum_fuse_fwd<bf16_t>(st, (const bf16_t*)bert, (const bf16_t*)pho, (const bf16_t*)res, (bf16_t*)fused, rows, H),
+              sum_fuse_fwd<float>(st, (const float*)bert, (const float*)pho, (const float*)res, (float*)fused, rows, H));
+}
+int realise_sum_fuse_bwd(void* stream, int dtype, const void* dfused, void* dbert, void* dpho, void* dres, int rows, int H,
+                         const uint8_t* row_live) {
+  hipStream_t st = (hipStream_t)stream;
+  RL_BY_DTYPE(sum_fuse_bwd<bf16_t>(st, (const bf16_t*)dfused, (bf16_t*)dbert, (bf16_t*)dpho, (bf16_t*)dres, rows, H, row_live),
+              sum_fuse_bwd<float>(st, (const float*)dfused, (float*)dbert, (float*)dpho, (float*)dres, rows, H, row_live));
 }
 int realise_batchnorm_fwd(void* stream, int dtype, const void* x, int P, int C, const float* gamma, const float* beta, float eps, float momentum,
                           float* running_mean, float* running_var, int64_t* num_batches_tracked, int training, int relu, void* y,
@@ -405,10 +417,10 @@ int realise_segment_sum(void* stream, int dtype, const void* x, const int32_t* i
 }
 
 // ---- layout --------------------------------------------------------------------------------------
-int realise_layout_count(const realise_config* cfg) { return cfg ? (int)build_layout(*cfg).tensors.size() : -1; }
+int realise_layout_count(const realise_config* cfg) { return cfg && variant_valid(*cfg) ? (int)build_layout(*cfg).tensors.size() : -1; }
 int realise_layout_entry(const realise_config* cfg, int index, char* name, int name_cap, int32_t* arena, int64_t* offset,
                          int32_t* ndim, int64_t* shape4) {
-  if (!cfg) return RL_ERR_ARG;
+  if (!cfg || !variant_valid(*cfg)) return RL_ERR_ARG;
   const Layout L = build_layout(*cfg);
   if (index < 0 || index >= (int)L.tensors.size()) return RL_ERR_ARG;
   const TensorInfo& t = L.tensors[index];
@@ -419,12 +431,12 @@ int realise_layout_entry(const realise_config* cfg, int index, char* name, int n
   return RL_OK;
 }
 int64_t realise_arena_elems(const realise_config* cfg, int arena) {
-  if (!cfg || arena < 0 || arena >= AR_COUNT) return -1;
+  if (!cfg || !variant_valid(*cfg) || arena < 0 || arena >= AR_COUNT) return -1;
   return build_layout(*cfg).arena_elems[arena];
 }
-int realise_bucket_count(const realise_config* cfg) { return cfg ? (int)build_layout(*cfg).buckets.size() : -1; }
+int realise_bucket_count(const realise_config* cfg) { return cfg && variant_valid(*cfg) ? (int)build_layout(*cfg).buckets.size() : -1; }
 int realise_bucket_bounds(const realise_config* cfg, int bucket, int64_t* begin, int64_t* end) {
-  if (!cfg) return RL_ERR_ARG;
+  if (!cfg || !variant_valid(*cfg)) return RL_ERR_ARG;
   const Layout L = build_layout(*cfg);
   if (bucket < 0 || bucket >= (int)L.buckets.size()) return RL_ERR_ARG;
   *begin = L.buckets[bucket].first; *end = L.buckets[bucket].second;

@@ -120,6 +120,7 @@ static inline uint64_t splitmix(uint64_t x) {
 
 template <typename T> struct Engine : EngineBase {
   realise_config cfg;
+  Variant vr;              // which branches this model has (layout.h: every branch decision reads this, not model_type)
   Layout L;
   float *P = nullptr, *G = nullptr, *PU = nullptr, *FZ = nullptr, *BF = nullptr;
   int64_t* BI = nullptr;
@@ -227,14 +228,19 @@ template <typename T> struct Engine : EngineBase {
     for (int k = 0; k < 2; ++k) (void)hipEventCreateWithFlags(&ev_join[k], hipEventDisableTiming);
     return true;
   }
+  // the branch streams this model uses: bit 0 = bst[0] (pinyin branch), bit 1 = bst[1] (glyph branch); fork / join touch only those
+  int branch_mask() const { return (vr.pho ? 1 : 0) | (vr.res ? 2 : 0); }
   int fork(hipStream_t st) {
+    const int mask = branch_mask();
+    if (mask == 0) return RL_OK;
     if (hipEventRecord(ev_fork, st) != hipSuccess) return RL_ERR_LAUNCH;
-    for (int k = 0; k < 2; ++k) if (hipStreamWaitEvent(bst[k], ev_fork, 0) != hipSuccess) return RL_ERR_LAUNCH;
+    for (int k = 0; k < 2; ++k) if ((mask >> k & 1) && hipStreamWaitEvent(bst[k], ev_fork, 0) != hipSuccess) return RL_ERR_LAUNCH;
     return RL_OK;
   }
   int join(hipStream_t st) {
+    const int mask = branch_mask();
     for (int k = 0; k < 2; ++k)
-      if (hipEventRecord(ev_join[k], bst[k]) != hipSuccess || hipStreamWaitEvent(st, ev_join[k], 0) != hipSuccess) return RL_ERR_LAUNCH;
+      if ((mask >> k & 1) && (hipEventRecord(ev_join[k], bst[k]) != hipSuccess || hipStreamWaitEvent(st, ev_join[k], 0) != hipSuccess)) return RL_ERR_LAUNCH;
     return RL_OK;
   }
   const int32_t* alive_dev = nullptr;      // device-side n_alive[Tp] of the last batch (nullptr: host counts)
@@ -268,7 +274,7 @@ template <typename T> struct Engine : EngineBase {
   float* gp(int64_t off) const { return G + off; }
 
   Engine(const realise_config& c, float* p, float* g, float* pu, float* fz, float* bf, int64_t* bi)
-      : cfg(c), L(build_layout(c)), P(p), G(g), PU(pu), FZ(fz), BF(bf), BI(bi) {
+      : cfg(c), vr(variant_of(c)), L(build_layout(c)), P(p), G(g), PU(pu), FZ(fz), BF(bf), BI(bi) {
     H = c.hidden; nh = c.heads; I = c.intermediate; V = c.vocab; Vp = (V + 63) & ~63;
     plan_shadows();
   }
@@ -290,11 +296,13 @@ template <typename T> struct Engine : EngineBase {
     plan_stack(sh_bert, cfg.bert_layers);
     sh_cls_w = b.take((int64_t)V * H * e);
     sh_cls_wT = b.take((int64_t)Vp * H * e);      // [H][Vp], columns >= V stay zero (the shadow arena is zero-initialised)
-    if (cfg.model_type == 1) {
-      plan_stack(sh_pho, cfg.pho_layers);
-      plan_stack(sh_out, cfg.out_layers);
+    if (vr.pho) plan_stack(sh_pho, cfg.pho_layers);
+    if (vr.arch) plan_stack(sh_out, cfg.out_layers);
+    if (vr.pho) {
       sh_gru_hh = b.take(3LL * H * H * e);
       sh_gru_hhT = b.take(3LL * H * H * e);
+    }
+    if (vr.res) {
       for (int k = 0; k < 5; ++k) {
         const BlockOff& o = L.blocks[k];
         BlockSh& s = sh_blk[k];
@@ -345,11 +353,9 @@ template <typename T> struct Engine : EngineBase {
     n_descs_a = (int)d.size(); desc_tiles_a = tiles;
     tiles = 0;                                   // second group: its own launch, tile ids restart
     add(L.cls_w, V, H, sh_cls_w, sh_cls_wT, Vp);
-    if (cfg.model_type == 1) {
-      add_stack(L.pho, sh_pho);
-      add_stack(L.outb, sh_out);
-      add(L.gru_w_hh, 3 * H, H, sh_gru_hh, sh_gru_hhT);
-    }
+    if (vr.pho) add_stack(L.pho, sh_pho);
+    if (vr.arch) add_stack(L.outb, sh_out);
+    if (vr.pho) add(L.gru_w_hh, 3 * H, H, sh_gru_hh, sh_gru_hhT);
     if (d.size() > 256) return RL_ERR_ARG;
     if (hipMemcpyAsync(sh + sh_descs, d.data(), d.size() * sizeof(CastDesc), hipMemcpyHostToDevice, st) != hipSuccess) return RL_ERR_LAUNCH;
     n_descs = (int)d.size(); desc_tiles = tiles; descs_built = true;
@@ -369,15 +375,16 @@ template <typename T> struct Engine : EngineBase {
     // stream, the conv-weight launch (+ the glyph table when it changed) on the glyph stream, where the glyph branch of the
     // forward queues up behind it by itself.  ev_shadow[k] orders any OTHER consumer (a forward without branch streams, the
     // glyph-only entry points): wait_shadows().
-    const bool ovl = cfg.model_type == 1 && g_branch_overlap && branches_ok() && shadow_events_ok();
-    hipStream_t s_b = ovl ? bst[0] : st, s_c = ovl ? bst[1] : st;
+    // (the ablation model: a stream only for a branch that exists - without the pinyin branch the second group goes on the caller's stream)
+    const bool ovl = vr.arch && branch_mask() != 0 && g_branch_overlap && branches_ok() && shadow_events_ok();
+    hipStream_t s_b = ovl && vr.pho ? bst[0] : st, s_c = ovl && vr.res ? bst[1] : st;
     if (ovl) RL_TRY(fork(st));
     const CastDesc* dd = (const CastDesc*)(sh + sh_descs);
     if (!skip_linear) {
       RL_TRY(cast_transpose_multi<T>(st, dd, n_descs_a, desc_tiles_a));
       RL_TRY(cast_transpose_multi<T>(s_b, dd + n_descs_a, n_descs - n_descs_a, desc_tiles));
     }
-    if (cfg.model_type == 1) {
+    if (vr.res) {
       ConvShadowDescs cd;
       auto addc = [&](const float* w, int Co, int Ci, int KHW, int Cpad, T* fwd, T* dgrad, const TapOrder& ord = TapOrder()) {
         ConvShadowDesc& x = cd.d[cd.n++];
@@ -405,7 +412,7 @@ template <typename T> struct Engine : EngineBase {
     }
     shadows_pending = false;
     if (ovl) {
-      for (int k = 0; k < 2; ++k) if (hipEventRecord(ev_shadow[k], bst[k]) != hipSuccess) return RL_ERR_LAUNCH;
+      for (int k = 0; k < 2; ++k) if ((branch_mask() >> k & 1) && hipEventRecord(ev_shadow[k], bst[k]) != hipSuccess) return RL_ERR_LAUNCH;
       shadows_pending = true;
     }
     return RL_OK;
@@ -527,7 +534,7 @@ template <typename T> struct Engine : EngineBase {
   }
   int wait_shadows(hipStream_t s) {
     if (!shadows_pending) return RL_OK;
-    for (int k = 0; k < 2; ++k) if (hipStreamWaitEvent(s, ev_shadow[k], 0) != hipSuccess) return RL_ERR_LAUNCH;
+    for (int k = 0; k < 2; ++k) if ((branch_mask() >> k & 1) && hipStreamWaitEvent(s, ev_shadow[k], 0) != hipSuccess) return RL_ERR_LAUNCH;
     return RL_OK;
   }
 
@@ -560,7 +567,7 @@ template <typename T> struct Engine : EngineBase {
     };
     p.mask_add = b.take(Tk * 4);
     p.ids_clean = b.take(Tk * 8);
-    p.pho_clean = (!glyph_only && cfg.model_type == 1) ? b.take(Tk * (int64_t)(Tp > 0 ? Tp : 1) * 8) : 0;
+    p.pho_clean = (!glyph_only && vr.pho) ? b.take(Tk * (int64_t)(Tp > 0 ? Tp : 1) * 8) : 0;
     if (!glyph_only) {
       plan_stack(p.bert, cfg.bert_layers, "bert");
       p.out_d = b.take(Tk * H * e);
@@ -592,29 +599,34 @@ template <typename T> struct Engine : EngineBase {
       s0.gB = p.gB; s0.gE = p.gE; s0.rowdot = p.rowdot; s0.tn_slab = p.tn_slab; s0.tn_slab2 = p.tn_slab2; s0.ln_slots = p.ln_slots;
       for (int k = 0; k < 2; ++k) { s0.wC1[k] = p.wC1[k]; s0.wC2[k] = p.wC2[k]; s0.wD[k] = p.wD[k]; s0.wF[k] = p.wF[k]; }
       p.sc[1] = s0; p.sc[2] = s0;
-      if (cfg.model_type == 1) {
-        if (!glyph_only) {          // pho branch: a full private set (its layers run next to the bert layers)
+      if (vr.arch) {
+        if (!glyph_only && vr.pho) {          // pho branch: a full private set (its layers run next to the bert layers)
           typename Plan::Scratch& s1 = p.sc[1];
           s1.gB = b.take(Tk * H * e); s1.gE = b.take(Tk * H * e); s1.rowdot = b.take((int64_t)B * nh * S * 4);
           s1.tn_slab = b.take(TN_SLAB_ELEMS * 4); s1.tn_slab2 = s1.tn_slab; s1.ln_slots = b.take((int64_t)(LN_FOLD_MAX + 1) * LN_SLOT_BYTES);
           s1.wC1[0] = b.take(Tk * H * e); s1.wC2[0] = b.take(Tk * H * e); s1.wD[0] = b.take(Tk * I * e); s1.wF[0] = b.take(Tk * 3 * H * e);
           s1.wC1[1] = s1.wC1[0]; s1.wC2[1] = s1.wC2[0]; s1.wD[1] = s1.wD[0]; s1.wF[1] = s1.wF[0];
         }
-        typename Plan::Scratch& s2 = p.sc[2];   // glyph branch: LayerNorm-backward output, slabs of the conv weight gradients
-        s2.gE = b.take(Tk * H * e); s2.tn_slab = b.take(TN_SLAB_ELEMS * 4); s2.ln_slots = b.take((int64_t)(LN_FOLD_MAX + 1) * LN_SLOT_BYTES);
+        if (vr.res) {
+          typename Plan::Scratch& s2 = p.sc[2];   // glyph branch: LayerNorm-backward output, slabs of the conv weight gradients
+          s2.gE = b.take(Tk * H * e); s2.tn_slab = b.take(TN_SLAB_ELEMS * 4); s2.ln_slots = b.take((int64_t)(LN_FOLD_MAX + 1) * LN_SLOT_BYTES);
+        }
       }
     }
-    if (cfg.model_type == 1) {
+    if (vr.arch) {
       if (!glyph_only) {
-        plan_stack(p.pho, cfg.pho_layers, "pho_model");
+        if (vr.pho) plan_stack(p.pho, cfg.pho_layers, "pho_model");
         plan_stack(p.outb, cfg.out_layers, "output_block");
-        p.gru_table = b.take(64LL * 3 * H * 4);
-        p.gru_hs = b.take((int64_t)Tp * Tk * H * e);
-        p.gru_rzn = b.take((int64_t)Tp * Tk * 3 * H * e);
-        p.gru_gh = b.take((int64_t)Tp * Tk * 3 * H * e);
-        p.gru_out = b.take(Tk * H * e);
-        tap("pho_gru", p.gru_out, Tk * H);
+        if (vr.pho) {
+          p.gru_table = b.take(64LL * 3 * H * 4);
+          p.gru_hs = b.take((int64_t)Tp * Tk * H * e);
+          p.gru_rzn = b.take((int64_t)Tp * Tk * 3 * H * e);
+          p.gru_gh = b.take((int64_t)Tp * Tk * 3 * H * e);
+          p.gru_out = b.take(Tk * H * e);
+          tap("pho_gru", p.gru_out, Tk * H);
+        }
       }
+      if (vr.res) {
       int hin = cfg.glyph_size;
       for (int k = 0; k < 5; ++k) {
         BlockAct& a = p.blk[k];
@@ -637,15 +649,24 @@ template <typename T> struct Engine : EngineBase {
       tap("glyph.bounds", p.gu_bounds, 64 / (int64_t)sizeof(T)); tap("glyph.inv", p.gu_inv, Tk * 4 / (int64_t)sizeof(T));
       tap("glyph.counts", p.gu_counts, Tk * 4 / (int64_t)sizeof(T)); tap("glyph.ids", p.gu_ids, Tk * 8 / (int64_t)sizeof(T));
       p.res_xhat = b.take(Tk * H * e); p.res_rstd = b.take(Tk * 4); p.res_h = b.take(Tk * H * e);
-      p.gate_mean = b.take((int64_t)B * H * 4); p.gate_msum = b.take(B * 4 + 256); p.gate_g = b.take(Tk * 16);
+      tap("res_h", p.res_h, Tk * H);
+      }
+      if (vr.gate) { p.gate_mean = b.take((int64_t)B * H * 4); p.gate_msum = b.take(B * 4 + 256); p.gate_g = b.take(Tk * 16); }
       p.fused = b.take(Tk * H * e);
-      tap("res_h", p.res_h, Tk * H); tap("fused", p.fused, Tk * H);
-      p.X1 = b.take(Tk * H * e); p.X2 = b.take(Tk * H * e); p.X3 = b.take(Tk * H * e); p.dz = b.take(Tk * 16);
-      p.gru_dh = b.take(Tw * H * e); p.gru_dgi = b.take(Tw * 3 * H * e); p.gru_dgh = b.take(Tw * 3 * H * e);
-      p.gru_onehot = b.take(Tw * 64 * e); p.gru_dtable = b.take(64LL * 3 * H * 4);
-      const int64_t big = (int64_t)p.blk[0].Pout * 64 * e;     // block 1 is the largest activation
-      p.r_dout = b.take(big); p.r_dc2 = b.take(big); p.r_dcs = b.take(big); p.r_dh1 = b.take(big); p.r_dc1 = b.take(big);
-      p.r_dx = b.take(big);
+      tap("fused", p.fused, Tk * H);
+      p.X1 = b.take(Tk * H * e);
+      if (vr.pho) p.X2 = b.take(Tk * H * e);
+      if (vr.res) p.X3 = b.take(Tk * H * e);
+      if (vr.gate) p.dz = b.take(Tk * 16);
+      if (vr.pho) {
+        p.gru_dh = b.take(Tw * H * e); p.gru_dgi = b.take(Tw * 3 * H * e); p.gru_dgh = b.take(Tw * 3 * H * e);
+        p.gru_onehot = b.take(Tw * 64 * e); p.gru_dtable = b.take(64LL * 3 * H * 4);
+      }
+      if (vr.res) {
+        const int64_t big = (int64_t)p.blk[0].Pout * 64 * e;     // block 1 is the largest activation
+        p.r_dout = b.take(big); p.r_dc2 = b.take(big); p.r_dcs = b.take(big); p.r_dh1 = b.take(big); p.r_dc1 = b.take(big);
+        p.r_dx = b.take(big);
+      }
     }
     {   // named views of the scratch regions (diagnostics: tools/diag_stale.py zeroes them one at a time)
       const int64_t e1 = (int64_t)sizeof(T);
@@ -653,13 +674,15 @@ template <typename T> struct Engine : EngineBase {
       stap("tn_slab", p.tn_slab, TN_SLAB_ELEMS * 4); stap("ln_slots", p.ln_slots, LN_SLOT_BYTES);
       stap("gA", p.gA, Tk * H * e); stap("gB", p.gB, Tk * H * e); stap("gC", p.gC, Tk * H * e); stap("gE", p.gE, Tk * H * e);
       stap("gD", p.gD, Tw * I * e); stap("gF", p.gF, Tw * 3 * H * e);
-      if (cfg.model_type == 1) {
+      if (vr.res) {
         const int64_t big = (int64_t)p.blk[0].Pout * 64 * e;
         stap("r_dout", p.r_dout, big); stap("r_dc2", p.r_dc2, big); stap("r_dcs", p.r_dcs, big); stap("r_dh1", p.r_dh1, big);
         stap("r_dc1", p.r_dc1, big); stap("r_dx", p.r_dx, big); stap("bn_sums", p.bn_sums, 2 * 1024 * 4);
         stap("bn_slots", p.bn_slots, (int64_t)COL_SLOT_BYTES); stap("seg_acc", p.seg_acc, Tk * H * 4);
-        stap("X1", p.X1, Tk * H * e); stap("X2", p.X2, Tk * H * e); stap("X3", p.X3, Tk * H * e);
       }
+      if (vr.arch) stap("X1", p.X1, Tk * H * e);
+      if (vr.pho) stap("X2", p.X2, Tk * H * e);
+      if (vr.res) stap("X3", p.X3, Tk * H * e);
     }
     p.total = b.off;
     return p;
@@ -1194,8 +1217,10 @@ template <typename T> struct Engine : EngineBase {
 
   GateArgs<T> gate_args() const {
     GateArgs<T> g;
-    g.B = pl.B; g.S = pl.S; g.H = H;
-    g.bert = wp<T>(pl.bert.layers.back().y2); g.pho = wp<T>(pl.pho.layers.back().y2); g.res = wp<T>(pl.res_h);
+    g.B = pl.B; g.S = pl.S; g.H = H; g.nsrc = vr.nsrc;
+    g.bert = wp<T>(pl.bert.layers.back().y2);
+    g.pho = vr.pho ? wp<T>(pl.pho.layers.back().y2) : nullptr;
+    g.res = vr.res ? wp<T>(pl.res_h) : nullptr;
     g.masks = last.masks; g.W = pp(L.gate_w); g.bias = pp(L.gate_b);
     g.mean = wp<float>(pl.gate_mean); g.msum = wp<float>(pl.gate_msum); g.g = wp<float>(pl.gate_g); g.fused = wp<T>(pl.fused);
     return g;
@@ -1230,8 +1255,8 @@ template <typename T> struct Engine : EngineBase {
   int forward(hipStream_t st, const realise_batch& b) override {
     if (!sh || !ws) return RL_ERR_ARG;
     if (b.B < 1 || b.S < 1 || b.S > cfg.max_pos) return RL_ERR_ARG;       // (S > 128: the tiled attention kernels, attention.hip)
-    const int Tp = cfg.model_type == 1 ? b.Tp : 1;
-    if (cfg.model_type == 1 && (Tp < 1 || !b.pho_idx || !b.pho_perm || !b.pho_lens_sorted || (!b.n_alive && !b.n_alive_dev))) return RL_ERR_ARG;
+    const int Tp = vr.pho ? b.Tp : 1;
+    if (vr.pho && (Tp < 1 || !b.pho_idx || !b.pho_perm || !b.pho_lens_sorted || (!b.n_alive && !b.n_alive_dev))) return RL_ERR_ARG;
     if (pl.B != b.B || pl.S != b.S || pl.Tp != Tp) {
       RL_TRY(install_plan(st, make_plan(b.B, b.S, Tp)));
     }
@@ -1243,8 +1268,8 @@ template <typename T> struct Engine : EngineBase {
     last_alive.assign(Tp, 0);
     // host counts (the reference's contract: pho_lens is a host list) or, after realise_build_pho, device counts: every
     // step is then launched over all B*S rows and bounded on the device
-    if (cfg.model_type == 1) for (int t = 0; t < Tp; ++t) last_alive[t] = b.n_alive ? b.n_alive[t] : b.B * b.S;
-    alive_dev = (cfg.model_type == 1 && !b.n_alive) ? b.n_alive_dev : nullptr;
+    if (vr.pho) for (int t = 0; t < Tp; ++t) last_alive[t] = b.n_alive ? b.n_alive[t] : b.B * b.S;
+    alive_dev = (vr.pho && !b.n_alive) ? b.n_alive_dev : nullptr;
     last.n_alive = nullptr;
     have_fwd = false;
     const int Tk = b.B * b.S;
@@ -1252,9 +1277,11 @@ template <typename T> struct Engine : EngineBase {
     // everything below (and the backward) reads range-checked copies of the ids: a bad id raises in the module, never faults here
     RL_TRY(sanitize_ids(st, b.src_idx, Tk, V, wp<int64_t>(pl.ids_clean), id_flag));
     last.src_idx = wp<int64_t>(pl.ids_clean);
-    if (cfg.model_type == 1) {
+    if (vr.pho) {
       RL_TRY(sanitize_ids(st, b.pho_idx, (int64_t)Tk * Tp, cfg.pho_vocab, wp<int64_t>(pl.pho_clean), id_flag));
       last.pho_idx = wp<int64_t>(pl.pho_clean);
+    } else {
+      last.pho_idx = nullptr; last.pho_perm = nullptr; last.pho_lens_sorted = nullptr;      // (a batch may carry pinyin nobody reads)
     }
     // Rows after a sentence's last real / loss position are padding no query attends to and no loss term reads: every backward
     // activation row there is an exact zero (the embedding scatter has relied on it since round 1).  The backward skips them
@@ -1275,7 +1302,8 @@ template <typename T> struct Engine : EngineBase {
       dead_ok = true; rows_live = true;      // (the tables exist; no backward follows an evaluation forward)
     }
     const T* bert_h = nullptr;
-    const bool ovl = cfg.model_type == 1 && g_branch_overlap && branches_ok();
+    // (with no side branch - the ablation model with neither - there is nothing to fork: everything stays on the caller's stream)
+    const bool ovl = vr.arch && branch_mask() != 0 && g_branch_overlap && branches_ok();
     hipStream_t s_pho = ovl ? bst[0] : st, s_glyph = ovl ? bst[1] : st;
     // operand copies refreshed on the branch streams (refresh_shadows): with the branch streams in use below, each branch is already
     // ordered behind its own copies and the caller's stream meets the classifier / output-stack copies at the join; otherwise wait here
@@ -1285,14 +1313,16 @@ template <typename T> struct Engine : EngineBase {
     // shorter branches reach the GPU only after that, enqueued last (1) they start at once and bert joins them ~0.4 ms later.
     if (!(ovl && g_fwd_order == 1)) RL_TRY(stack_forward(st, 0, L.bert, sh_bert, pl.bert, last.src_idx, nullptr, 0, &bert_h));
     const T* top = bert_h;
-    if (cfg.model_type == 1) {
-      RL_TRY(wait_opt(s_pho, opt_groups));                          // (pipelined sweep: pinyin / output stacks and the GRU are one piece)
-      RL_TRY(gru_forward(s_pho));
-      const T* pho_h = nullptr;
-      RL_TRY(stack_forward(s_pho, 1, L.pho, sh_pho, pl.pho, nullptr, wp<T>(pl.gru_out), 0, &pho_h));
-      const T* res = nullptr;
-      RL_TRY(resnet_forward(s_glyph, last.src_idx, &res));
-      {
+    if (vr.arch) {
+      if (vr.pho) {
+        RL_TRY(wait_opt(s_pho, opt_groups));                        // (pipelined sweep: pinyin / output stacks and the GRU are one piece)
+        RL_TRY(gru_forward(s_pho));
+        const T* pho_h = nullptr;
+        RL_TRY(stack_forward(s_pho, 1, L.pho, sh_pho, pl.pho, nullptr, wp<T>(pl.gru_out), 0, &pho_h));
+      }
+      if (vr.res) {
+        const T* res = nullptr;
+        RL_TRY(resnet_forward(s_glyph, last.src_idx, &res));
         LnFwdArgs<T> ln; ln.rows = Tk; ln.H = H; ln.x = res; ln.row_index = wp<int>(pl.gu_inv);      // token t reads its glyph's row
         ln.gamma = pp(L.res_ln_g); ln.beta = pp(L.res_ln_b); ln.eps = cfg.ln_eps;
         ln.y = wp<T>(pl.res_h); ln.xhat = bwd_follows() ? wp<T>(pl.res_xhat) : nullptr; ln.rstd = wp<float>(pl.res_rstd);
@@ -1301,7 +1331,8 @@ template <typename T> struct Engine : EngineBase {
       if (ovl && g_fwd_order == 1) { RL_TRY(stack_forward(st, 0, L.bert, sh_bert, pl.bert, last.src_idx, nullptr, 0, &bert_h)); top = bert_h; }
       if (ovl) RL_TRY(join(st));
       RL_TRY(sync_optimizer(st));                                   // every piece of a pipelined sweep is now in front of this stream
-      RL_TRY(gate_fwd<T>(st, gate_args()));
+      if (vr.gate) RL_TRY(gate_fwd<T>(st, gate_args()));
+      else RL_TRY(sum_fuse_fwd<T>(st, bert_h, wp<T>(pl.pho.layers.back().y2), wp<T>(pl.res_h), wp<T>(pl.fused), Tk, H));
       RL_TRY(stack_forward(st, 2, L.outb, sh_out, pl.outb, nullptr, wp<T>(pl.fused), 1, &top));
     }
     RL_TRY(sync_optimizer(st));
@@ -1366,7 +1397,7 @@ template <typename T> struct Engine : EngineBase {
   // res_out[t, :] = resnet(char_images_multifonts[src_idx[t]]), before resnet_layernorm.
   bool have_glyph_fwd = false;
   int glyph_forward(hipStream_t st, const int64_t* ids, int B, int S, int training, void* res_out) override {
-    if (!sh || !ws || cfg.model_type != 1 || !ids || !res_out || B < 1 || S < 1) return RL_ERR_ARG;
+    if (!sh || !ws || !vr.res || !ids || !res_out || B < 1 || S < 1) return RL_ERR_ARG;
     RL_TRY(sync_optimizer(st));
     if (pl.B != B || pl.S != S || pl.Tp != -1) {
       RL_TRY(install_plan(st, make_plan(B, S, -1)));
@@ -1417,7 +1448,8 @@ template <typename T> struct Engine : EngineBase {
         }
       };
       add_stack(L.bert);
-      if (cfg.model_type == 1) { add_stack(L.pho); add_stack(L.outb); }
+      if (vr.pho) add_stack(L.pho);
+      if (vr.arch) add_stack(L.outb);
       std::sort(skip.begin(), skip.end());
       fill_host.clear();
       int64_t at = 0;
@@ -1449,7 +1481,7 @@ template <typename T> struct Engine : EngineBase {
     const T* dl = wp<T>(pl.dlogits);
     T* gA = wp<T>(pl.gA);
     const DropParams dfin = site(5000, cfg.hidden_dropout);
-    const T* top = cfg.model_type == 1 ? wp<T>(pl.outb.layers.back().y2) : wp<T>(pl.bert.layers.back().y2);
+    const T* top = vr.arch ? wp<T>(pl.outb.layers.back().y2) : wp<T>(pl.bert.layers.back().y2);
     const T* cls_in = dfin.thresh ? wp<T>(pl.out_d) : top;
     if (cls_compact) {
       const int* n_act = wp<int>(pl.cls_nact);
@@ -1478,7 +1510,7 @@ template <typename T> struct Engine : EngineBase {
   int run_stage(hipStream_t st, int s) {
     const int Tk = pl.B * pl.S;
     T* gA = wp<T>(pl.gA);
-    if (cfg.model_type == 0) {
+    if (!vr.arch) {
       // stage g (0..groups-1): bert layer group g (stage 0 also runs the head); last stage: embeddings
       const int groups = L.bert_groups;
       if (s < groups) {
@@ -1491,14 +1523,16 @@ template <typename T> struct Engine : EngineBase {
       }
       return RL_OK;
     }
-    switch (s) {
-      case 0: RL_TRY(stage_out_block(st)); break;
-      case 1: RL_TRY(stage_gate(st)); RL_TRY(stage_glyph(st)); break;
-      case 2: RL_TRY(stage_pho(st)); break;
-      default: RL_TRY(stage_bert(st, s - 3)); break;
+    // stages = buckets: 0 output_block | 1 fusion (+ glyph ResNet) | 2 pinyin branch (when present) | bert groups | bert embeddings
+    if (s == 0) return stage_out_block(st);
+    if (s == 1) {
+      RL_TRY(stage_fuse(st));
+      return vr.res ? stage_glyph(st) : RL_OK;
     }
-    return RL_OK;
+    if (vr.pho && s == 2) return stage_pho(st);
+    return stage_bert(st, s - first_bert_stage());
   }
+  int first_bert_stage() const { return vr.pho ? 3 : 2; }
   int stage_out_block(hipStream_t st) {      // head + output_block; leaves d fused in gB (set 0)
     T* gA = wp<T>(pl.gA);
     RL_TRY(stage_head(st));
@@ -1506,9 +1540,11 @@ template <typename T> struct Engine : EngineBase {
     RL_TRY(emb_backward(st, 2, L.outb, pl.outb, nullptr, 1, gA, wp<T>(pl.sc[0].gB)));
     return RL_OK;
   }
-  int stage_gate(hipStream_t st) {           // d fused -> X1 (d bert), X2 (d pho), X3 (d res) + gate_net gradients
+  int stage_fuse(hipStream_t st) {           // d fused -> X1 (d bert), X2 (d pho), X3 (d res) [+ gate_net gradients]
+    if (!vr.gate) return sum_fuse_bwd<T>(st, wp<T>(pl.sc[0].gB), wp<T>(pl.X1), wp<T>(pl.X2), wp<T>(pl.X3), pl.B * pl.S, H, live_rows());
     GateArgs<T> g = gate_args();
-    g.dfused = wp<T>(pl.sc[0].gB); g.dbert = wp<T>(pl.X1); g.dpho = wp<T>(pl.X2); g.dres = wp<T>(pl.X3); g.dz = wp<float>(pl.dz);
+    g.dfused = wp<T>(pl.sc[0].gB); g.dbert = wp<T>(pl.X1); g.dz = wp<float>(pl.dz);
+    g.dpho = vr.pho ? wp<T>(pl.X2) : nullptr; g.dres = vr.res ? wp<T>(pl.X3) : nullptr;
     g.dW = gp(L.gate_w); g.dbias = gp(L.gate_b); g.row_live = live_rows();
     return gate_bwd<T>(st, g);
   }
@@ -1564,20 +1600,21 @@ template <typename T> struct Engine : EngineBase {
     for (int i = 0; i < n; ++i) if (evs[i] == nullptr) return RL_ERR_ARG;
     RL_TRY(begin_gradient_pass(st, false));
     cs = 0;
-    if (cfg.model_type == 1 && g_branch_overlap && branches_ok()) {
+    if (vr.arch && g_branch_overlap && (branch_mask() == 0 || branches_ok())) {
       branch_mode = true;
+      const int b0 = first_bert_stage();
       int rc = stage_out_block(st);
       if (rc == RL_OK) rc = signal_bucket(evs[0], st, true, 0);
-      if (rc == RL_OK) rc = stage_gate(st);
+      if (rc == RL_OK) rc = stage_fuse(st);
       if (rc == RL_OK) rc = fork(st);
-      if (rc == RL_OK) { cs = 2; rc = stage_glyph(bst[1]); }
-      if (rc == RL_OK) rc = signal_bucket(evs[1], bst[1], false, 1);          // gate (before the fork) + glyph ResNet
-      if (rc == RL_OK) { cs = 1; rc = stage_pho(bst[0]); }
-      if (rc == RL_OK) rc = signal_bucket(evs[2], bst[0], false, 2);
+      if (rc == RL_OK && vr.res) { cs = 2; rc = stage_glyph(bst[1]); }
+      if (rc == RL_OK) rc = signal_bucket(evs[1], vr.res ? bst[1] : st, false, 1);      // fusion (before the fork) + glyph ResNet
+      if (rc == RL_OK && vr.pho) { cs = 1; rc = stage_pho(bst[0]); }
+      if (rc == RL_OK && vr.pho) rc = signal_bucket(evs[2], bst[0], false, 2);
       cs = 0;
       for (int g = 0; rc == RL_OK && g <= L.bert_groups; ++g) {
         rc = stage_bert(st, g);
-        if (rc == RL_OK) rc = signal_bucket(evs[3 + g], st, true, 3 + g);
+        if (rc == RL_OK) rc = signal_bucket(evs[b0 + g], st, true, b0 + g);
       }
       const int rj = join(st);
       const int rs = join_side(st);
@@ -1599,13 +1636,13 @@ template <typename T> struct Engine : EngineBase {
     if (first == 0) RL_TRY(begin_gradient_pass(st, false));           // (a bucket-by-bucket caller starts its pass with stage 0)
     cs = 0;
     // whole pass in one call (no per-bucket gradient exchange in between): the three branches behind the gate run concurrently
-    if (cfg.model_type == 1 && first == 0 && last_stage == n - 1 && g_branch_overlap && branches_ok()) {
+    if (vr.arch && first == 0 && last_stage == n - 1 && g_branch_overlap && (branch_mask() == 0 || branches_ok())) {
       branch_mode = true;
       int rc = stage_out_block(st);
-      if (rc == RL_OK) rc = stage_gate(st);
+      if (rc == RL_OK) rc = stage_fuse(st);
       if (rc == RL_OK) rc = fork(st);
-      if (rc == RL_OK) { cs = 2; rc = stage_glyph(bst[1]); }
-      if (rc == RL_OK) { cs = 1; rc = stage_pho(bst[0]); }
+      if (rc == RL_OK && vr.res) { cs = 2; rc = stage_glyph(bst[1]); }
+      if (rc == RL_OK && vr.pho) { cs = 1; rc = stage_pho(bst[0]); }
       cs = 0;
       for (int g = 0; rc == RL_OK && g <= L.bert_groups; ++g) rc = stage_bert(st, g);
       const int rj = join(st);
@@ -1620,7 +1657,8 @@ template <typename T> struct Engine : EngineBase {
 
 EngineBase* make_engine(const realise_config& c, float* p, float* g, float* pu, float* fz, float* bf, int64_t* bi) {
   if (c.hidden % 64 || c.hidden / c.heads != 64 || c.hidden > 1024 || (c.intermediate % 8) || (c.vocab % 8)) return nullptr;
-  if (c.model_type == 1 && c.hidden != 768) return nullptr;     // CharResNet output is 768 wide (char_cnn.py:44)
+  if (!variant_valid(c)) return nullptr;
+  if (variant_of(c).res && c.hidden != 768) return nullptr;     // CharResNet output is 768 wide (char_cnn.py:44)
   if (c.dtype == REALISE_BF16) return new Engine<bf16_t>(c, p, g, pu, fz, bf, bi);
   if (c.dtype == REALISE_F32) return new Engine<float>(c, p, g, pu, fz, bf, bi);
   return nullptr;

@@ -46,6 +46,34 @@ struct Layout {
 
 inline int64_t align64(int64_t x) { return (x + 63) & ~(int64_t)63; }
 
+// What a configuration computes: SpellBert is the bert stack alone, SpellBertPho2ResArch3 has every branch, the ablation model
+// (model_type 2, src/models_abla.py:33-96) what its switches keep.  Every layout / engine decision reads this, not model_type.
+struct Variant {
+  bool arch = false;     // output_block behind a fusion of the branches (model_type 1, 2)
+  bool pho = false;      // pinyin branch: pho_embeddings, pho_gru, pho_model
+  bool res = false;      // glyph branch: glyph table, resnet, resnet_layernorm
+  bool gate = false;     // gate fusion (gate_net); false on an arch model: sum fusion
+  int nsrc = 1;          // fusion sources: bert + the present branches
+};
+inline Variant variant_of(const realise_config& c) {
+  Variant v;
+  v.arch = c.model_type == 1 || c.model_type == 2;
+  if (!v.arch) return v;
+  const bool abla = c.model_type == 2;
+  v.pho = !abla || c.with_pho != 0;
+  v.res = !abla || c.with_res != 0;
+  v.gate = !abla || c.fusion == 0;
+  v.nsrc = 1 + (v.pho ? 1 : 0) + (v.res ? 1 : 0);
+  return v;
+}
+// model_type 2 fields in range, sum fusion only with both branches (the reference's sum path adds None otherwise)
+inline bool variant_valid(const realise_config& c) {
+  if (c.model_type < 0 || c.model_type > 2) return false;
+  if (c.model_type != 2) return true;
+  if ((c.with_pho != 0 && c.with_pho != 1) || (c.with_res != 0 && c.with_res != 1) || (c.fusion != 0 && c.fusion != 1)) return false;
+  return c.fusion == 0 || (c.with_pho == 1 && c.with_res == 1);
+}
+
 inline Layout build_layout(const realise_config& c) {
   Layout L;
   const int64_t H = c.hidden, I = c.intermediate, V = c.vocab;
@@ -116,48 +144,56 @@ inline Layout build_layout(const realise_config& c) {
     return b;
   };
 
-  const bool arch3 = c.model_type == 1;
+  const Variant vr = variant_of(c);
   int64_t begin = 0;
   L.bert.layers.resize(c.bert_layers);
   // ---- bucket 0: classifier bias (+ untied weight), output_block
   L.cls_b = add(AR_TRAIN, "classifier.bias", {V});
   if (!c.tie_classifier) L.cls_w = add(AR_TRAIN, "classifier.weight", {V, H});
-  if (arch3) {
+  if (vr.arch) {
     L.outb.layers.resize(c.out_layers);
     add_layers_desc(L.outb, "output_block.", c.out_layers - 1, 0);
     add_emb(L.outb, "output_block.", false);
     close_bucket(begin);
-    // ---- bucket 1: gate, resnet LN, glyph ResNet (blocks 5..1)
-    L.gate_w = add(AR_TRAIN, "gate_net.weight", {3, 4 * H});
-    L.gate_b = add(AR_TRAIN, "gate_net.bias", {3});
-    L.res_ln_g = add(AR_TRAIN, "resnet_layernorm.weight", {H});
-    L.res_ln_b = add(AR_TRAIN, "resnet_layernorm.bias", {H});
-    const int chans[6] = {c.num_fonts, 64, 128, 256, 512, 768};
-    for (int b = 5; b >= 1; --b) {
-      BlockOff& k = L.blocks[b - 1];
-      k.cin = chans[b - 1]; k.cout = chans[b];
-      const std::string p = "resnet.res_block" + std::to_string(b) + ".";
-      k.w2 = add(AR_TRAIN, p + "residual_function.3.weight", {k.cout, k.cout, 3, 3});
-      k.bn2 = add_bn(p + "residual_function.4.", k.cout);
-      k.ws = add(AR_TRAIN, p + "shortcut.0.weight", {k.cout, k.cin, 1, 1});
-      k.bns = add_bn(p + "shortcut.1.", k.cout);
-      k.w1 = add(AR_TRAIN, p + "residual_function.0.weight", {k.cout, k.cin, 3, 3});
-      k.bn1 = add_bn(p + "residual_function.1.", k.cout);
+    // ---- bucket 1: gate [G, (G+1)H] (models_abla.py:86-87), resnet LN, glyph ResNet (blocks 5..1) - never empty: sum fusion has both branches
+    if (vr.gate) {
+      L.gate_w = add(AR_TRAIN, "gate_net.weight", {vr.nsrc, (vr.nsrc + 1) * H});
+      L.gate_b = add(AR_TRAIN, "gate_net.bias", {vr.nsrc});
+    }
+    if (vr.res) {
+      L.res_ln_g = add(AR_TRAIN, "resnet_layernorm.weight", {H});
+      L.res_ln_b = add(AR_TRAIN, "resnet_layernorm.bias", {H});
+      const int chans[6] = {c.num_fonts, 64, 128, 256, 512, 768};
+      for (int b = 5; b >= 1; --b) {
+        BlockOff& k = L.blocks[b - 1];
+        k.cin = chans[b - 1]; k.cout = chans[b];
+        const std::string p = "resnet.res_block" + std::to_string(b) + ".";
+        k.w2 = add(AR_TRAIN, p + "residual_function.3.weight", {k.cout, k.cout, 3, 3});
+        k.bn2 = add_bn(p + "residual_function.4.", k.cout);
+        k.ws = add(AR_TRAIN, p + "shortcut.0.weight", {k.cout, k.cin, 1, 1});
+        k.bns = add_bn(p + "shortcut.1.", k.cout);
+        k.w1 = add(AR_TRAIN, p + "residual_function.0.weight", {k.cout, k.cin, 3, 3});
+        k.bn1 = add_bn(p + "residual_function.1.", k.cout);
+      }
     }
     close_bucket(begin);
-    // ---- bucket 2: pho_model, GRU, pinyin embedding
-    L.pho.layers.resize(c.pho_layers);
-    add_layers_desc(L.pho, "pho_model.", c.pho_layers - 1, 0);
-    add_emb(L.pho, "pho_model.", false);
-    L.gru_w_hh = add(AR_TRAIN, "pho_gru.weight_hh_l0", {3 * H, H});
-    L.gru_b_hh = add(AR_TRAIN, "pho_gru.bias_hh_l0", {3 * H});
-    L.gru_w_ih = add(AR_TRAIN, "pho_gru.weight_ih_l0", {3 * H, H});
-    L.gru_b_ih = add(AR_TRAIN, "pho_gru.bias_ih_l0", {3 * H});
-    L.pho_emb = add(AR_TRAIN, "pho_embeddings.weight", {c.pho_vocab, H});
-    close_bucket(begin);
+    // ---- bucket 2 (with the pinyin branch): pho_model, GRU, pinyin embedding
+    if (vr.pho) {
+      L.pho.layers.resize(c.pho_layers);
+      add_layers_desc(L.pho, "pho_model.", c.pho_layers - 1, 0);
+      add_emb(L.pho, "pho_model.", false);
+      L.gru_w_hh = add(AR_TRAIN, "pho_gru.weight_hh_l0", {3 * H, H});
+      L.gru_b_hh = add(AR_TRAIN, "pho_gru.bias_hh_l0", {3 * H});
+      L.gru_w_ih = add(AR_TRAIN, "pho_gru.weight_ih_l0", {3 * H, H});
+      L.gru_b_ih = add(AR_TRAIN, "pho_gru.bias_ih_l0", {3 * H});
+      L.pho_emb = add(AR_TRAIN, "pho_embeddings.weight", {c.pho_vocab, H});
+      close_bucket(begin);
+    }
     // models.py:674-679: one font -> nn.Embedding "char_images.weight" [V, 1024]; several -> Parameter [V, F, 32, 32].  Same bytes.
-    if (c.num_fonts == 1) L.glyph = add(AR_FROZEN, "char_images.weight", {V, (int64_t)c.glyph_size * c.glyph_size});
-    else L.glyph = add(AR_FROZEN, "char_images_multifonts", {V, c.num_fonts, c.glyph_size, c.glyph_size});
+    if (vr.res) {
+      if (c.num_fonts == 1) L.glyph = add(AR_FROZEN, "char_images.weight", {V, (int64_t)c.glyph_size * c.glyph_size});
+      else L.glyph = add(AR_FROZEN, "char_images_multifonts", {V, c.num_fonts, c.glyph_size, c.glyph_size});
+    }
   }
   // ---- bert layers in groups of <= 4 (one bucket each)
   {

@@ -144,9 +144,16 @@ template <typename T> struct GateArgs {
   // optional byte per token row (row_liveness): 0 = a padding row behind the sentence's last attended / loss position.  Its d fused row is an
   // exact zero, so the backward writes its zeros without reading the row's (possibly stale - live-row steps) forward activations.
   const uint8_t* row_live = nullptr;
+  // number of gated sources (src/models_abla.py:239-275): bert, then pho and res where non-null (nsrc = 2: exactly one of them).
+  // W is [nsrc][(nsrc + 1) H], bias [nsrc]; g / dz keep their row pitch of 4.  3 = SpellBertPho2ResArch3.
+  int nsrc = 3;
 };
 template <typename T> int gate_fwd(hipStream_t st, const GateArgs<T>& a);
 template <typename T> int gate_bwd(hipStream_t st, const GateArgs<T>& a);
+// sum fusion (src/models_abla.py:278-279): fused = (bert + pho) + res in fp32; the backward copies d fused to the three branches
+template <typename T> int sum_fuse_fwd(hipStream_t st, const T* bert, const T* pho, const T* res, T* fused, int rows, int H);
+template <typename T> int sum_fuse_bwd(hipStream_t st, const T* dfused, T* dbert, T* dpho, T* dres, int rows, int H,
+                                       const uint8_t* row_live = nullptr);      // row_live: padding rows (0) get exact zeros
 
 // ---- pinyin GRU (K6) ------------------------------------------------------------------------------
 template <typename T> struct GruStepArgs {

@@ -1626,137 +1626,195 @@ __global__ void __launch_bounds__(256) gate_mean_kernel(GateArgs<T> a) {
   }
 }
 
-template <typename T>
+// The gate family is instantiated per number of sources NSRC (src/models_abla.py:239-275): bert, then pho and res where present.
+// W rows are (NSRC + 1) H wide, [src 0 | ... | src NSRC-1 | mean]; g / dz rows keep a pitch of 4 (unused slots hold 0).  NSRC = 3 is
+// SpellBertPho2ResArch3 and performs the same operations in the same order as the three-source kernels always did.
+template <typename T, int NSRC> __device__ __forceinline__ void gate_sources(const GateArgs<T>& a, const T* (&x)[NSRC]) {
+  x[0] = a.bert;
+  if constexpr (NSRC == 3) { x[1] = a.pho; x[2] = a.res; }
+  if constexpr (NSRC == 2) x[1] = a.pho != nullptr ? a.pho : a.res;
+}
+template <typename T, int NSRC> __device__ __forceinline__ void gate_grads(const GateArgs<T>& a, T* (&d)[NSRC]) {
+  d[0] = a.dbert;
+  if constexpr (NSRC == 3) { d[1] = a.dpho; d[2] = a.dres; }
+  if constexpr (NSRC == 2) d[1] = a.pho != nullptr ? a.dpho : a.dres;
+}
+
+template <typename T, int NSRC>
 __global__ void __launch_bounds__(256) gate_fwd_kernel(GateArgs<T> a) {   // one wave per token
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + wave;
   if (row >= a.B * a.S) return;
   const int H = a.H, b = row / a.S;
-  floatx4 xb[LN_MAXV], xp[LN_MAXV], xr[LN_MAXV];
-  float z[3] = {0.f, 0.f, 0.f};
+  const T* src[NSRC];
+  gate_sources<T, NSRC>(a, src);
+  floatx4 xs[NSRC][LN_MAXV];
+  float z[NSRC];
+#pragma unroll
+  for (int k = 0; k < NSRC; ++k) z[k] = 0.f;
 #pragma unroll
   for (int i = 0; i < LN_MAXV; ++i) {
     const int c = (i * 64 + lane) * 4;
     if (c < H) {
-      xb[i] = load4<T>(a.bert + (int64_t)row * H + c);
-      xp[i] = load4<T>(a.pho + (int64_t)row * H + c);
-      xr[i] = load4<T>(a.res + (int64_t)row * H + c);
+#pragma unroll
+      for (int d = 0; d < NSRC; ++d) xs[d][i] = load4<T>(src[d] + (int64_t)row * H + c);
       const floatx4 xm = *(const floatx4*)(a.mean + (int64_t)b * H + c);
 #pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const float* w = a.W + (int64_t)k * 4 * H + c;
-        const floatx4 w0 = *(const floatx4*)w, w1 = *(const floatx4*)(w + H), w2 = *(const floatx4*)(w + 2 * H),
-                      w3 = *(const floatx4*)(w + 3 * H);
+      for (int k = 0; k < NSRC; ++k) {
+        const float* w = a.W + (int64_t)k * (NSRC + 1) * H + c;
+        floatx4 wd[NSRC + 1];
 #pragma unroll
-        for (int j = 0; j < 4; ++j) z[k] += w0[j] * xb[i][j] + w1[j] * xp[i][j] + w2[j] * xr[i][j] + w3[j] * xm[j];
+        for (int d = 0; d <= NSRC; ++d) wd[d] = *(const floatx4*)(w + d * H);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          float t = wd[0][j] * xs[0][i][j];
+#pragma unroll
+          for (int d = 1; d < NSRC; ++d) t = t + wd[d][j] * xs[d][i][j];
+          z[k] += t + wd[NSRC][j] * xm[j];
+        }
       }
     }
   }
-  float gk[3];
+  float gk[NSRC];
 #pragma unroll
-  for (int k = 0; k < 3; ++k) gk[k] = sigmoidf_(wave_sum(z[k]) + a.bias[k]);
-  if (lane == 0) { a.g[row * 4 + 0] = gk[0]; a.g[row * 4 + 1] = gk[1]; a.g[row * 4 + 2] = gk[2]; a.g[row * 4 + 3] = 0.f; }
+  for (int k = 0; k < NSRC; ++k) gk[k] = sigmoidf_(wave_sum(z[k]) + a.bias[k]);
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) a.g[row * 4 + k] = k < NSRC ? gk[k < NSRC ? k : 0] : 0.f;
+  }
 #pragma unroll
   for (int i = 0; i < LN_MAXV; ++i) {
     const int c = (i * 64 + lane) * 4;
-    if (c < H) store4<T>(a.fused + (int64_t)row * H + c, xb[i] * gk[0] + xp[i] * gk[1] + xr[i] * gk[2]);
+    if (c < H) {
+      floatx4 f = xs[0][i] * gk[0];
+#pragma unroll
+      for (int d = 1; d < NSRC; ++d) f = f + xs[d][i] * gk[d];
+      store4<T>(a.fused + (int64_t)row * H + c, f);
+    }
   }
 }
+template <typename T> static bool gate_args_ok(const GateArgs<T>& a) {
+  if ((a.H & 3) || a.H > LN_MAXV * 256 || a.nsrc < 1 || a.nsrc > 3) return false;
+  if (a.nsrc == 3) return a.pho != nullptr && a.res != nullptr;
+  if (a.nsrc == 2) return (a.pho != nullptr) != (a.res != nullptr);
+  return true;
+}
 template <typename T> int gate_fwd(hipStream_t st, const GateArgs<T>& a) {
-  if ((a.H & 3) || a.H > LN_MAXV * 256) return RL_ERR_ARG;
+  if (!gate_args_ok(a)) return RL_ERR_ARG;
   hipLaunchKernelGGL((gate_mean_kernel<T>), dim3((a.H / 4 + 63) / 64, a.B), dim3(256), 0, st, a);
-  hipLaunchKernelGGL((gate_fwd_kernel<T>), dim3((a.B * a.S + 3) / 4), dim3(256), 0, st, a);
+  const dim3 grid((a.B * a.S + 3) / 4);
+  switch (a.nsrc) {
+    case 3: hipLaunchKernelGGL((gate_fwd_kernel<T, 3>), grid, dim3(256), 0, st, a); break;
+    case 2: hipLaunchKernelGGL((gate_fwd_kernel<T, 2>), grid, dim3(256), 0, st, a); break;
+    default: hipLaunchKernelGGL((gate_fwd_kernel<T, 1>), grid, dim3(256), 0, st, a); break;
+  }
   return RL_LAUNCH_CHECK();
 }
 template int gate_fwd<bf16_t>(hipStream_t, const GateArgs<bf16_t>&);
 template int gate_fwd<float>(hipStream_t, const GateArgs<float>&);
 
-// backward, step 1 (per token): dz_k and the direct parts of dbert/dpho/dres
-template <typename T>
+// backward, step 1 (per token): dz_k and the direct parts of the source gradients
+template <typename T, int NSRC>
 __global__ void __launch_bounds__(256) gate_bwd_token_kernel(GateArgs<T> a) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + wave;
   if (row >= a.B * a.S) return;
   const int H = a.H;
+  T* dst[NSRC];
+  gate_grads<T, NSRC>(a, dst);
   if (a.row_live != nullptr && a.row_live[row] == 0) {      // padding row: d fused is an exact zero, so is everything derived from it
     if (lane == 0) *(floatx4*)(a.dz + (int64_t)row * 4) = floatx4{0.f, 0.f, 0.f, 0.f};
     const floatx4 z4 = floatx4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
     for (int i = 0; i < LN_MAXV; ++i) {
       const int c = (i * 64 + lane) * 4;
-      if (c < H) { store4<T>(a.dbert + (int64_t)row * H + c, z4); store4<T>(a.dpho + (int64_t)row * H + c, z4); store4<T>(a.dres + (int64_t)row * H + c, z4); }
+      if (c < H) {
+#pragma unroll
+        for (int d = 0; d < NSRC; ++d) store4<T>(dst[d] + (int64_t)row * H + c, z4);
+      }
     }
     return;
   }
+  const T* src[NSRC];
+  gate_sources<T, NSRC>(a, src);
   floatx4 df[LN_MAXV];
-  float dg[3] = {0.f, 0.f, 0.f};
+  float dg[NSRC];
+#pragma unroll
+  for (int d = 0; d < NSRC; ++d) dg[d] = 0.f;
 #pragma unroll
   for (int i = 0; i < LN_MAXV; ++i) {
     const int c = (i * 64 + lane) * 4;
     if (c < H) {
       df[i] = load4<T>(a.dfused + (int64_t)row * H + c);
-      const floatx4 xb = load4<T>(a.bert + (int64_t)row * H + c), xp = load4<T>(a.pho + (int64_t)row * H + c),
-                    xr = load4<T>(a.res + (int64_t)row * H + c);
+      floatx4 x[NSRC];
 #pragma unroll
-      for (int j = 0; j < 4; ++j) { dg[0] += df[i][j] * xb[j]; dg[1] += df[i][j] * xp[j]; dg[2] += df[i][j] * xr[j]; }
+      for (int d = 0; d < NSRC; ++d) x[d] = load4<T>(src[d] + (int64_t)row * H + c);
+#pragma unroll
+      for (int j = 0; j < 4; ++j)
+#pragma unroll
+        for (int d = 0; d < NSRC; ++d) dg[d] += df[i][j] * x[d][j];
     }
   }
-  float gk[3], dz[3];
+  float gk[NSRC], dz[NSRC];
 #pragma unroll
-  for (int k = 0; k < 3; ++k) {
+  for (int k = 0; k < NSRC; ++k) {
     gk[k] = a.g[row * 4 + k];
     dz[k] = wave_sum(dg[k]) * gk[k] * (1.0f - gk[k]);
   }
-  if (lane == 0) { a.dz[row * 4 + 0] = dz[0]; a.dz[row * 4 + 1] = dz[1]; a.dz[row * 4 + 2] = dz[2]; a.dz[row * 4 + 3] = 0.f; }
+  if (lane == 0) {
+#pragma unroll
+    for (int k = 0; k < 4; ++k) a.dz[row * 4 + k] = k < NSRC ? dz[k < NSRC ? k : 0] : 0.f;
+  }
 #pragma unroll
   for (int i = 0; i < LN_MAXV; ++i) {
     const int c = (i * 64 + lane) * 4;
     if (c < H) {
-      floatx4 ob = df[i] * gk[0], op = df[i] * gk[1], orr = df[i] * gk[2];
+      floatx4 o[NSRC];
 #pragma unroll
-      for (int k = 0; k < 3; ++k) {
-        const float* w = a.W + (int64_t)k * 4 * H + c;
-        ob += *(const floatx4*)w * dz[k];
-        op += *(const floatx4*)(w + H) * dz[k];
-        orr += *(const floatx4*)(w + 2 * H) * dz[k];
+      for (int d = 0; d < NSRC; ++d) o[d] = df[i] * gk[d];
+#pragma unroll
+      for (int k = 0; k < NSRC; ++k) {
+        const float* w = a.W + (int64_t)k * (NSRC + 1) * H + c;
+#pragma unroll
+        for (int d = 0; d < NSRC; ++d) o[d] += *(const floatx4*)(w + d * H) * dz[k];
       }
-      store4<T>(a.dbert + (int64_t)row * H + c, ob);
-      store4<T>(a.dpho + (int64_t)row * H + c, op);
-      store4<T>(a.dres + (int64_t)row * H + c, orr);
+#pragma unroll
+      for (int d = 0; d < NSRC; ++d) store4<T>(dst[d] + (int64_t)row * H + c, o[d]);
     }
   }
 }
-// step 2 (per sentence): d(mean) -> spread over the masked tokens of dbert, and dW[:, 3H:4H] += sum_s dz * mean.
+// step 2 (per sentence): d(mean) -> spread over the masked tokens of dbert, and dW[:, NSRC H:(NSRC + 1) H] += sum_s dz * mean.
 // grid (H / 256, B), 256 threads = 64 column quads x 4 row lanes (the row walk over S is split four ways).
-template <typename T>
+template <typename T, int NSRC>
 __global__ void __launch_bounds__(256) gate_bwd_mean_kernel(GateArgs<T> a) {
   __shared__ float zpart[4][4];
   const int q = threadIdx.x & 63, rl = threadIdx.x >> 6;
   const int c = (blockIdx.x * 64 + q) * 4;
   const int b = blockIdx.y;
   const int H = a.H;
-  if (q < 3) {                                   // lane q of row lane rl: partial sum of dz_q over its rows
+  constexpr int WP = NSRC + 1;                   // W row pitch in units of H
+  if (q < NSRC) {                                // lane q of row lane rl: partial sum of dz_q over its rows
     float z = 0.f;
     for (int s = rl; s < a.S; s += 4) z += a.dz[((int64_t)b * a.S + s) * 4 + q];
     zpart[rl][q] = z;
   }
   __syncthreads();
-  float zs[3];
+  float zs[NSRC];
 #pragma unroll
-  for (int k = 0; k < 3; ++k) zs[k] = (zpart[0][k] + zpart[1][k]) + (zpart[2][k] + zpart[3][k]);
+  for (int k = 0; k < NSRC; ++k) zs[k] = (zpart[0][k] + zpart[1][k]) + (zpart[2][k] + zpart[3][k]);
   if (c >= H) return;
   floatx4 dm = floatx4{0.f, 0.f, 0.f, 0.f};
 #pragma unroll
-  for (int k = 0; k < 3; ++k) dm += *(const floatx4*)(a.W + (int64_t)k * 4 * H + 3 * H + c) * zs[k];
+  for (int k = 0; k < NSRC; ++k) dm += *(const floatx4*)(a.W + (int64_t)k * WP * H + NSRC * H + c) * zs[k];
   if (rl == 0) {
     const floatx4 mean = *(const floatx4*)(a.mean + (int64_t)b * H + c);
 #pragma unroll
-    for (int k = 0; k < 3; ++k)
+    for (int k = 0; k < NSRC; ++k)
 #pragma unroll
-      for (int j = 0; j < 4; ++j) atomicAdd(a.dW + (int64_t)k * 4 * H + 3 * H + c + j, zs[k] * mean[j]);
+      for (int j = 0; j < 4; ++j) atomicAdd(a.dW + (int64_t)k * WP * H + NSRC * H + c + j, zs[k] * mean[j]);
     if (c == 0)
 #pragma unroll
-      for (int k = 0; k < 3; ++k) atomicAdd(a.dbias + k, zs[k]);
+      for (int k = 0; k < NSRC; ++k) atomicAdd(a.dbias + k, zs[k]);
   }
   dm = dm / a.msum[b];
   for (int s = rl; s < a.S; s += 4) {
@@ -1767,36 +1825,43 @@ __global__ void __launch_bounds__(256) gate_bwd_mean_kernel(GateArgs<T> a) {
     }
   }
 }
-// step 3: dW[k, src H + c] += sum_t dz_k[t] * X_src(t, c) for the three sources and the three gates in ONE pass over bert / pho / res
+// step 3: dW[k, src H + c] += sum_t dz_k[t] * X_src(t, c) for every source and gate in ONE pass over the sources
 // (was nine column reductions, each re-reading one source: 190 us of launches at the join of the three branches).
-// grid (H / 128, row chunks), 256 threads = 32 column quads x 8 row lanes; nine float4 accumulators per thread; atomics at the end.
-template <typename T>
+// grid (H / 128, row chunks), 256 threads = 32 column quads x 8 row lanes; NSRC x NSRC float4 accumulators per thread; atomics at the end.
+template <typename T, int NSRC>
 __global__ void __launch_bounds__(256) gate_dw_kernel(GateArgs<T> a, int rows_per_block) {
   __shared__ floatx4 red[8][32];
   const int cx = threadIdx.x & 31, ry = threadIdx.x >> 5;
   const int c = (blockIdx.x * 32 + cx) * 4;
   const int H = a.H, T_ = a.B * a.S;
   const int r0 = blockIdx.y * rows_per_block, r1 = min(T_, r0 + rows_per_block);
-  floatx4 acc[3][3];
+  const T* src[NSRC];
+  gate_sources<T, NSRC>(a, src);
+  floatx4 acc[NSRC][NSRC];
 #pragma unroll
-  for (int s = 0; s < 3; ++s)
+  for (int s = 0; s < NSRC; ++s)
 #pragma unroll
-    for (int k = 0; k < 3; ++k) acc[s][k] = floatx4{0.f, 0.f, 0.f, 0.f};
+    for (int k = 0; k < NSRC; ++k) acc[s][k] = floatx4{0.f, 0.f, 0.f, 0.f};
   if (c < H) {
     for (int r = r0 + ry; r < r1; r += 8) {
       const floatx4 dz = *(const floatx4*)(a.dz + (int64_t)r * 4);
-      if (dz[0] == 0.f && dz[1] == 0.f && dz[2] == 0.f) continue;      // padding rows (and any other all-zero row): nothing to add, nothing read
-      const floatx4 x[3] = {load4<T>(a.bert + (int64_t)r * H + c), load4<T>(a.pho + (int64_t)r * H + c), load4<T>(a.res + (int64_t)r * H + c)};
+      bool zero = true;
 #pragma unroll
-      for (int s = 0; s < 3; ++s)
+      for (int k = 0; k < NSRC; ++k) zero = zero && dz[k] == 0.f;
+      if (zero) continue;      // padding rows (and any other all-zero row): nothing to add, nothing read
+      floatx4 x[NSRC];
 #pragma unroll
-        for (int k = 0; k < 3; ++k) acc[s][k] += x[s] * dz[k];
+      for (int s = 0; s < NSRC; ++s) x[s] = load4<T>(src[s] + (int64_t)r * H + c);
+#pragma unroll
+      for (int s = 0; s < NSRC; ++s)
+#pragma unroll
+        for (int k = 0; k < NSRC; ++k) acc[s][k] += x[s] * dz[k];
     }
   }
 #pragma unroll
-  for (int s = 0; s < 3; ++s)
+  for (int s = 0; s < NSRC; ++s)
 #pragma unroll
-    for (int k = 0; k < 3; ++k) {
+    for (int k = 0; k < NSRC; ++k) {
       __syncthreads();
       red[ry][cx] = acc[s][k];
       __syncthreads();
@@ -1804,27 +1869,80 @@ __global__ void __launch_bounds__(256) gate_dw_kernel(GateArgs<T> a, int rows_pe
         floatx4 v = red[0][cx];
 #pragma unroll
         for (int j = 1; j < 8; ++j) v += red[j][cx];
-        float* o = a.dW + (int64_t)k * 4 * H + (int64_t)s * H + c;
+        float* o = a.dW + (int64_t)k * (NSRC + 1) * H + (int64_t)s * H + c;
 #pragma unroll
         for (int j = 0; j < 4; ++j) atomicAdd(o + j, v[j]);
       }
     }
 }
-template <typename T> int gate_bwd(hipStream_t st, const GateArgs<T>& a) {
-  if ((a.H & 3) || a.H > LN_MAXV * 256) return RL_ERR_ARG;
+template <typename T, int NSRC> static void gate_bwd_launch(hipStream_t st, const GateArgs<T>& a) {
   const int T_ = a.B * a.S;
-  hipLaunchKernelGGL((gate_bwd_token_kernel<T>), dim3((T_ + 3) / 4), dim3(256), 0, st, a);
-  hipLaunchKernelGGL((gate_bwd_mean_kernel<T>), dim3((a.H / 4 + 63) / 64, a.B), dim3(256), 0, st, a);
+  hipLaunchKernelGGL((gate_bwd_token_kernel<T, NSRC>), dim3((T_ + 3) / 4), dim3(256), 0, st, a);
+  hipLaunchKernelGGL((gate_bwd_mean_kernel<T, NSRC>), dim3((a.H / 4 + 63) / 64, a.B), dim3(256), 0, st, a);
   const int gx = (a.H + 127) / 128;
   int gy = 1024 / gx;
   if (gy > (T_ + 31) / 32) gy = (T_ + 31) / 32;
   if (gy < 1) gy = 1;
   const int rows_per_block = (T_ + gy - 1) / gy;
-  hipLaunchKernelGGL((gate_dw_kernel<T>), dim3(gx, gy), dim3(256), 0, st, a, rows_per_block);
+  hipLaunchKernelGGL((gate_dw_kernel<T, NSRC>), dim3(gx, gy), dim3(256), 0, st, a, rows_per_block);
+}
+template <typename T> int gate_bwd(hipStream_t st, const GateArgs<T>& a) {
+  if (!gate_args_ok(a)) return RL_ERR_ARG;
+  if (a.nsrc == 2 && (a.pho != nullptr ? a.dpho : a.dres) == nullptr) return RL_ERR_ARG;
+  switch (a.nsrc) {
+    case 3: gate_bwd_launch<T, 3>(st, a); break;
+    case 2: gate_bwd_launch<T, 2>(st, a); break;
+    default: gate_bwd_launch<T, 1>(st, a); break;
+  }
   return RL_LAUNCH_CHECK();
 }
 template int gate_bwd<bf16_t>(hipStream_t, const GateArgs<bf16_t>&);
 template int gate_bwd<float>(hipStream_t, const GateArgs<float>&);
+
+// ---------------------------------------------------------------------------------------------
+// Sum fusion (src/models_abla.py:278-279): hiddens = bert + pho + res, evaluated left to right in fp32 as torch does.
+// ---------------------------------------------------------------------------------------------
+template <typename T>
+__global__ void __launch_bounds__(256) sum_fuse_fwd_kernel(const T* bert, const T* pho, const T* res, T* fused, int rows, int H) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;      // one wave per token row
+  const int row = blockIdx.x * 4 + wave;
+  if (row >= rows) return;
+  for (int c = lane * 4; c < H; c += 256) {
+    const int64_t o = (int64_t)row * H + c;
+    store4<T>(fused + o, (load4<T>(bert + o) + load4<T>(pho + o)) + load4<T>(res + o));
+  }
+}
+// The backward hands the same d fused to every branch.  Not aliased: the bert and pinyin stacks' backwards overwrite their incoming
+// gradient buffer in place (layers_backward: d output in, d input out) and run concurrently, so each branch gets its own copy.
+// row_live (nullable): a padding row (0) gets exact zeros without its d fused row being read, as the gate backward does.
+template <typename T>
+__global__ void __launch_bounds__(256) sum_fuse_bwd_kernel(const T* dfused, T* dbert, T* dpho, T* dres, int rows, int H, const uint8_t* row_live) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + wave;
+  if (row >= rows) return;
+  const bool live = row_live == nullptr || row_live[row] != 0;
+  for (int c = lane * 4; c < H; c += 256) {
+    const int64_t o = (int64_t)row * H + c;
+    const floatx4 d = live ? load4<T>(dfused + o) : floatx4{0.f, 0.f, 0.f, 0.f};
+    store4<T>(dbert + o, d);
+    store4<T>(dpho + o, d);
+    store4<T>(dres + o, d);
+  }
+}
+template <typename T> int sum_fuse_fwd(hipStream_t st, const T* bert, const T* pho, const T* res, T* fused, int rows, int H) {
+  if (!bert || !pho || !res || !fused || rows < 1 || H < 4 || (H & 3)) return RL_ERR_ARG;
+  hipLaunchKernelGGL((sum_fuse_fwd_kernel<T>), dim3((rows + 3) / 4), dim3(256), 0, st, bert, pho, res, fused, rows, H);
+  return RL_LAUNCH_CHECK();
+}
+template <typename T> int sum_fuse_bwd(hipStream_t st, const T* dfused, T* dbert, T* dpho, T* dres, int rows, int H, const uint8_t* row_live) {
+  if (!dfused || !dbert || !dpho || !dres || rows < 1 || H < 4 || (H & 3)) return RL_ERR_ARG;
+  hipLaunchKernelGGL((sum_fuse_bwd_kernel<T>), dim3((rows + 3) / 4), dim3(256), 0, st, dfused, dbert, dpho, dres, rows, H, row_live);
+  return RL_LAUNCH_CHECK();
+}
+template int sum_fuse_fwd<bf16_t>(hipStream_t, const bf16_t*, const bf16_t*, const bf16_t*, bf16_t*, int, int);
+template int sum_fuse_fwd<float>(hipStream_t, const float*, const float*, const float*, float*, int, int);
+template int sum_fuse_bwd<bf16_t>(hipStream_t, const bf16_t*, bf16_t*, bf16_t*, bf16_t*, int, int, const uint8_t*);
+template int sum_fuse_bwd<float>(hipStream_t, const float*, float*, float*, float*, int, int, const uint8_t*);
 
 // ---------------------------------------------------------------------------------------------
 // Glyph dedup: distinct token ids of the batch in order of first occurrence (deterministic).

@@ -112,41 +112,52 @@ def tensor_specs(cfg, model_type="arch3"):
         specs.append((prefix + "pooler.dense.weight", (H, H), "normal"))
         specs.append((prefix + "pooler.dense.bias", (H,), "zeros"))
 
-    if model_type == "arch3":
+    if model_type not in ("bert", "arch3", "arch3-abla"):
+        raise ValueError("model_type must be 'bert', 'arch3' or 'arch3-abla'")
+    # arch3-abla (src/models_abla.py:33-96): the switches drop whole branches; (yes, yes, gate) is arch3 key for key
+    arch = model_type != "bert"
+    with_pho = not arch or model_type == "arch3" or cfg.get("with_pho", "yes") == "yes"
+    with_res = not arch or model_type == "arch3" or cfg.get("with_res", "yes") == "yes"
+    gate = model_type == "arch3" or cfg.get("fusion", "gate") == "gate"
+    G = 1 + int(with_pho) + int(with_res)
+    if arch and with_res:
         F_ = cfg["num_fonts"]
         if F_ == 1:      # models.py:674-676: the single-font model keeps the table as an nn.Embedding [V, 1024]
             specs.append(("char_images.weight", (V, cfg["glyph_size"] * cfg["glyph_size"]), "glyph"))
         else:
             specs.append(("char_images_multifonts", (V, F_, cfg["glyph_size"], cfg["glyph_size"]), "glyph"))
     bert("bert.", cfg["num_hidden_layers"])
-    if model_type == "arch3":
-        specs.append(("pho_embeddings.weight", (cfg["pho_vocab_size"], H), "normal"))
-        specs.append(("pho_gru.weight_ih_l0", (3 * H, H), "gru"))
-        specs.append(("pho_gru.weight_hh_l0", (3 * H, H), "gru"))
-        specs.append(("pho_gru.bias_ih_l0", (3 * H,), "gru"))
-        specs.append(("pho_gru.bias_hh_l0", (3 * H,), "gru"))
-        bert("pho_model.", cfg["pho_layers"])
-        chans = [cfg["num_fonts"], 64, 128, 256, 512, 768]
-        for b in range(1, 6):
-            ci, co = chans[b - 1], chans[b]
-            p = "resnet.res_block%d." % b
+    if arch:
+        if with_pho:
+            specs.append(("pho_embeddings.weight", (cfg["pho_vocab_size"], H), "normal"))
+            specs.append(("pho_gru.weight_ih_l0", (3 * H, H), "gru"))
+            specs.append(("pho_gru.weight_hh_l0", (3 * H, H), "gru"))
+            specs.append(("pho_gru.bias_ih_l0", (3 * H,), "gru"))
+            specs.append(("pho_gru.bias_hh_l0", (3 * H,), "gru"))
+            bert("pho_model.", cfg["pho_layers"])
+        if with_res:
+            chans = [cfg["num_fonts"], 64, 128, 256, 512, 768]
+            for b in range(1, 6):
+                ci, co = chans[b - 1], chans[b]
+                p = "resnet.res_block%d." % b
 
-            def bn(q):
-                specs.append((q + "weight", (co,), "ones"))
-                specs.append((q + "bias", (co,), "zeros"))
-                specs.append((q + "running_mean", (co,), "zeros"))
-                specs.append((q + "running_var", (co,), "bn_var"))
-                specs.append((q + "num_batches_tracked", (), "count"))
-            specs.append((p + "residual_function.0.weight", (co, ci, 3, 3), "conv"))
-            bn(p + "residual_function.1.")
-            specs.append((p + "residual_function.3.weight", (co, co, 3, 3), "conv"))
-            bn(p + "residual_function.4.")
-            specs.append((p + "shortcut.0.weight", (co, ci, 1, 1), "conv"))
-            bn(p + "shortcut.1.")
-        specs.append(("resnet_layernorm.weight", (H,), "ones"))
-        specs.append(("resnet_layernorm.bias", (H,), "zeros"))
-        specs.append(("gate_net.weight", (3, 4 * H), "normal"))
-        specs.append(("gate_net.bias", (3,), "zeros"))
+                def bn(q):
+                    specs.append((q + "weight", (co,), "ones"))
+                    specs.append((q + "bias", (co,), "zeros"))
+                    specs.append((q + "running_mean", (co,), "zeros"))
+                    specs.append((q + "running_var", (co,), "bn_var"))
+                    specs.append((q + "num_batches_tracked", (), "count"))
+                specs.append((p + "residual_function.0.weight", (co, ci, 3, 3), "conv"))
+                bn(p + "residual_function.1.")
+                specs.append((p + "residual_function.3.weight", (co, co, 3, 3), "conv"))
+                bn(p + "residual_function.4.")
+                specs.append((p + "shortcut.0.weight", (co, ci, 1, 1), "conv"))
+                bn(p + "shortcut.1.")
+            specs.append(("resnet_layernorm.weight", (H,), "ones"))
+            specs.append(("resnet_layernorm.bias", (H,), "zeros"))
+        if gate:
+            specs.append(("gate_net.weight", (G, (G + 1) * H), "normal"))
+            specs.append(("gate_net.bias", (G,), "zeros"))
         bert("output_block.", cfg["out_layers"])
     specs.append(("classifier.weight", (V, H), "normal"))
     specs.append(("classifier.bias", (V,), "zeros"))

@@ -187,6 +187,12 @@ class RealiseModule(nn.Module):
     def device(self):
         return self._arenas[0].device
 
+    def _has_pinyin_branch(self):
+        return self.model_type == "arch3"
+
+    def _has_glyph_branch(self):
+        return self.model_type == "arch3"
+
     # ------------------------------------------------------------------ reference-facing API
     def init_weights(self, seed=0, scheme="reference"):
         """transformers/modeling_bert.py:496-506 + PyTorch defaults, from a torch-independent generator."""
@@ -500,9 +506,10 @@ class RealiseModule(nn.Module):
         cb.src_idx, cb.masks = src.data_ptr(), masks.data_ptr()
         cb.tgt_idx = tgt.data_ptr() if tgt is not None else None
         cb.loss_masks = loss_masks.data_ptr() if loss_masks is not None else None
-        if self.model_type == "arch3" and "pho_idx" not in batch and getattr(self, "_pho_table", None) is not None:
+        with_pho = self._has_pinyin_branch()
+        if with_pho and "pho_idx" not in batch and getattr(self, "_pho_table", None) is not None:
             batch = self.build_batch_device(batch)
-        if self.model_type == "arch3" and "_pho_device" in batch:
+        if with_pho and "_pho_device" in batch:
             pho_idx = batch["pho_idx"]
             perm_d, lens_d, alive_d = batch["_pho_device"]
             if pho_idx.shape[0] != B * S:
@@ -512,7 +519,7 @@ class RealiseModule(nn.Module):
             cb.pho_idx, cb.pho_perm, cb.pho_lens_sorted = pho_idx.data_ptr(), perm_d.data_ptr(), lens_d.data_ptr()
             cb.n_alive = None
             cb.n_alive_dev = alive_d.data_ptr()
-        elif self.model_type == "arch3":
+        elif with_pho:
             pho_idx = self._dev(batch["pho_idx"])
             lens = np.asarray(batch["pho_lens"], dtype=np.int32)         # stays a HOST list in the reference (run.py:189)
             if pho_idx.shape[0] != B * S or lens.shape[0] != B * S:
@@ -576,8 +583,8 @@ class RealiseModule(nn.Module):
     def glyph_forward(self, src_idx, training=None):
         """BASELINE configs[3]: the glyph ResNet alone - ``resnet(char_images_multifonts[src_idx])`` (src/models.py:829-836,
         src/char_cnn.py:46-55) -> [B, S, 768] in the compute dtype, before ``resnet_layernorm``."""
-        if self.model_type != "arch3":
-            raise RuntimeError("glyph_forward needs the full model")
+        if not self._has_glyph_branch():
+            raise RuntimeError("glyph_forward needs a model with the glyph branch")
         src = self._dev(src_idx)
         B, S = src.shape
         self._ensure_engine(B, S, -1)
