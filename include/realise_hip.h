@@ -170,6 +170,19 @@ int realise_embedding_bwd(void* stream, int dtype, const void* de, const int64_t
 int realise_glyph_unique(void* stream, const int64_t* ids, int T, int V, int32_t* first_scratch, int32_t* flag_scratch, int64_t* uniq_ids, float* counts,
                          int32_t* inv, int32_t* bounds, int nhw, const int32_t* hw);
 int realise_segment_sum(void* stream, int dtype, const void* x, const int32_t* inv, int T, int C, float* acc, void* out, const int32_t* nuniq_dev);
+/* The flatten at the top of CharResNet1 (char_cnn.py:74 `h = h.view(h.shape[0], -1)` of an NCHW [N, C, 2, 2] tensor): the tower keeps its
+ * maps NHWC, so a row of its top is [p][c] (p = 2y + x, C = H / 4 channels) while the reference's feature index is f = c * 4 + p.  The
+ * three operators at that boundary permute inside registers; H % 16 == 0, H <= 1024.
+ *   realise_layernorm_fwd_chw4 - resnet_layernorm (models.py:838) of the flattened rows: x holds storage-order rows, row r reads row
+ *     row_index[r] of it (nullable: row r); gamma / beta and the outputs y / xhat (nullable) are in feature order, so the backward is
+ *     realise_layernorm_bwd.
+ *   realise_gather_rows_chw4 - the flatten itself with the per-token gather: out[t][c * 4 + p] = x[inv[t]][p * C + c].
+ *   realise_segment_sum_chw4 - its gradient summed over the tokens of a glyph: x [T][H] in feature order,
+ *     out[u][p * C + c] = sum over inv[t] == u of x[t][c * 4 + p] (acc: T*H floats of scratch; rows >= *nuniq_dev untouched). */
+int realise_layernorm_fwd_chw4(void* stream, int dtype, const void* x, const int32_t* row_index, const float* gamma, const float* beta, float eps,
+                               void* y, void* xhat, float* rstd, int rows, int H);
+int realise_gather_rows_chw4(void* stream, int dtype, const void* x, const int32_t* inv, int T, int H, void* out);
+int realise_segment_sum_chw4(void* stream, int dtype, const void* x, const int32_t* inv, int T, int H, float* acc, void* out, const int32_t* nuniq_dev);
 
 /* Eval decode: ids[row] = argmax over the V logits of the row, first maximum wins - replaces
  * `logits.detach().cpu().numpy()` + `np.argmax(preds, axis=-1)` (src/run.py:262-263): only the ids cross PCIe. */
@@ -190,6 +203,12 @@ typedef struct {
   /* model_type 2 only (ignored otherwise; run.py:373-375): 1 = the pinyin branch / the glyph branch is present; fusion 0 = gate over
    * the G = 1 + with_pho + with_res sources (gate_net [G, (G+1)H]), 1 = sum (needs both branches) */
   int32_t with_pho, with_res, fusion;
+  /* the glyph encoder (run.py:292,419-421 --image_model_type; models.py:681-686): 0 = CharResNet (char_cnn.py:36-55: five blocks,
+   * num_fonts input channels, a [768, 1, 1] top), exactly what a zero-initialised field gave before it existed; 1 = CharResNet1
+   * (char_cnn.py:57-75: four blocks 64-128-192-192, ONE input channel, a [192, 2, 2] top flattened channel-major to 768).  Read where
+   * the configuration has a glyph branch: type 1 there needs num_fonts == 1 (the reference builds CharResNet1 with in_channels = 1
+   * and dies at its first forward otherwise), hidden == 768 and glyph_size == 32.  Any other value is refused. */
+  int32_t image_model_type;
 } realise_config;
 
 /* Parameter layout: the library is the source of truth for where each state_dict tensor of the

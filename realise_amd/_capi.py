@@ -55,7 +55,8 @@ class Config(C.Structure):
                                          "type_vocab", "bert_layers", "pho_layers", "out_layers", "num_fonts",
                                          "glyph_size", "pho_vocab")] + \
                [("hidden_dropout", C.c_float), ("attn_dropout", C.c_float), ("ln_eps", C.c_float),
-                ("tie_classifier", C.c_int32), ("with_pho", C.c_int32), ("with_res", C.c_int32), ("fusion", C.c_int32)]
+                ("tie_classifier", C.c_int32), ("with_pho", C.c_int32), ("with_res", C.c_int32), ("fusion", C.c_int32),
+                ("image_model_type", C.c_int32)]
 
 
 class Batch(C.Structure):
@@ -118,6 +119,9 @@ SYMBOLS = {
     "realise_embedding_bwd": (_I, [_P, _I, _P, _P, _I, _I, _I, _P, _P, _I, _P]),
     "realise_glyph_unique": (_I, [_P, _P, _I, _I, _P, _P, _P, _P, _P, _P, _I, _P]),
     "realise_segment_sum": (_I, [_P, _I, _P, _P, _I, _I, _P, _P, _P]),
+    "realise_layernorm_fwd_chw4": (_I, [_P, _I, _P, _P, _P, _P, _F, _P, _P, _P, _I, _I]),
+    "realise_gather_rows_chw4": (_I, [_P, _I, _P, _P, _I, _I, _P]),
+    "realise_segment_sum_chw4": (_I, [_P, _I, _P, _P, _I, _I, _P, _P, _P]),
     "realise_argmax": (_I, [_P, _I, _P, _L, _I, _I, _P]),
     "realise_build_pho": (_I, [_P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P]),
     "realise_layout_count": (_I, [C.POINTER(Config)]),
@@ -220,6 +224,8 @@ def make_config(cfg, model_type, dtype, tie=True):
     c.with_pho = 1 if cfg.get("with_pho", "yes") == "yes" else 0
     c.with_res = 1 if cfg.get("with_res", "yes") == "yes" else 0
     c.fusion = 1 if cfg.get("fusion", "gate") == "sum" else 0
+    # the glyph encoder (run.py:419-421): 0 = CharResNet, 1 = CharResNet1; read where the model has a glyph branch
+    c.image_model_type = int(cfg.get("image_model_type", 0))
     return c
 
 

@@ -52,15 +52,31 @@ class RealiseConfig(dict):
     def __setattr__(self, k, v):
         self[k] = v
 
-    def validate(self):
+    def validate(self, glyph_branch=True):
+        """``glyph_branch``: the model being built has a glyph tower (a module passes what it knows; a bare config assumes one)."""
         if self["hidden_size"] % self["num_attention_heads"] != 0:
             raise ValueError("hidden size must be a multiple of the head count (modeling_bert.py:199-202)")
         if self["hidden_size"] // self["num_attention_heads"] != 64:
             raise ValueError("the HIP attention kernels are built for head_dim 64")
         if self["hidden_act"] != "gelu":
             raise ValueError("only the erf GELU of the reference path is implemented")
-        if self["image_model_type"] != 0:
+        # models.py:681-686: 0 = CharResNet, 1 = CharResNet1, anything else raises with this text
+        if self["image_model_type"] not in (0, 1):
             raise NotImplementedError("invalid image_model_type %d" % self["image_model_type"])
+        # CharResNet1() is built with its default in_channels=1 whatever num_fonts is (models.py:684) and flattens a [192, 2, 2] map
+        # to 768 features (char_cnn.py:74).  The reference builds the model with several fonts or another hidden size and dies at its
+        # first forward ("expected input ... to have 1 channels", a shape mismatch in resnet_layernorm); here it is refused at
+        # construction.  A model without the glyph branch carries the field and ignores it, as the reference does.
+        if self["image_model_type"] == 1 and glyph_branch:
+            if self["num_fonts"] != 1:
+                raise ValueError("image_model_type=1 (CharResNet1) takes one input channel: it needs num_fonts=1, got %d"
+                                 % self["num_fonts"])
+            if self["hidden_size"] != 768:
+                raise ValueError("image_model_type=1 (CharResNet1) flattens a 192x2x2 map to 768 features: it needs "
+                                 "hidden_size=768, got %d" % self["hidden_size"])
+            if self["glyph_size"] != 32:
+                raise ValueError("image_model_type=1 (CharResNet1) ends on a 2x2 map of a 32x32 glyph: it needs glyph_size=32, "
+                                 "got %d" % self["glyph_size"])
         for k in ("with_pho", "with_res"):
             if self.get(k, "yes") not in ("yes", "no"):
                 raise ValueError("%s must be 'yes' or 'no' (run.py:373-374), got %r" % (k, self[k]))

@@ -70,6 +70,13 @@ static int tn_grouped(hipStream_t st, int n, const realise_tn_problem* pr, int P
   return gemm_tn_group<T>(st, n, g, P, 1.0f, overwrite, live, n_live, list_rows);
 }
 
+template <typename T>
+static int ln_fwd_chw4_call(hipStream_t st, const void* x, const int32_t* row_index, const float* gamma, const float* beta, float eps, void* y,
+                            void* xhat, float* rstd, int rows, int H) {
+  LnFwdArgs<T> a; a.rows = rows; a.H = H; a.x = (const T*)x; a.row_index = (const int*)row_index; a.gamma = gamma; a.beta = beta; a.eps = eps;
+  a.y = (T*)y; a.xhat = (T*)xhat; a.rstd = rstd;
+  return ln_fwd_chw4<T>(st, a);
+}
 extern "C" {
 
 const char* realise_version(void) { return "realise_hip 0.3 (gfx950)"; }
@@ -415,12 +422,31 @@ int realise_segment_sum(void* stream, int dtype, const void* x, const int32_t* i
   RL_BY_DTYPE(segment_sum<bf16_t>(st, (const bf16_t*)x, (const int*)inv, T, C, acc, (bf16_t*)out, (const int*)nuniq_dev),
               segment_sum<float>(st, (const float*)x, (const int*)inv, T, C, acc, (float*)out, (const int*)nuniq_dev));
 }
+int realise_layernorm_fwd_chw4(void* stream, int dtype, const void* x, const int32_t* row_index, const float* gamma, const float* beta, float eps,
+                               void* y, void* xhat, float* rstd, int rows, int H) {
+  if (!x || !gamma || !beta || !y) return RL_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  RL_BY_DTYPE(ln_fwd_chw4_call<bf16_t>(st, x, row_index, gamma, beta, eps, y, xhat, rstd, rows, H),
+              ln_fwd_chw4_call<float>(st, x, row_index, gamma, beta, eps, y, xhat, rstd, rows, H));
+}
+int realise_gather_rows_chw4(void* stream, int dtype, const void* x, const int32_t* inv, int T, int H, void* out) {
+  if (!x || !inv || !out) return RL_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  RL_BY_DTYPE(gather_rows_chw4<bf16_t>(st, (const bf16_t*)x, (const int*)inv, T, H, (bf16_t*)out),
+              gather_rows_chw4<float>(st, (const float*)x, (const int*)inv, T, H, (float*)out));
+}
+int realise_segment_sum_chw4(void* stream, int dtype, const void* x, const int32_t* inv, int T, int H, float* acc, void* out, const int32_t* nuniq_dev) {
+  if (!x || !inv || !acc || !out || !nuniq_dev) return RL_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  RL_BY_DTYPE(segment_sum_chw4<bf16_t>(st, (const bf16_t*)x, (const int*)inv, T, H, acc, (bf16_t*)out, (const int*)nuniq_dev),
+              segment_sum_chw4<float>(st, (const float*)x, (const int*)inv, T, H, acc, (float*)out, (const int*)nuniq_dev));
+}
 
 // ---- layout --------------------------------------------------------------------------------------
-int realise_layout_count(const realise_config* cfg) { return cfg && variant_valid(*cfg) ? (int)build_layout(*cfg).tensors.size() : -1; }
+int realise_layout_count(const realise_config* cfg) { return cfg && config_ok(*cfg) ? (int)build_layout(*cfg).tensors.size() : -1; }
 int realise_layout_entry(const realise_config* cfg, int index, char* name, int name_cap, int32_t* arena, int64_t* offset,
                          int32_t* ndim, int64_t* shape4) {
-  if (!cfg || !variant_valid(*cfg)) return RL_ERR_ARG;
+  if (!cfg || !config_ok(*cfg)) return RL_ERR_ARG;
   const Layout L = build_layout(*cfg);
   if (index < 0 || index >= (int)L.tensors.size()) return RL_ERR_ARG;
   const TensorInfo& t = L.tensors[index];
@@ -431,12 +457,12 @@ int realise_layout_entry(const realise_config* cfg, int index, char* name, int n
   return RL_OK;
 }
 int64_t realise_arena_elems(const realise_config* cfg, int arena) {
-  if (!cfg || !variant_valid(*cfg) || arena < 0 || arena >= AR_COUNT) return -1;
+  if (!cfg || !config_ok(*cfg) || arena < 0 || arena >= AR_COUNT) return -1;
   return build_layout(*cfg).arena_elems[arena];
 }
-int realise_bucket_count(const realise_config* cfg) { return cfg && variant_valid(*cfg) ? (int)build_layout(*cfg).buckets.size() : -1; }
+int realise_bucket_count(const realise_config* cfg) { return cfg && config_ok(*cfg) ? (int)build_layout(*cfg).buckets.size() : -1; }
 int realise_bucket_bounds(const realise_config* cfg, int bucket, int64_t* begin, int64_t* end) {
-  if (!cfg || !variant_valid(*cfg)) return RL_ERR_ARG;
+  if (!cfg || !config_ok(*cfg)) return RL_ERR_ARG;
   const Layout L = build_layout(*cfg);
   if (bucket < 0 || bucket >= (int)L.buckets.size()) return RL_ERR_ARG;
   *begin = L.buckets[bucket].first; *end = L.buckets[bucket].second;

@@ -134,7 +134,7 @@ template <typename T> struct Engine : EngineBase {
   struct LayerSh { int64_t qkv_w, qkv_wT, ao_w, ao_wT, in_w, in_wT, out_w, out_wT; };
   struct BlockSh { int64_t w1f, w1d, w1p, w2f, w2d, wsf, wsd; int cin_pad; };
   std::vector<LayerSh> sh_bert, sh_pho, sh_out;
-  BlockSh sh_blk[5];
+  BlockSh sh_blk[TOWER_MAX_BLOCKS];      // the first L.tower.nblocks are in use
   int64_t sh_cls_w = 0, sh_cls_wT = 0, sh_gru_hh = 0, sh_gru_hhT = 0, sh_glyph = 0;
   int64_t shadow_total = 0;
   bool glyph_built = false, descs_built = false;
@@ -156,7 +156,7 @@ template <typename T> struct Engine : EngineBase {
     int B = 0, S = 0, Tp = 0;
     int64_t total = 0;
     StackAct bert, pho, outb;
-    BlockAct blk[5];
+    BlockAct blk[TOWER_MAX_BLOCKS];
     int64_t mask_add, out_d, dlogits, count, loss_internal;
     int64_t cls_act, cls_inv, cls_nact, cls_xc, cls_gc, cls_slab;
     int64_t live_rows = 0;                // ascending list of the live rows (row-granular layer GEMMs)
@@ -303,7 +303,7 @@ template <typename T> struct Engine : EngineBase {
       sh_gru_hhT = b.take(3LL * H * H * e);
     }
     if (vr.res) {
-      for (int k = 0; k < 5; ++k) {
+      for (int k = 0; k < L.tower.nblocks; ++k) {
         const BlockOff& o = L.blocks[k];
         BlockSh& s = sh_blk[k];
         s.cin_pad = pad8(o.cin);
@@ -390,7 +390,7 @@ template <typename T> struct Engine : EngineBase {
         ConvShadowDesc& x = cd.d[cd.n++];
         x.w = w; x.fwd = fwd; x.dgrad = dgrad; x.Co = Co; x.Ci = Ci; x.KHW = KHW; x.Cpad = Cpad; x.CiRows = Cpad; x.block_begin = 0; x.order = ord;
       };
-      for (int k = 0; k < 5; ++k) {
+      for (int k = 0; k < L.tower.nblocks; ++k) {
         const BlockOff& o = L.blocks[k];
         const BlockSh& s = sh_blk[k];
         addc(pp(o.w1), o.cout, o.cin, 9, s.cin_pad, sp<T>(s.w1f), sp<T>(s.w1d));
@@ -628,7 +628,7 @@ template <typename T> struct Engine : EngineBase {
       }
       if (vr.res) {
       int hin = cfg.glyph_size;
-      for (int k = 0; k < 5; ++k) {
+      for (int k = 0; k < L.tower.nblocks; ++k) {
         BlockAct& a = p.blk[k];
         const int C = L.blocks[k].cout;
         a.Hin = hin; a.Hout = hin / 2; a.Pout = (int)(Tk * a.Hout * a.Hout);
@@ -991,8 +991,8 @@ template <typename T> struct Engine : EngineBase {
     // (order of first occurrence) and BatchNorm weights each glyph by its multiplicity: identical statistics
     // to the reference's dense [B*S, F, 32, 32] pass, a fraction of the work (PAD alone is ~1/3 of the rows).
     {
-      HwList hw; hw.n = 5;
-      for (int k = 0; k < 5; ++k) hw.v[k] = pl.blk[k].Hout * pl.blk[k].Hout;
+      HwList hw; hw.n = L.tower.nblocks;
+      for (int k = 0; k < hw.n; ++k) hw.v[k] = pl.blk[k].Hout * pl.blk[k].Hout;
       RL_TRY(glyph_unique(st, ids, pl.B * pl.S, V, wp<int>(pl.gu_first), wp<int>(pl.gu_flag), wp<int64_t>(pl.gu_ids),
                           wp<float>(pl.gu_counts), wp<int>(pl.gu_inv), wp<int>(pl.gu_bounds), hw));
     }
@@ -1001,7 +1001,7 @@ template <typename T> struct Engine : EngineBase {
     if (!fuse7) RL_TRY(gather_glyphs(st));
     const T* x = fuse7 ? sp<T>(sh_glyph) : wp<T>(pl.gu_dense);
     const int64_t* index = fuse7 ? wp<int64_t>(pl.gu_ids) : nullptr;
-    for (int k = 0; k < 5; ++k) {
+    for (int k = 0; k < L.tower.nblocks; ++k) {
       const BlockOff& o = L.blocks[k];
       const BlockSh& s = sh_blk[k];
       BlockAct& a = pl.blk[k];
@@ -1056,12 +1056,20 @@ template <typename T> struct Engine : EngineBase {
     *out = x;
     return RL_OK;
   }
-  // d_top: gradient w.r.t. block-5 output per DISTINCT glyph [U,768] (already summed over the tokens sharing it)
+  // d(flattened tower output) per token [B*S, 768] -> r_dout: d(top map) per DISTINCT glyph in the tower's NHWC storage order, summed
+  // over the tokens that share the glyph (a 2x2 top undoes the reference's channel-major flatten on the way)
+  int top_segment_sum(hipStream_t st, const T* d_res) {
+    const int Tk = pl.B * pl.S;
+    if (L.tower.top_pixels() == 4)
+      return segment_sum_chw4<T>(st, d_res, wp<int>(pl.gu_inv), Tk, H, wp<float>(pl.seg_acc), wp<T>(pl.r_dout), wp<int>(pl.gu_bounds));
+    return segment_sum<T>(st, d_res, wp<int>(pl.gu_inv), Tk, H, wp<float>(pl.seg_acc), wp<T>(pl.r_dout), wp<int>(pl.gu_bounds));
+  }
+  // d_top: gradient w.r.t. the last block's output per DISTINCT glyph [U, top pixels, top channels] (already summed over the tokens sharing it)
   int resnet_backward(hipStream_t st, const T* d_top) {
     float* sums = wp<float>(pl.bn_sums);
     const T* d_out = d_top;
     if (!glyph_gathered) { RL_TRY(gather_glyphs(st)); glyph_gathered = true; }      // K7: block 1's weight gradients read the gathered images
-    for (int k = 4; k >= 0; --k) {
+    for (int k = L.tower.nblocks - 1; k >= 0; --k) {
       const BlockOff& o = L.blocks[k];
       const BlockSh& s = sh_blk[k];
       BlockAct& a = pl.blk[k];
@@ -1326,7 +1334,9 @@ template <typename T> struct Engine : EngineBase {
         LnFwdArgs<T> ln; ln.rows = Tk; ln.H = H; ln.x = res; ln.row_index = wp<int>(pl.gu_inv);      // token t reads its glyph's row
         ln.gamma = pp(L.res_ln_g); ln.beta = pp(L.res_ln_b); ln.eps = cfg.ln_eps;
         ln.y = wp<T>(pl.res_h); ln.xhat = bwd_follows() ? wp<T>(pl.res_xhat) : nullptr; ln.rstd = wp<float>(pl.res_rstd);
-        RL_TRY(ln_fwd<T>(s_glyph, ln));
+        // a 2x2 top (CharResNet1): the rows arrive [p][c], the LayerNorm stores them in the reference's c * 4 + p feature order
+        if (L.tower.top_pixels() == 4) RL_TRY(ln_fwd_chw4<T>(s_glyph, ln));
+        else RL_TRY(ln_fwd<T>(s_glyph, ln));
       }
       if (ovl && g_fwd_order == 1) { RL_TRY(stack_forward(st, 0, L.bert, sh_bert, pl.bert, last.src_idx, nullptr, 0, &bert_h)); top = bert_h; }
       if (ovl) RL_TRY(join(st));
@@ -1410,7 +1420,8 @@ template <typename T> struct Engine : EngineBase {
     have_fwd = false; have_glyph_fwd = false;
     const T* res = nullptr;
     RL_TRY(resnet_forward(st, last.src_idx, &res));
-    RL_TRY(gather_rows<T>(st, res, wp<int>(pl.gu_inv), B * S, H, (T*)res_out));
+    if (L.tower.top_pixels() == 4) RL_TRY(gather_rows_chw4<T>(st, res, wp<int>(pl.gu_inv), B * S, H, (T*)res_out));
+    else RL_TRY(gather_rows<T>(st, res, wp<int>(pl.gu_inv), B * S, H, (T*)res_out));
     have_glyph_fwd = training != 0;
     return RL_OK;
   }
@@ -1419,8 +1430,7 @@ template <typename T> struct Engine : EngineBase {
     if (!have_glyph_fwd || !d_res) { fprintf(stderr, "[realise_hip] glyph_backward without a training glyph_forward\n"); return RL_ERR_ARG; }
     RL_TRY(sync_optimizer(st));
     RL_TRY(begin_gradient_pass(st, true));
-    const int Tk = pl.B * pl.S;
-    RL_TRY(segment_sum<T>(st, (const T*)d_res, wp<int>(pl.gu_inv), Tk, H, wp<float>(pl.seg_acc), wp<T>(pl.r_dout), wp<int>(pl.gu_bounds)));
+    RL_TRY(top_segment_sum(st, (const T*)d_res));
     RL_TRY(resnet_backward(st, wp<T>(pl.r_dout)));
     return RL_OK;
   }
@@ -1555,7 +1565,7 @@ template <typename T> struct Engine : EngineBase {
     ln.row_live = live_rows();
     ln.gamma = pp(L.res_ln_g); ln.dx = wp<T>(sc.gE); ln.dgamma = gp(L.res_ln_g); ln.dbeta = gp(L.res_ln_b);
     RL_TRY(ln_bwd<T>(st, ln));
-    RL_TRY(segment_sum<T>(st, wp<T>(sc.gE), wp<int>(pl.gu_inv), Tk, H, wp<float>(pl.seg_acc), wp<T>(pl.r_dout), wp<int>(pl.gu_bounds)));
+    RL_TRY(top_segment_sum(st, wp<T>(sc.gE)));
     return resnet_backward(st, wp<T>(pl.r_dout));
   }
   int stage_pho(hipStream_t st) {            // pho_model + GRU
@@ -1657,8 +1667,10 @@ template <typename T> struct Engine : EngineBase {
 
 EngineBase* make_engine(const realise_config& c, float* p, float* g, float* pu, float* fz, float* bf, int64_t* bi) {
   if (c.hidden % 64 || c.hidden / c.heads != 64 || c.hidden > 1024 || (c.intermediate % 8) || (c.vocab % 8)) return nullptr;
-  if (!variant_valid(c)) return nullptr;
-  if (variant_of(c).res && c.hidden != 768) return nullptr;     // CharResNet output is 768 wide (char_cnn.py:44)
+  if (!config_ok(c)) return nullptr;
+  if (variant_of(c).res) {      // the flattened tower output is the hidden state: 768 x 1 x 1 (char_cnn.py:44) or 192 x 2 x 2 (char_cnn.py:74)
+    if (c.hidden != tower_of(c).features()) return nullptr;
+  }
   if (c.dtype == REALISE_BF16) return new Engine<bf16_t>(c, p, g, pu, fz, bf, bi);
   if (c.dtype == REALISE_F32) return new Engine<float>(c, p, g, pu, fz, bf, bi);
   return nullptr;

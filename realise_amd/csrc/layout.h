@@ -1,6 +1,6 @@
 // Parameter layout of the reference's state_dict inside the engine's flat arenas.
 // Names and shapes follow src/models.py:652-698, transformers/modeling_bert.py:155-416 and
-// src/char_cnn.py:9-55 exactly (427 keys for SpellBertPho2ResArch3).
+// src/char_cnn.py:9-75 exactly (427 keys for SpellBertPho2ResArch3).
 #pragma once
 #include <stdint.h>
 #include <string>
@@ -31,6 +31,27 @@ struct StackOff {
 struct BnOff { int64_t g, b; int64_t rmean, rvar; int64_t nbt; };   // g,b: AR_TRAIN; rmean,rvar: AR_BUF_F32; nbt: AR_BUF_I64
 struct BlockOff { int cin, cout; int64_t w1, w2, ws; BnOff bn1, bn2, bns; };
 
+// The glyph tower as data (run.py:292 --image_model_type, models.py:681-686): every block is a BasicBlock with a stride-2 3x3
+// convolution, a stride-1 3x3 convolution and a stride-2 1x1 shortcut, so a tower is its channel list; the map side halves per block.
+//   type 0  CharResNet  (char_cnn.py:36-55): F -> 64 -> 128 -> 256 -> 512 -> 768, 32x32 -> 1x1, output [N, 768]
+//   type 1  CharResNet1 (char_cnn.py:57-75): 1 -> 64 -> 128 -> 192 -> 192,        32x32 -> 2x2, output the NCHW flatten [N, 192 * 4]
+static constexpr int TOWER_MAX_BLOCKS = 5;
+struct Tower {
+  int nblocks = 0;
+  int chans[TOWER_MAX_BLOCKS + 1] = {0, 0, 0, 0, 0, 0};   // chans[0] = input channels, chans[k] = output channels of block k
+  int top_side = 1;                                       // side of the last block's map
+  int top_channels() const { return chans[nblocks]; }
+  int top_pixels() const { return top_side * top_side; }
+  int features() const { return top_channels() * top_pixels(); }       // width of the flattened output (char_cnn.py:54,74)
+};
+inline Tower tower_of(const realise_config& c) {
+  Tower t;
+  if (c.image_model_type == 1) { t.nblocks = 4; const int ch[5] = {1, 64, 128, 192, 192}; for (int i = 0; i < 5; ++i) t.chans[i] = ch[i]; }
+  else { t.nblocks = 5; const int ch[6] = {c.num_fonts, 64, 128, 256, 512, 768}; for (int i = 0; i < 6; ++i) t.chans[i] = ch[i]; }
+  t.top_side = c.glyph_size >> t.nblocks;
+  return t;
+}
+
 struct Layout {
   std::vector<TensorInfo> tensors;
   int64_t arena_elems[AR_COUNT] = {0, 0, 0, 0, 0};
@@ -40,7 +61,8 @@ struct Layout {
   int64_t pho_emb = -1, gru_w_ih = -1, gru_w_hh = -1, gru_b_ih = -1, gru_b_hh = -1;
   int64_t res_ln_g = -1, res_ln_b = -1, gate_w = -1, gate_b = -1;
   int64_t glyph = -1;                                  // AR_FROZEN
-  BlockOff blocks[5];
+  Tower tower;                                         // nblocks == 0 without the glyph branch
+  BlockOff blocks[TOWER_MAX_BLOCKS];
   int bert_groups = 0;                                 // number of buckets the bert layers are split in
 };
 
@@ -72,6 +94,15 @@ inline bool variant_valid(const realise_config& c) {
   if (c.model_type != 2) return true;
   if ((c.with_pho != 0 && c.with_pho != 1) || (c.with_res != 0 && c.with_res != 1) || (c.fusion != 0 && c.fusion != 1)) return false;
   return c.fusion == 0 || (c.with_pho == 1 && c.with_res == 1);
+}
+// variant_valid + the glyph tower: image_model_type 0 / 1 only (models.py:681-686 raises NotImplementedError for anything else).
+// CharResNet1 is built with in_channels = 1 whatever num_fonts is and flattens a [192, 2, 2] map, so with the glyph branch present
+// type 1 needs one font, hidden == 768 and a 32x32 glyph; without the branch the field is carried and ignored, as in the reference.
+inline bool config_ok(const realise_config& c) {
+  if (!variant_valid(c)) return false;
+  if (c.image_model_type != 0 && c.image_model_type != 1) return false;
+  if (c.image_model_type == 1 && variant_of(c).res && (c.num_fonts != 1 || c.hidden != 768 || c.glyph_size != 32)) return false;
+  return true;
 }
 
 inline Layout build_layout(const realise_config& c) {
@@ -155,7 +186,7 @@ inline Layout build_layout(const realise_config& c) {
     add_layers_desc(L.outb, "output_block.", c.out_layers - 1, 0);
     add_emb(L.outb, "output_block.", false);
     close_bucket(begin);
-    // ---- bucket 1: gate [G, (G+1)H] (models_abla.py:86-87), resnet LN, glyph ResNet (blocks 5..1) - never empty: sum fusion has both branches
+    // ---- bucket 1: gate [G, (G+1)H] (models_abla.py:86-87), resnet LN, glyph ResNet (last block first) - never empty: sum fusion has both branches
     if (vr.gate) {
       L.gate_w = add(AR_TRAIN, "gate_net.weight", {vr.nsrc, (vr.nsrc + 1) * H});
       L.gate_b = add(AR_TRAIN, "gate_net.bias", {vr.nsrc});
@@ -163,10 +194,10 @@ inline Layout build_layout(const realise_config& c) {
     if (vr.res) {
       L.res_ln_g = add(AR_TRAIN, "resnet_layernorm.weight", {H});
       L.res_ln_b = add(AR_TRAIN, "resnet_layernorm.bias", {H});
-      const int chans[6] = {c.num_fonts, 64, 128, 256, 512, 768};
-      for (int b = 5; b >= 1; --b) {
+      L.tower = tower_of(c);
+      for (int b = L.tower.nblocks; b >= 1; --b) {
         BlockOff& k = L.blocks[b - 1];
-        k.cin = chans[b - 1]; k.cout = chans[b];
+        k.cin = L.tower.chans[b - 1]; k.cout = L.tower.chans[b];
         const std::string p = "resnet.res_block" + std::to_string(b) + ".";
         k.w2 = add(AR_TRAIN, p + "residual_function.3.weight", {k.cout, k.cout, 3, 3});
         k.bn2 = add_bn(p + "residual_function.4.", k.cout);

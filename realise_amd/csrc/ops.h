@@ -243,6 +243,14 @@ template <typename T> int segment_sum(hipStream_t st, const T* x, const int* inv
 template <typename T> int gather_images(hipStream_t st, const T* table, const int64_t* ids, const int* nuniq, int max_images, int64_t elems, T* dense);
 // out[t][:] = x[inv[t]][:]
 template <typename T> int gather_rows(hipStream_t st, const T* x, const int* inv, int T_, int C, T* out);
+// The NCHW flatten of a 2x2 top map (CharResNet1, char_cnn.py:74): a storage row is [p][c] (NHWC, C = H / 4 channels), feature
+// f = c * 4 + p.  H % 16 == 0, H <= 1024.  The three kernels at that boundary permute inside registers:
+//   ln_fwd_chw4: LayerNorm of storage rows (a.x, read through a.row_index when set), gamma / beta / y / xhat in feature order
+//   gather_rows_chw4: out[t][c * 4 + p] = x[inv[t]][p * C + c]
+//   segment_sum_chw4: x [T][H] in feature order -> out[u][p * C + c] = sum over inv[t] == u of x[t][c * 4 + p]
+template <typename T> int ln_fwd_chw4(hipStream_t st, const LnFwdArgs<T>& a);
+template <typename T> int gather_rows_chw4(hipStream_t st, const T* x, const int* inv, int T_, int H, T* out);
+template <typename T> int segment_sum_chw4(hipStream_t st, const T* x, const int* inv, int T_, int H, float* acc, T* out, const int* nuniq_dev);
 
 // ---- weight shadows (operand copies in the compute dtype) ----------------------------------------
 template <typename T> int cast_copy(hipStream_t st, const float* src, T* dst, int64_t n);

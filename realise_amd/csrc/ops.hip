@@ -2082,6 +2082,120 @@ template int gather_rows<bf16_t>(hipStream_t, const bf16_t*, const int*, int, in
 template int gather_rows<float>(hipStream_t, const float*, const int*, int, int, float*);
 
 // ---------------------------------------------------------------------------------------------
+// The NCHW flatten of a 2x2 top map (CharResNet1, char_cnn.py:74 `h.view(h.shape[0], -1)` of [N, C, 2, 2]): the tower keeps its maps
+// NHWC, a row of the top is [p][c] (p = 2y + x, storage index p * C + c) and its consumers need feature f = c * 4 + p.  The three
+// kernels at that boundary carry the permutation themselves, so no launch exists only to permute: one 64-lane wave per row, lane l
+// owns channels 4l .. 4l + 3 = the 16 consecutive features 16l .. 16l + 15.  It reads its channels as one 4-wide access per pixel
+// (contiguous across the lanes), transposes the 4 x 4 block in registers and touches the feature-ordered side as 16 consecutive
+// elements - both global sides stay contiguous, no strided scatter.  H = 4 C, C % 4 == 0, H <= 1024.
+// ---------------------------------------------------------------------------------------------
+static inline bool chw4_ok(int H) { return H >= 16 && (H & 15) == 0 && H <= 1024; }
+// resnet_layernorm (models.py:838) over rows read in storage order (through row_index: the glyph dedup gather): the statistics do not
+// depend on the order; gamma / beta are applied and y / xhat stored at the feature index, so the backward is the plain ln_bwd
+template <typename T>
+__global__ void __launch_bounds__(256) ln_fwd_chw4_kernel(LnFwdArgs<T> a) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + wave;
+  if (row >= a.rows) return;
+  const int H = a.H, C = H >> 2, c0 = lane * 4;
+  const bool on = c0 < C;
+  const T* src = a.x + (int64_t)(a.row_index ? a.row_index[row] : row) * H;
+  floatx4 q[4];
+  float sum = 0.f;
+#pragma unroll
+  for (int p = 0; p < 4; ++p) {
+    q[p] = on ? load4<T>(src + p * C + c0) : floatx4{0.f, 0.f, 0.f, 0.f};
+    sum += q[p][0] + q[p][1] + q[p][2] + q[p][3];
+  }
+  const float mean = wave_sum(sum) / (float)H;
+  float sq = 0.f;
+  if (on) {
+#pragma unroll
+    for (int p = 0; p < 4; ++p)
+#pragma unroll
+      for (int j = 0; j < 4; ++j) { const float d = q[p][j] - mean; sq += d * d; }
+  }
+  const float var = wave_sum(sq) / (float)H;
+  const float rstd = 1.0f / sqrtf(var + a.eps);
+  if (lane == 0 && a.rstd != nullptr) a.rstd[row] = rstd;
+  if (!on) return;
+  const int64_t o = (int64_t)row * H + 4 * c0;          // channel c0 + j owns features 4 (c0 + j) + p
+#pragma unroll
+  for (int j = 0; j < 4; j += 2) {
+    floatx4 xh[2], y[2];
+#pragma unroll
+    for (int h = 0; h < 2; ++h) {
+      const floatx4 gm = *(const floatx4*)(a.gamma + 4 * (c0 + j + h)), bt = *(const floatx4*)(a.beta + 4 * (c0 + j + h));
+#pragma unroll
+      for (int p = 0; p < 4; ++p) {
+        xh[h][p] = (q[p][j + h] - mean) * rstd;
+        y[h][p] = xh[h][p] * gm[p] + bt[p];
+      }
+    }
+    if (a.xhat != nullptr) store8<T>(a.xhat + o + 4 * j, xh[0], xh[1]);
+    store8<T>(a.y + o + 4 * j, y[0], y[1]);
+  }
+}
+template <typename T> int ln_fwd_chw4(hipStream_t st, const LnFwdArgs<T>& a) {
+  if (a.rows <= 0) return RL_OK;
+  if (!chw4_ok(a.H) || a.in_mode != 0 || a.drop.thresh != 0u || a.row_live != nullptr) return RL_ERR_ARG;
+  hipLaunchKernelGGL((ln_fwd_chw4_kernel<T>), dim3((a.rows + 3) / 4), dim3(256), 0, st, a);
+  return RL_LAUNCH_CHECK();
+}
+template int ln_fwd_chw4<bf16_t>(hipStream_t, const LnFwdArgs<bf16_t>&);
+template int ln_fwd_chw4<float>(hipStream_t, const LnFwdArgs<float>&);
+
+// out[t][c * 4 + p] = x[inv[t]][p * C + c]: gather_rows with the flatten (the glyph-only entry point)
+template <typename T>
+__global__ void __launch_bounds__(256) gather_rows_chw4_kernel(const T* __restrict__ x, const int* __restrict__ inv, int T_, int H, T* __restrict__ out) {
+  const int t = blockIdx.x * 4 + (threadIdx.x >> 6), c0 = (threadIdx.x & 63) * 4, C = H >> 2;
+  if (t >= T_ || c0 >= C) return;
+  const T* src = x + (int64_t)inv[t] * H;
+  floatx4 q[4];
+#pragma unroll
+  for (int p = 0; p < 4; ++p) q[p] = load4<T>(src + p * C + c0);
+  T* o = out + (int64_t)t * H + 4 * c0;
+#pragma unroll
+  for (int j = 0; j < 4; j += 2)
+    store8<T>(o + 4 * j, floatx4{q[0][j], q[1][j], q[2][j], q[3][j]}, floatx4{q[0][j + 1], q[1][j + 1], q[2][j + 1], q[3][j + 1]});
+}
+template <typename T> int gather_rows_chw4(hipStream_t st, const T* x, const int* inv, int T_, int H, T* out) {
+  if (!chw4_ok(H)) return RL_ERR_ARG;
+  if (T_ <= 0) return RL_OK;
+  hipLaunchKernelGGL((gather_rows_chw4_kernel<T>), dim3((T_ + 3) / 4), dim3(256), 0, st, x, inv, T_, H, out);
+  return RL_LAUNCH_CHECK();
+}
+template int gather_rows_chw4<bf16_t>(hipStream_t, const bf16_t*, const int*, int, int, bf16_t*);
+template int gather_rows_chw4<float>(hipStream_t, const float*, const int*, int, int, float*);
+
+// segment_sum whose input rows are in feature order and whose output rows are in storage order: the scatter into the fp32
+// accumulator is the plain one, the cast that follows it anyway stores out[u][p * C + c] = acc[u][c * 4 + p]
+template <typename T>
+__global__ void segsum_cast_chw4_kernel(const float* __restrict__ acc, T* __restrict__ out, int H, const int* __restrict__ nuniq) {
+  const int C = H >> 2, per_row = H >> 4;
+  const int64_t n = (int64_t)(*nuniq) * per_row;
+  for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t u = i / per_row;
+    const int c0 = (int)(i - u * per_row) * 4;
+    const float* a = acc + u * H + 4 * c0;
+    const floatx4 v0 = *(const floatx4*)a, v1 = *(const floatx4*)(a + 4), v2 = *(const floatx4*)(a + 8), v3 = *(const floatx4*)(a + 12);
+    T* o = out + u * H + c0;
+#pragma unroll
+    for (int p = 0; p < 4; ++p) store4<T>(o + p * C, floatx4{v0[p], v1[p], v2[p], v3[p]});
+  }
+}
+template <typename T> int segment_sum_chw4(hipStream_t st, const T* x, const int* inv, int T_, int H, float* acc, T* out, const int* nuniq_dev) {
+  if (!chw4_ok(H)) return RL_ERR_ARG;
+  if (T_ <= 0) return RL_OK;
+  (void)hipMemsetAsync(acc, 0, (size_t)T_ * H * sizeof(float), st);
+  hipLaunchKernelGGL((segsum_scatter_kernel<T>), dim3((H / 4 + 63) / 64, T_), dim3(64), 0, st, x, inv, T_, H, acc);
+  hipLaunchKernelGGL((segsum_cast_chw4_kernel<T>), dim3(1024), dim3(256), 0, st, acc, out, H, nuniq_dev);
+  return RL_LAUNCH_CHECK();
+}
+template int segment_sum_chw4<bf16_t>(hipStream_t, const bf16_t*, const int*, int, int, float*, bf16_t*, const int*);
+template int segment_sum_chw4<float>(hipStream_t, const float*, const int*, int, int, float*, float*, const int*);
+
+// ---------------------------------------------------------------------------------------------
 // Row-wise argmax: one 256-thread workgroup per row, 16-byte loads, (value, index) pairs reduced with the
 // first-occurrence tie rule.
 // ---------------------------------------------------------------------------------------------

@@ -136,8 +136,8 @@ def tensor_specs(cfg, model_type="arch3"):
             specs.append(("pho_gru.bias_hh_l0", (3 * H,), "gru"))
             bert("pho_model.", cfg["pho_layers"])
         if with_res:
-            chans = [cfg["num_fonts"], 64, 128, 256, 512, 768]
-            for b in range(1, 6):
+            chans = tower_channels(cfg)
+            for b in range(1, len(chans)):
                 ci, co = chans[b - 1], chans[b]
                 p = "resnet.res_block%d." % b
 
@@ -162,6 +162,14 @@ def tensor_specs(cfg, model_type="arch3"):
     specs.append(("classifier.weight", (V, H), "normal"))
     specs.append(("classifier.bias", (V,), "zeros"))
     return specs
+
+
+def tower_channels(cfg):
+    """[input channels, block 1 .. block n output channels] of the glyph tower: CharResNet (char_cnn.py:36-55) or, with
+    image_model_type 1, CharResNet1 (char_cnn.py:57-75), which always takes one channel"""
+    if cfg.get("image_model_type", 0) == 1:
+        return [1, 64, 128, 192, 192]
+    return [cfg["num_fonts"], 64, 128, 256, 512, 768]
 
 
 def init_state_dict_numpy(cfg, model_type="arch3", seed=0, scheme="reference", tie=True):

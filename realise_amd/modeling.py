@@ -61,8 +61,8 @@ class RealiseModule(nn.Module):
         super().__init__()
         if not isinstance(config, RealiseConfig):
             config = RealiseConfig(**{k: getattr(config, k) for k in RealiseConfig.DEFAULTS if hasattr(config, k)})
-        config.validate()
         self.config = config
+        config.validate(glyph_branch=self._has_glyph_branch())
         self.vocab_size = config.vocab_size
         self.compute_dtype = compute_dtype or os.environ.get("REALISE_DTYPE", "bf16")
         if self.compute_dtype not in _DTYPES:
