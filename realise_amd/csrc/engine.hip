@@ -166,10 +166,10 @@ template <typename T> struct Engine : EngineBase {
     int64_t res_xhat, res_rstd, res_h, gate_mean, gate_msum, gate_g, fused;
     int64_t bn_sums, bn_slots;
     int64_t gu_first, gu_flag, gu_ids, gu_counts, gu_inv, gu_bounds, seg_acc, gu_dense;   // glyph dedup
-    // backward scratch
-    int64_t gA, gB, gC, gE, gD, gF, rowdot, X1, X2, X3, dz, tn_slab, ln_slots;
-    int64_t wC1[2], wC2[2], wD[2], wF[2], tn_slab2;      // per-parity dY copies + second slab: weight gradients on the side stream
-    // backward scratch of the three concurrent branches: 0 = bert (the fields above), 1 = pho_model + GRU, 2 = glyph ResNet
+    // backward: gA = the gradient that enters a stack; X1 / X2 / X3 = d bert / d pho / d res behind the fusion
+    int64_t gA, X1, X2, X3, dz;
+    // backward scratch of the three concurrent lanes: 0 = bert (+ head, output block), 1 = pho_model + GRU, 2 = glyph ResNet
+    // (wC1 / wC2 / wD / wF: per-parity dY copies, tn_slab2: second slab - weight gradients on the side stream)
     struct Scratch { int64_t gB, gE, rowdot, tn_slab, tn_slab2, ln_slots, wC1[2], wC2[2], wD[2], wF[2]; } sc[3];
     std::vector<std::pair<int64_t, int64_t>> zero_once;      // (offset, bytes): self-cleaning accumulators, zero-filled when the plan is installed
     int64_t gru_dh, gru_dgi, gru_dgh, gru_onehot, gru_dtable;
@@ -219,7 +219,10 @@ template <typename T> struct Engine : EngineBase {
   // branch overlap: two engine-owned streams next to the caller's, fork / join events
   hipStream_t bst[2] = {nullptr, nullptr};
   hipEvent_t ev_fork = nullptr, ev_join[2] = {nullptr, nullptr};
-  int cs = 0;                              // scratch set the backward helpers currently enqueue with (pl.sc[cs])
+  // What a backward helper enqueues with: a stream together with the scratch set and the pending LayerNorm folds that belong to it.
+  // two_sets: the lane owns two dY buffer sets, so its layer weight gradients may go to the side stream (the bert lane only).
+  struct Lane { hipStream_t st; const typename Plan::Scratch* sc; LnFoldSites* pend; bool two_sets; };
+  Lane lane(int k, hipStream_t st) { return Lane{st, &pl.sc[k], &pend[k], k == 0}; }
   bool branches_ok() {
     if (bst[0] != nullptr) return true;
     for (int k = 0; k < 2; ++k)
@@ -582,37 +585,37 @@ template <typename T> struct Engine : EngineBase {
     p.cls_xc = b.take(Tk * H * e); p.cls_gc = b.take(Tk * H * e);
     p.zero_once.push_back({p.cls_xc, Tk * H * e}); p.zero_once.push_back({p.cls_gc, Tk * H * e});
     p.cls_slab = (!glyph_only && sizeof(T) == 2) ? b.take(4 * Tk * H * 4) : 0;      // fp32 planes of the split-K classifier data gradient
-    // shared backward scratch
-    p.gA = b.take(Tk * H * e); p.gB = b.take(Tk * H * e); p.gC = b.take(Tk * H * e); p.gE = b.take(Tk * H * e);
+    // Backward scratch.  gA is the gradient that enters a stack; everything else is per lane (Plan::sc).  What a lane's set holds:
+    //   SET_TWO   (the bert lane, and every stage of a serial pass): gB / gE / rowdot, two slabs and TWO sets of a layer's four dY
+    //             matrices - operands of the deferred weight gradients: they live in the buffer set of the layer's parity until the
+    //             side stream has consumed them
+    //   SET_ONE   (the pinyin lane: its layers run next to the bert layers): the same with ONE dY set and one slab, named by both parities
+    //   SET_GLYPH (the glyph lane): LayerNorm-backward output, slabs of the conv weight gradients, fold slots; the rest shared with set 0
+    // The takes of a kind come in the order the workspace has always had them (it differs between the kinds): every offset stays put.
     const int64_t Tw = glyph_only ? 1 : Tk;               // the wide BERT scratch is not needed by the glyph-only plan
-    p.gD = b.take(Tw * I * e); p.gF = b.take(Tw * 3 * H * e); p.rowdot = b.take((int64_t)B * nh * S * 4);
-    // operands of the deferred weight gradients: a layer's four dY matrices live in the buffer set of its parity until the
-    // side stream has consumed them (set 0 aliases the classic gC / gD / gF scratch)
-    p.wC1[0] = p.gC; p.wD[0] = p.gD; p.wF[0] = p.gF; p.wC2[0] = b.take(Tw * H * e);
-    p.wC1[1] = b.take(Tw * H * e); p.wC2[1] = b.take(Tw * H * e); p.wD[1] = b.take(Tw * I * e); p.wF[1] = b.take(Tw * 3 * H * e);
-    p.tn_slab2 = b.take(TN_SLAB_ELEMS * 4);
-    p.tn_slab = b.take(TN_SLAB_ELEMS * 4);
-    p.ln_slots = b.take((int64_t)(LN_FOLD_MAX + 1) * LN_SLOT_BYTES);     // LN_FOLD_MAX deferred sites + one immediate region
-    tap("d_x0", p.gB, Tk * H);
-    {
-      typename Plan::Scratch& s0 = p.sc[0];
-      s0.gB = p.gB; s0.gE = p.gE; s0.rowdot = p.rowdot; s0.tn_slab = p.tn_slab; s0.tn_slab2 = p.tn_slab2; s0.ln_slots = p.ln_slots;
-      for (int k = 0; k < 2; ++k) { s0.wC1[k] = p.wC1[k]; s0.wC2[k] = p.wC2[k]; s0.wD[k] = p.wD[k]; s0.wF[k] = p.wF[k]; }
-      p.sc[1] = s0; p.sc[2] = s0;
-      if (vr.arch) {
-        if (!glyph_only && vr.pho) {          // pho branch: a full private set (its layers run next to the bert layers)
-          typename Plan::Scratch& s1 = p.sc[1];
-          s1.gB = b.take(Tk * H * e); s1.gE = b.take(Tk * H * e); s1.rowdot = b.take((int64_t)B * nh * S * 4);
-          s1.tn_slab = b.take(TN_SLAB_ELEMS * 4); s1.tn_slab2 = s1.tn_slab; s1.ln_slots = b.take((int64_t)(LN_FOLD_MAX + 1) * LN_SLOT_BYTES);
-          s1.wC1[0] = b.take(Tk * H * e); s1.wC2[0] = b.take(Tk * H * e); s1.wD[0] = b.take(Tk * I * e); s1.wF[0] = b.take(Tk * 3 * H * e);
-          s1.wC1[1] = s1.wC1[0]; s1.wC2[1] = s1.wC2[0]; s1.wD[1] = s1.wD[0]; s1.wF[1] = s1.wF[0];
-        }
-        if (vr.res) {
-          typename Plan::Scratch& s2 = p.sc[2];   // glyph branch: LayerNorm-backward output, slabs of the conv weight gradients
-          s2.gE = b.take(Tk * H * e); s2.tn_slab = b.take(TN_SLAB_ELEMS * 4); s2.ln_slots = b.take((int64_t)(LN_FOLD_MAX + 1) * LN_SLOT_BYTES);
-        }
+    enum { SET_TWO, SET_ONE, SET_GLYPH };
+    auto take_scratch = [&](typename Plan::Scratch& s, int kind) {
+      auto hid = [&](int64_t rows) { return b.take(rows * H * e); };
+      auto rowdot = [&]() { return b.take((int64_t)B * nh * S * 4); };
+      auto slab = [&]() { return b.take(TN_SLAB_ELEMS * 4); };
+      auto slots = [&]() { return b.take((int64_t)(LN_FOLD_MAX + 1) * LN_SLOT_BYTES); };     // LN_FOLD_MAX deferred sites + one immediate region
+      if (kind == SET_TWO) {
+        s.gB = hid(Tk); s.wC1[0] = hid(Tk); s.gE = hid(Tk); s.wD[0] = b.take(Tw * I * e); s.wF[0] = b.take(Tw * 3 * H * e); s.rowdot = rowdot();
+        s.wC2[0] = hid(Tw); s.wC1[1] = hid(Tw); s.wC2[1] = hid(Tw); s.wD[1] = b.take(Tw * I * e); s.wF[1] = b.take(Tw * 3 * H * e);
+        s.tn_slab2 = slab(); s.tn_slab = slab(); s.ln_slots = slots();
+      } else if (kind == SET_ONE) {
+        s.gB = hid(Tk); s.gE = hid(Tk); s.rowdot = rowdot(); s.tn_slab = s.tn_slab2 = slab(); s.ln_slots = slots();
+        s.wC1[0] = s.wC1[1] = hid(Tk); s.wC2[0] = s.wC2[1] = hid(Tk); s.wD[0] = s.wD[1] = b.take(Tk * I * e); s.wF[0] = s.wF[1] = b.take(Tk * 3 * H * e);
+      } else {
+        s.gE = hid(Tk); s.tn_slab = slab(); s.ln_slots = slots();
       }
-    }
+    };
+    p.gA = b.take(Tk * H * e);
+    take_scratch(p.sc[0], SET_TWO);
+    tap("d_x0", p.sc[0].gB, Tk * H);
+    p.sc[1] = p.sc[2] = p.sc[0];                          // (a lane this model does not have, and what the glyph lane shares)
+    if (vr.arch && vr.pho && !glyph_only) take_scratch(p.sc[1], SET_ONE);
+    if (vr.arch && vr.res) take_scratch(p.sc[2], SET_GLYPH);
     if (vr.arch) {
       if (!glyph_only) {
         if (vr.pho) plan_stack(p.pho, cfg.pho_layers, "pho_model");
@@ -667,22 +670,6 @@ template <typename T> struct Engine : EngineBase {
         p.r_dout = b.take(big); p.r_dc2 = b.take(big); p.r_dcs = b.take(big); p.r_dh1 = b.take(big); p.r_dc1 = b.take(big);
         p.r_dx = b.take(big);
       }
-    }
-    {   // named views of the scratch regions (diagnostics: tools/diag_stale.py zeroes them one at a time)
-      const int64_t e1 = (int64_t)sizeof(T);
-      auto stap = [&](const char* n, int64_t off, int64_t bytes) { tap(std::string("scratch.") + n, off, bytes / e1); };
-      stap("tn_slab", p.tn_slab, TN_SLAB_ELEMS * 4); stap("ln_slots", p.ln_slots, LN_SLOT_BYTES);
-      stap("gA", p.gA, Tk * H * e); stap("gB", p.gB, Tk * H * e); stap("gC", p.gC, Tk * H * e); stap("gE", p.gE, Tk * H * e);
-      stap("gD", p.gD, Tw * I * e); stap("gF", p.gF, Tw * 3 * H * e);
-      if (vr.res) {
-        const int64_t big = (int64_t)p.blk[0].Pout * 64 * e;
-        stap("r_dout", p.r_dout, big); stap("r_dc2", p.r_dc2, big); stap("r_dcs", p.r_dcs, big); stap("r_dh1", p.r_dh1, big);
-        stap("r_dc1", p.r_dc1, big); stap("r_dx", p.r_dx, big); stap("bn_sums", p.bn_sums, 2 * 1024 * 4);
-        stap("bn_slots", p.bn_slots, (int64_t)COL_SLOT_BYTES); stap("seg_acc", p.seg_acc, Tk * H * 4);
-      }
-      if (vr.arch) stap("X1", p.X1, Tk * H * e);
-      if (vr.pho) stap("X2", p.X2, Tk * H * e);
-      if (vr.res) stap("X3", p.X3, Tk * H * e);
     }
     p.total = b.off;
     return p;
@@ -813,35 +800,36 @@ template <typename T> struct Engine : EngineBase {
   // LayerNorms of four transformer layers) are folded by ONE launch at the end of the layer group instead of one fold per site
   // (38 launches of ~7 us on the critical chain per step).  Per scratch set (= per branch stream).
   LnFoldSites pend[3];
-  float* ln_region(int k) const { return wp<float>(pl.sc[cs].ln_slots) + (int64_t)k * LN_SLOT_FLOATS; }
-  int flush_ln_folds(hipStream_t st) {
-    LnFoldSites& f = pend[cs];
+  float* ln_region(const Lane& la, int k) const { return wp<float>(la.sc->ln_slots) + (int64_t)k * LN_SLOT_FLOATS; }
+  int flush_ln_folds(const Lane& la) {
+    LnFoldSites& f = *la.pend;
     if (f.n == 0) return RL_OK;
     f.H = H;
-    const int rc = ln_fold_multi(st, f);
+    const int rc = ln_fold_multi(la.st, f);
     f.n = 0;
     return rc;
   }
-  int ln_bwd_deferred(hipStream_t st, LnBwdArgs<T>& ln) {
-    LnFoldSites& f = pend[cs];
+  int ln_bwd_deferred(const Lane& la, LnBwdArgs<T>& ln) {
+    LnFoldSites& f = *la.pend;
     int nrec = 0;
-    ln.slots = ln_region(f.n);
+    ln.slots = ln_region(la, f.n);
     ln.deferred_records = &nrec;
-    RL_TRY(ln_bwd<T>(st, ln));
+    RL_TRY(ln_bwd<T>(la.st, ln));
     if (nrec > 0) {
       f.s[f.n++] = LnFoldSite{ln.slots, nrec, ln.dgamma, ln.dbeta};
-      if (f.n == LN_FOLD_MAX) RL_TRY(flush_ln_folds(st));
+      if (f.n == LN_FOLD_MAX) RL_TRY(flush_ln_folds(la));
     }
     return RL_OK;
   }
 
   // backward of layers [hi .. lo] of a stack; gA holds d(output of layer hi) on entry and d(input of layer lo) on exit
-  int layers_backward(hipStream_t st, int sid, const StackOff& so, const std::vector<LayerSh>& shs, StackAct& a, int hi, int lo,
+  int layers_backward(const Lane& la, int sid, const StackOff& so, const std::vector<LayerSh>& shs, StackAct& a, int hi, int lo,
                       T* gA) {
     const int B = pl.B, S = pl.S, Tk = B * S;
-    const typename Plan::Scratch& sc = pl.sc[cs];
+    const hipStream_t st = la.st;
+    const typename Plan::Scratch& sc = *la.sc;
     T* gB = wp<T>(sc.gB); T* gE = wp<T>(sc.gE);
-    const bool ov = g_wgrad_overlap && (!branch_mode || cs == 0) && side_ok();      // under branch overlap only the bert branch owns two dY sets
+    const bool ov = g_wgrad_overlap && la.two_sets && side_ok();      // under branch overlap only the bert lane owns two dY sets
     for (int l = hi; l >= lo; --l) {
       const LayerOff& o = so.layers[l];
       const LayerSh& w = shs[l];
@@ -880,7 +868,7 @@ template <typename T> struct Engine : EngineBase {
         LnBwdArgs<T> ln; ln.rows = Tk; ln.H = H; ln.dy = gA; ln.xhat = wp<T>(t.s2); ln.rstd = wp<float>(t.rstd2); ln.row_live = live_rows();
         ln.gamma = pp(o.out_ln_g); ln.dx = gB; ln.dx_drop = (d3.thresh || keep_dy) ? gC1 : nullptr; ln.out_drop = d3;
         ln.dgamma = gp(o.out_ln_g); ln.dbeta = gp(o.out_ln_b);
-        RL_TRY(ln_bwd_deferred(st, ln));
+        RL_TRY(ln_bwd_deferred(la, ln));
       }
       const T* dso = (d3.thresh || keep_dy) ? gC1 : gB;
       RL_TRY(wgrad(0, dso, H, wp<T>(t.post), I, H, I, gp(o.out_b), gp(o.out_w)));
@@ -897,7 +885,7 @@ template <typename T> struct Engine : EngineBase {
         LnBwdArgs<T> ln; ln.rows = Tk; ln.H = H; ln.dy = gB; ln.xhat = wp<T>(t.s1); ln.rstd = wp<float>(t.rstd1); ln.row_live = live_rows();
         ln.gamma = pp(o.ao_ln_g); ln.dx = gA; ln.dx_drop = (d2.thresh || keep_dy) ? gC2 : nullptr; ln.out_drop = d2;
         ln.dgamma = gp(o.ao_ln_g); ln.dbeta = gp(o.ao_ln_b);
-        RL_TRY(ln_bwd_deferred(st, ln));
+        RL_TRY(ln_bwd_deferred(la, ln));
       }
       const T* dsa = (d2.thresh || keep_dy) ? gC2 : gA;
       RL_TRY(wgrad(2, dsa, H, wp<T>(t.ctx), H, H, H, gp(o.ao_b), gp(o.ao_w)));
@@ -928,13 +916,14 @@ template <typename T> struct Engine : EngineBase {
         done_pending[p] = true;
       }
     }
-    return flush_ln_folds(st);
+    return flush_ln_folds(la);
   }
 
   // embeddings backward: gA = d(embedding output) -> dx (T*, d of the pre-LayerNorm sum) ; scatters table grads
-  int emb_backward(hipStream_t st, int sid, const StackOff& so, StackAct& a, const int64_t* ids, int pos_zero, const T* gA, T* dx) {
+  int emb_backward(const Lane& la, int sid, const StackOff& so, StackAct& a, const int64_t* ids, int pos_zero, const T* gA, T* dx) {
     const int B = pl.B, S = pl.S, Tk = B * S;
-    LnBwdArgs<T> ln; ln.slots = ln_region(LN_FOLD_MAX); ln.rows = Tk; ln.H = H; ln.dy = gA; ln.in_drop = site(sid * 1000 + 900, cfg.hidden_dropout);
+    const hipStream_t st = la.st;
+    LnBwdArgs<T> ln; ln.slots = ln_region(la, LN_FOLD_MAX); ln.rows = Tk; ln.H = H; ln.dy = gA; ln.in_drop = site(sid * 1000 + 900, cfg.hidden_dropout);
     ln.xhat = wp<T>(a.emb_xhat); ln.rstd = wp<float>(a.emb_rstd); ln.gamma = pp(so.ln_g); ln.dx = dx;
     ln.dgamma = gp(so.ln_g); ln.dbeta = gp(so.ln_b);
     ln.row_live = live_rows();      // (padding rows: dy is an exact zero - dx written as zeros without reading the row's saved xhat)
@@ -1065,7 +1054,8 @@ template <typename T> struct Engine : EngineBase {
     return segment_sum<T>(st, d_res, wp<int>(pl.gu_inv), Tk, H, wp<float>(pl.seg_acc), wp<T>(pl.r_dout), wp<int>(pl.gu_bounds));
   }
   // d_top: gradient w.r.t. the last block's output per DISTINCT glyph [U, top pixels, top channels] (already summed over the tokens sharing it)
-  int resnet_backward(hipStream_t st, const T* d_top) {
+  int resnet_backward(const Lane& la, const T* d_top) {
+    const hipStream_t st = la.st;
     float* sums = wp<float>(pl.bn_sums);
     const T* d_out = d_top;
     if (!glyph_gathered) { RL_TRY(gather_glyphs(st)); glyph_gathered = true; }      // K7: block 1's weight gradients read the gathered images
@@ -1101,7 +1091,7 @@ template <typename T> struct Engine : EngineBase {
                                Pn, Co, dcs, gp(o.bns.g), gp(o.bns.b), rb, Pn));
       }
       // conv2 (3x3 s1): weight grad and data grad
-      { TnEpi te; te.slab = wp<float>(pl.sc[cs].tn_slab); te.slab_elems = TN_SLAB_ELEMS; te.mode = TN_CONVW; te.out = gp(o.w2); te.Cin = Co; te.Cpad = Co; te.KHW = 9;
+      { TnEpi te; te.slab = wp<float>(la.sc->tn_slab); te.slab_elems = TN_SLAB_ELEMS; te.mode = TN_CONVW; te.out = gp(o.w2); te.Cin = Co; te.Cpad = Co; te.KHW = 9;
         if (a.Hout == 1) { te.tap0 = 4; RL_TRY(gemm_tn<T>(st, dc2, Co, wp<T>(a.h1), Co, Pn, Co, Co, te, rb.rows_dev)); }       // centre tap only
         else RL_TRY(gemm_tn_conv<T>(st, dc2, Co, geom(wp<T>(a.h1), nullptr, Pn, a.Hout, a.Hout, Co, 3, 1, 1, 0, rb.rows_dev), Pn, Co, 9 * Co, te)); }
       { EpiParams<T> ep; ep.mode = EPI_STORE; ep.out = dh1; ep.ldo = Co;
@@ -1112,9 +1102,9 @@ template <typename T> struct Engine : EngineBase {
       RL_TRY(bn_bwd_apply<T>(st, dh1, wp<T>(a.h1), wp<T>(a.c1), wp<float>(a.bn1.mean), wp<float>(a.bn1.rstd), pp(o.bn1.g), sums,
                              Pn, Co, dc1, gp(o.bn1.g), gp(o.bn1.b), rb, Pn));
       // conv1 (3x3 s2) and shortcut (1x1 s2) weight grads
-      { TnEpi te; te.slab = wp<float>(pl.sc[cs].tn_slab); te.slab_elems = TN_SLAB_ELEMS; te.mode = TN_CONVW; te.out = gp(o.w1); te.Cin = o.cin; te.Cpad = Cin; te.KHW = 9;
+      { TnEpi te; te.slab = wp<float>(la.sc->tn_slab); te.slab_elems = TN_SLAB_ELEMS; te.mode = TN_CONVW; te.out = gp(o.w1); te.Cin = o.cin; te.Cpad = Cin; te.KHW = 9;
         RL_TRY(gemm_tn_conv<T>(st, dc1, Co, geom(x_in, index, Pn, a.Hout, a.Hin, Cin, 3, 2, 1, 0, rb.rows_dev), Pn, Co, 9 * Cin, te)); }
-      { TnEpi te; te.slab = wp<float>(pl.sc[cs].tn_slab); te.slab_elems = TN_SLAB_ELEMS; te.mode = TN_CONVW; te.out = gp(o.ws); te.Cin = o.cin; te.Cpad = Cin; te.KHW = 1;
+      { TnEpi te; te.slab = wp<float>(la.sc->tn_slab); te.slab_elems = TN_SLAB_ELEMS; te.mode = TN_CONVW; te.out = gp(o.ws); te.Cin = o.cin; te.Cpad = Cin; te.KHW = 1;
         RL_TRY(gemm_tn_conv<T>(st, dcs, Co, geom(x_in, index, Pn, a.Hout, a.Hin, Cin, 1, 2, 0, 0, rb.rows_dev), Pn, Co, Cin, te)); }
       if (k > 0) {   // d x_in = dgrad(conv1) + dgrad(shortcut); the glyph table itself is frozen
         const int Pin = pl.blk[k - 1].Pout;
@@ -1192,7 +1182,8 @@ template <typename T> struct Engine : EngineBase {
     }
     return RL_OK;
   }
-  int gru_backward(hipStream_t st, const T* dout) {
+  int gru_backward(const Lane& la, const T* dout) {
+    const hipStream_t st = la.st;
     const int N = pl.B * pl.S, Tp = last.Tp;
     float* dtable = wp<float>(pl.gru_dtable);
     RL_TRY(fill_f32(st, dtable, 0.f, 64LL * 3 * H));
@@ -1208,12 +1199,12 @@ template <typename T> struct Engine : EngineBase {
       a.rzn = wp<T>(pl.gru_rzn) + (int64_t)t * N * 3 * H; a.dout = dout; a.dh = wp<T>(pl.gru_dh); a.dgi = wp<T>(pl.gru_dgi);
       a.dgh = wp<T>(pl.gru_dgh); a.onehot = wp<T>(pl.gru_onehot);
       RL_TRY(gru_step_bwd<T>(st, a));
-      { TnEpi te; te.slab = wp<float>(pl.sc[cs].tn_slab); te.slab_elems = TN_SLAB_ELEMS; te.out = dtable; te.ldo = 3 * H; RL_TRY(gemm_tn<T>(st, a.onehot, 64, a.dgi, 3 * H, n, 64, 3 * H, te, nd)); }
+      { TnEpi te; te.slab = wp<float>(la.sc->tn_slab); te.slab_elems = TN_SLAB_ELEMS; te.out = dtable; te.ldo = 3 * H; RL_TRY(gemm_tn<T>(st, a.onehot, 64, a.dgi, 3 * H, n, 64, 3 * H, te, nd)); }
       // d b_hh = column sums of dgh: rides along the W_hh weight-gradient GEMM of the step (fused ones-vector MFMA, TnEpi::colsum) -
       // six column-reduction + fold launch pairs less; step 0 has no recurrent GEMM and keeps the reduction
       if (t == 0) RL_TRY(bias_grad<T>(st, a.dgh, 3 * H, n, 3 * H, gp(L.gru_b_hh), nd));
       if (t > 0) {
-        { TnEpi te; te.slab = wp<float>(pl.sc[cs].tn_slab); te.slab_elems = TN_SLAB_ELEMS; te.out = gp(L.gru_w_hh); te.ldo = H; te.colsum = gp(L.gru_b_hh);
+        { TnEpi te; te.slab = wp<float>(la.sc->tn_slab); te.slab_elems = TN_SLAB_ELEMS; te.out = gp(L.gru_w_hh); te.ldo = H; te.colsum = gp(L.gru_b_hh);
           RL_TRY(gemm_tn<T>(st, a.dgh, 3 * H, hs_prev, H, n, 3 * H, H, te, nd)); }
         EpiParams<T> ep; ep.mode = EPI_STORE; ep.out = a.dh; ep.ldo = H; ep.accumulate = 1;
         RL_TRY(gemm_nt<T>(st, a.dgh, 3 * H, sp<T>(sh_gru_hhT), 3 * H, n, H, 3 * H, ep, nd));
@@ -1260,6 +1251,16 @@ template <typename T> struct Engine : EngineBase {
     if (hipMemsetAsync(ws, 0, (size_t)pl.total, st) != hipSuccess) return RL_ERR_LAUNCH;
     return RL_OK;
   }
+  // the size conditions of a live-row step (g_live_rows): bf16 with the 16-row block lists, whole 64-row tiles in every GEMM dimension,
+  // 32-bit byte offsets into the widest activation
+  bool live_step_ok(int Tk) const {
+    return g_live_rows && live16() && (Tk % 64) == 0 && (H % 64) == 0 && (I % 64) == 0 && (int64_t)Tk * I * 2 < 0xFFFFFF00ll;
+  }
+  // the row-liveness tables of batch b (row_live, the live 64- / 32- / 16-row block lists, their counts, live lengths, the live-row list)
+  int fill_live_tables(hipStream_t st, const realise_batch& b) {
+    return row_liveness(st, b.masks, b.loss_masks, pl.B, pl.S, wp<uint8_t>(pl.row_live), wp<int>(pl.live_t64), wp<int>(pl.live_t32),
+                        wp<int>(pl.live_t16), wp<int>(pl.live_n), wp<int>(pl.live_rlen), wp<int>(pl.live_rows));
+  }
   int forward(hipStream_t st, const realise_batch& b) override {
     if (!sh || !ws) return RL_ERR_ARG;
     if (b.B < 1 || b.S < 1 || b.S > cfg.max_pos) return RL_ERR_ARG;       // (S > 128: the tiled attention kernels, attention.hip)
@@ -1297,16 +1298,15 @@ template <typename T> struct Engine : EngineBase {
     // their forward activations in the transformer stacks either.
     dead_ok = b.tgt_idx != nullptr && b.loss_masks != nullptr && g_skip_dead && b.want_dlogits && b.masks != nullptr && (Tk % 64) == 0 &&
               Tk / live_list_rows() <= TN_LIST_MAX_ENTRIES;      // (the weight-gradient kernels keep the block list in LDS: beyond 65536 bf16 token rows the step is dense)
-    if (dead_ok) RL_TRY(row_liveness(st, b.masks, b.loss_masks, pl.B, pl.S, wp<uint8_t>(pl.row_live), wp<int>(pl.live_t64), wp<int>(pl.live_t32), wp<int>(pl.live_t16), wp<int>(pl.live_n), wp<int>(pl.live_rlen), wp<int>(pl.live_rows)));
+    if (dead_ok) RL_TRY(fill_live_tables(st, b));
     // (the weight gradients of a live-row step must walk the same block list - only the grouped launch takes one: ADVICE round 4)
-    rows_live = dead_ok && b.training && g_live_rows && g_wgrad_group && live16() && (H % 64) == 0 && (I % 64) == 0 && (int64_t)Tk * I * 2 < 0xFFFFFF00ll;
+    rows_live = dead_ok && b.training && g_wgrad_group && live_step_ok(Tk);
     // Round 6, opt-in (realise_batch.eval_live_rows): an EVALUATION forward over the live rows as well.  The reference's evaluation reads
     // the predictions of a sentence's real tokens only (run.py:262-270 cuts them at `lengths`; the loss counts loss_masks rows), so the
     // transformer stacks need not compute the padding rows behind a sentence's last attended / loss position: their logits rows come
     // out finite and meaningless, every other row and the loss bit-identical to the dense forward's (same kernels per row).
-    if (!b.training && !dead_ok && b.eval_live_rows && g_live_rows && live16() && b.masks != nullptr && (Tk % 64) == 0 && (H % 64) == 0 &&
-        (I % 64) == 0 && (int64_t)Tk * I * 2 < 0xFFFFFF00ll) {
-      RL_TRY(row_liveness(st, b.masks, b.loss_masks, pl.B, pl.S, wp<uint8_t>(pl.row_live), wp<int>(pl.live_t64), wp<int>(pl.live_t32), wp<int>(pl.live_t16), wp<int>(pl.live_n), wp<int>(pl.live_rlen), wp<int>(pl.live_rows)));
+    if (!b.training && !dead_ok && b.eval_live_rows && b.masks != nullptr && live_step_ok(Tk)) {
+      RL_TRY(fill_live_tables(st, b));
       dead_ok = true; rows_live = true;      // (the tables exist; no backward follows an evaluation forward)
     }
     const T* bert_h = nullptr;
@@ -1431,7 +1431,7 @@ template <typename T> struct Engine : EngineBase {
     RL_TRY(sync_optimizer(st));
     RL_TRY(begin_gradient_pass(st, true));
     RL_TRY(top_segment_sum(st, (const T*)d_res));
-    RL_TRY(resnet_backward(st, wp<T>(pl.r_dout)));
+    RL_TRY(resnet_backward(lane(0, st), wp<T>(pl.r_dout)));
     return RL_OK;
   }
 
@@ -1486,7 +1486,8 @@ template <typename T> struct Engine : EngineBase {
   // hidden) - instead of a read-modify-write pass over the ~200 MB of cross-entropy gradient rows
   const float* loss_grad = nullptr;
   void set_loss_grad(const float* g) override { loss_grad = g; }
-  int stage_head(hipStream_t st) {      // classifier + final dropout ; leaves d(top hidden) in gA
+  int stage_head(const Lane& la) {      // classifier + final dropout ; leaves d(top hidden) in gA
+    const hipStream_t st = la.st;
     const int Tk = pl.B * pl.S;
     const T* dl = wp<T>(pl.dlogits);
     T* gA = wp<T>(pl.gA);
@@ -1495,7 +1496,7 @@ template <typename T> struct Engine : EngineBase {
     const T* cls_in = dfin.thresh ? wp<T>(pl.out_d) : top;
     if (cls_compact) {
       const int* n_act = wp<int>(pl.cls_nact);
-      { TnEpi te; te.slab = wp<float>(pl.tn_slab); te.slab_elems = TN_SLAB_ELEMS; te.colsum = gp(L.cls_b); te.out = gp(L.cls_w); te.ldo = H;
+      { TnEpi te; te.slab = wp<float>(la.sc->tn_slab); te.slab_elems = TN_SLAB_ELEMS; te.colsum = gp(L.cls_b); te.out = gp(L.cls_w); te.ldo = H;
         te.alpha_dev = loss_grad;
         RL_TRY(gemm_tn<T>(st, dl, Vp, wp<T>(pl.cls_xc), H, Tk, V, H, te, n_act)); }
       if constexpr (sizeof(T) == 2) {
@@ -1508,7 +1509,7 @@ template <typename T> struct Engine : EngineBase {
         RL_TRY(gemm_nt<T>(st, dl, Vp, sp<T>(sh_cls_wT), Vp, Tk, H, Vp, ep)); }
       return scatter_rows_drop<T>(st, wp<T>(pl.cls_gc), wp<int>(pl.cls_inv), Tk, H, gA, dfin, loss_grad);      // rows outside the loss: zero; + the final dropout's map
     }
-    { TnEpi te; te.slab = wp<float>(pl.tn_slab); te.slab_elems = TN_SLAB_ELEMS; te.colsum = gp(L.cls_b); te.out = gp(L.cls_w); te.ldo = H; te.alpha_dev = loss_grad;
+    { TnEpi te; te.slab = wp<float>(la.sc->tn_slab); te.slab_elems = TN_SLAB_ELEMS; te.colsum = gp(L.cls_b); te.out = gp(L.cls_w); te.ldo = H; te.alpha_dev = loss_grad;
       RL_TRY(gemm_tn<T>(st, dl, Vp, cls_in, H, Tk, V, H, te)); }
     { EpiParams<T> ep; ep.mode = EPI_STORE; ep.out = gA; ep.ldo = H;
       RL_TRY(gemm_nt<T>(st, dl, Vp, sp<T>(sh_cls_wT), Vp, Tk, H, Vp, ep)); }      // K = Vp: the padding columns are exact zeros on both sides
@@ -1517,37 +1518,14 @@ template <typename T> struct Engine : EngineBase {
     return RL_OK;
   }
 
-  int run_stage(hipStream_t st, int s) {
-    const int Tk = pl.B * pl.S;
+  // stages = gradient buckets.  SpellBert: bert layer groups | bert embeddings.  The Arch3 family: 0 output_block | 1 fusion (+ glyph
+  // ResNet) | 2 pinyin branch (when present) | bert layer groups | bert embeddings
+  int first_bert_stage() const { return !vr.arch ? 0 : (vr.pho ? 3 : 2); }
+  int stage_out_block(const Lane& la) {      // head + output_block; leaves d fused in gB (set 0)
     T* gA = wp<T>(pl.gA);
-    if (!vr.arch) {
-      // stage g (0..groups-1): bert layer group g (stage 0 also runs the head); last stage: embeddings
-      const int groups = L.bert_groups;
-      if (s < groups) {
-        if (s == 0) RL_TRY(stage_head(st));
-        int hi = cfg.bert_layers - 1 - 4 * s;
-        int lo = hi - 3 > 0 ? hi - 3 : 0;
-        RL_TRY(layers_backward(st, 0, L.bert, sh_bert, pl.bert, hi, lo, gA));
-      } else {
-        RL_TRY(emb_backward(st, 0, L.bert, pl.bert, last.src_idx, 0, gA, wp<T>(pl.sc[0].gB)));
-      }
-      return RL_OK;
-    }
-    // stages = buckets: 0 output_block | 1 fusion (+ glyph ResNet) | 2 pinyin branch (when present) | bert groups | bert embeddings
-    if (s == 0) return stage_out_block(st);
-    if (s == 1) {
-      RL_TRY(stage_fuse(st));
-      return vr.res ? stage_glyph(st) : RL_OK;
-    }
-    if (vr.pho && s == 2) return stage_pho(st);
-    return stage_bert(st, s - first_bert_stage());
-  }
-  int first_bert_stage() const { return vr.pho ? 3 : 2; }
-  int stage_out_block(hipStream_t st) {      // head + output_block; leaves d fused in gB (set 0)
-    T* gA = wp<T>(pl.gA);
-    RL_TRY(stage_head(st));
-    RL_TRY(layers_backward(st, 2, L.outb, sh_out, pl.outb, cfg.out_layers - 1, 0, gA));
-    RL_TRY(emb_backward(st, 2, L.outb, pl.outb, nullptr, 1, gA, wp<T>(pl.sc[0].gB)));
+    RL_TRY(stage_head(la));
+    RL_TRY(layers_backward(la, 2, L.outb, sh_out, pl.outb, cfg.out_layers - 1, 0, gA));
+    RL_TRY(emb_backward(la, 2, L.outb, pl.outb, nullptr, 1, gA, wp<T>(pl.sc[0].gB)));
     return RL_OK;
   }
   int stage_fuse(hipStream_t st) {           // d fused -> X1 (d bert), X2 (d pho), X3 (d res) [+ gate_net gradients]
@@ -1558,39 +1536,37 @@ template <typename T> struct Engine : EngineBase {
     g.dW = gp(L.gate_w); g.dbias = gp(L.gate_b); g.row_live = live_rows();
     return gate_bwd<T>(st, g);
   }
-  int stage_glyph(hipStream_t st) {          // resnet LayerNorm, segment sum over the tokens of a glyph, glyph ResNet
+  // (the glyph lane needs a gE of its own: the LayerNorm backward below writes it while the bert lane's layers keep d ctx in theirs)
+  int stage_glyph(const Lane& la) {          // resnet LayerNorm, segment sum over the tokens of a glyph, glyph ResNet
     const int Tk = pl.B * pl.S;
-    const typename Plan::Scratch& sc = pl.sc[cs];
-    LnBwdArgs<T> ln; ln.slots = ln_region(LN_FOLD_MAX); ln.rows = Tk; ln.H = H; ln.dy = wp<T>(pl.X3); ln.xhat = wp<T>(pl.res_xhat); ln.rstd = wp<float>(pl.res_rstd);
+    LnBwdArgs<T> ln; ln.slots = ln_region(la, LN_FOLD_MAX); ln.rows = Tk; ln.H = H; ln.dy = wp<T>(pl.X3); ln.xhat = wp<T>(pl.res_xhat); ln.rstd = wp<float>(pl.res_rstd);
     ln.row_live = live_rows();
-    ln.gamma = pp(L.res_ln_g); ln.dx = wp<T>(sc.gE); ln.dgamma = gp(L.res_ln_g); ln.dbeta = gp(L.res_ln_b);
-    RL_TRY(ln_bwd<T>(st, ln));
-    RL_TRY(top_segment_sum(st, wp<T>(sc.gE)));
-    return resnet_backward(st, wp<T>(pl.r_dout));
+    ln.gamma = pp(L.res_ln_g); ln.dx = wp<T>(la.sc->gE); ln.dgamma = gp(L.res_ln_g); ln.dbeta = gp(L.res_ln_b);
+    RL_TRY(ln_bwd<T>(la.st, ln));
+    RL_TRY(top_segment_sum(la.st, wp<T>(la.sc->gE)));
+    return resnet_backward(la, wp<T>(pl.r_dout));
   }
-  int stage_pho(hipStream_t st) {            // pho_model + GRU
+  int stage_pho(const Lane& la) {            // pho_model + GRU
     T* g2 = wp<T>(pl.X2);
-    T* gE = wp<T>(pl.sc[cs].gE);
-    RL_TRY(layers_backward(st, 1, L.pho, sh_pho, pl.pho, cfg.pho_layers - 1, 0, g2));
-    RL_TRY(emb_backward(st, 1, L.pho, pl.pho, nullptr, 0, g2, gE));       // gE = d gru_out (original order)
-    return gru_backward(st, gE);
+    T* gE = wp<T>(la.sc->gE);
+    RL_TRY(layers_backward(la, 1, L.pho, sh_pho, pl.pho, cfg.pho_layers - 1, 0, g2));
+    RL_TRY(emb_backward(la, 1, L.pho, pl.pho, nullptr, 0, g2, gE));       // gE = d gru_out (original order)
+    return gru_backward(la, gE);
   }
-  int stage_bert(hipStream_t st, int g) {    // bert layer group g, or (g == groups) its embeddings
-    T* g1 = wp<T>(pl.X1);
+  // bert layer group g (SpellBert, where no output block did it: group 0 runs the head first), or (g == groups) the bert embeddings
+  int stage_bert(const Lane& la, int g) {
+    T* g1 = wp<T>(vr.arch ? pl.X1 : pl.gA);      // the gradient arrives from the fusion in X1, from the head in gA
     if (g < L.bert_groups) {
-      int hi = cfg.bert_layers - 1 - 4 * g;
-      int lo = hi - 3 > 0 ? hi - 3 : 0;
-      return layers_backward(st, 0, L.bert, sh_bert, pl.bert, hi, lo, g1);
+      if (!vr.arch && g == 0) RL_TRY(stage_head(la));
+      const int hi = cfg.bert_layers - 1 - 4 * g, lo = std::max(hi - 3, 0);
+      return layers_backward(la, 0, L.bert, sh_bert, pl.bert, hi, lo, g1);
     }
-    return emb_backward(st, 0, L.bert, pl.bert, last.src_idx, 0, g1, wp<T>(pl.sc[0].gB));
+    return emb_backward(la, 0, L.bert, pl.bert, last.src_idx, 0, g1, wp<T>(pl.sc[0].gB));
   }
 
-  bool branch_mode = false;
-  // Whole backward pass with a "bucket final" signal per gradient bucket: evs[i] (caller-owned hipEvent_t) is recorded once every
-  // kernel that writes into bucket i has been enqueued, on the stream that runs last for that bucket - so a data-parallel caller can
-  // start the all-reduce of bucket i on its own stream (hipStreamWaitEvent) while the three model branches and the deferred weight
-  // gradients keep running.  The per-bucket form of backward() would serialise the branches and join the weight-gradient stream at
-  // every bucket boundary.
+  // A "bucket final" signal per gradient bucket: evs[i] (caller-owned hipEvent_t) is recorded once every kernel that writes into
+  // bucket i has been enqueued, on the stream that runs last for that bucket - so a data-parallel caller can start the all-reduce of
+  // bucket i on its own stream (hipStreamWaitEvent) while the three model branches and the deferred weight gradients keep running.
   std::vector<hipEvent_t> ev_sig;       // one per bucket (any number of bert groups)
   int signal_bucket(void* ev, hipStream_t s, bool through_side, int slot) {
     hipEvent_t e = (hipEvent_t)ev;
@@ -1603,40 +1579,47 @@ template <typename T> struct Engine : EngineBase {
     }
     return hipEventRecord(e, s) == hipSuccess ? RL_OK : RL_ERR_LAUNCH;
   }
+  // The schedule of the backward, its only copy: stages first .. last_stage in order, each followed by its bucket signal when the
+  // caller brought events (evs == nullptr: no signals).
+  // Serial form: every stage on lane 0 of the caller's stream.
+  // Branched form - the whole pass of an Arch3 model in one call (no per-bucket gradient exchange in between): the same stages, with
+  // the glyph and the pinyin stage on lanes of their own (bst[1] / bst[0]), forked behind the fusion and joined after the last bert
+  // stage, so the three branches behind the gate run concurrently.  (A bucket-by-bucket caller would serialise the branches and join
+  // the weight-gradient stream at every bucket boundary: data-parallel callers use the signalled whole pass instead.)
+  int backward_pass(hipStream_t st, int first, int last_stage, void* const* evs) {
+    const bool branched = vr.arch && first == 0 && last_stage == n_stages() - 1 && g_branch_overlap && (branch_mask() == 0 || branches_ok());
+    const Lane bert = lane(0, st);
+    const Lane glyph = branched && vr.res ? lane(2, bst[1]) : bert, pho = branched && vr.pho ? lane(1, bst[0]) : bert;
+    const int b0 = first_bert_stage();
+    int rc = RL_OK;
+    for (int s = first; rc == RL_OK && s <= last_stage; ++s) {
+      hipStream_t fin = st;                  // the stream that runs last for bucket s
+      if (s >= b0) rc = stage_bert(bert, s - b0);
+      else if (s == 0) rc = stage_out_block(bert);
+      else if (s == 1) {                     // fusion (before the fork) + glyph ResNet
+        rc = stage_fuse(st);
+        if (rc == RL_OK && branched) rc = fork(st);
+        if (rc == RL_OK && vr.res) { rc = stage_glyph(glyph); fin = glyph.st; }
+      } else { rc = stage_pho(pho); fin = pho.st; }
+      if (evs == nullptr || rc != RL_OK) continue;
+      // The one difference between the serial forms: with bucket signals the side stream is joined after every stage, before the
+      // signal is recorded; without, once at the end.  Branched, nothing is joined in between: a bucket whose layers ran on the bert
+      // lane (output block, bert stages) is signalled through the side stream, where its weight gradients finish.
+      if (!branched) rc = join_side(st);
+      if (rc == RL_OK) rc = signal_bucket(evs[s], fin, branched && (s == 0 || s >= b0), s);
+    }
+    if (!branched) return rc != RL_OK ? rc : join_side(st);          // the caller's stream owns every gradient of these stages once this returns
+    const int rj = join(st);
+    const int rs = join_side(st);
+    return rc != RL_OK ? rc : (rj != RL_OK ? rj : rs);
+  }
   int backward_signalled(hipStream_t st, void* const* evs, int n_events) override {
     if (!have_fwd) { fprintf(stderr, "[realise_hip] backward without a training forward (tgt_idx + want_dlogits)\n"); return RL_ERR_ARG; }
     const int n = n_stages();
     if (n_events != n || evs == nullptr) return RL_ERR_ARG;
     for (int i = 0; i < n; ++i) if (evs[i] == nullptr) return RL_ERR_ARG;
     RL_TRY(begin_gradient_pass(st, false));
-    cs = 0;
-    if (vr.arch && g_branch_overlap && (branch_mask() == 0 || branches_ok())) {
-      branch_mode = true;
-      const int b0 = first_bert_stage();
-      int rc = stage_out_block(st);
-      if (rc == RL_OK) rc = signal_bucket(evs[0], st, true, 0);
-      if (rc == RL_OK) rc = stage_fuse(st);
-      if (rc == RL_OK) rc = fork(st);
-      if (rc == RL_OK && vr.res) { cs = 2; rc = stage_glyph(bst[1]); }
-      if (rc == RL_OK) rc = signal_bucket(evs[1], vr.res ? bst[1] : st, false, 1);      // fusion (before the fork) + glyph ResNet
-      if (rc == RL_OK && vr.pho) { cs = 1; rc = stage_pho(bst[0]); }
-      if (rc == RL_OK && vr.pho) rc = signal_bucket(evs[2], bst[0], false, 2);
-      cs = 0;
-      for (int g = 0; rc == RL_OK && g <= L.bert_groups; ++g) {
-        rc = stage_bert(st, g);
-        if (rc == RL_OK) rc = signal_bucket(evs[b0 + g], st, true, b0 + g);
-      }
-      const int rj = join(st);
-      const int rs = join_side(st);
-      branch_mode = false;
-      return rc != RL_OK ? rc : (rj != RL_OK ? rj : rs);
-    }
-    for (int s = 0; s < n; ++s) {
-      RL_TRY(run_stage(st, s));
-      RL_TRY(join_side(st));
-      RL_TRY(signal_bucket(evs[s], st, false, s));
-    }
-    return RL_OK;
+    return backward_pass(st, 0, n - 1, evs);
   }
   int backward(hipStream_t st, int first, int last_stage) override {
     if (!have_fwd) { fprintf(stderr, "[realise_hip] backward without a training forward (tgt_idx + want_dlogits)\n"); return RL_ERR_ARG; }
@@ -1644,24 +1627,7 @@ template <typename T> struct Engine : EngineBase {
     if (last_stage < 0) last_stage = n - 1;
     if (first < 0 || last_stage >= n || first > last_stage) return RL_ERR_ARG;
     if (first == 0) RL_TRY(begin_gradient_pass(st, false));           // (a bucket-by-bucket caller starts its pass with stage 0)
-    cs = 0;
-    // whole pass in one call (no per-bucket gradient exchange in between): the three branches behind the gate run concurrently
-    if (vr.arch && first == 0 && last_stage == n - 1 && g_branch_overlap && (branch_mask() == 0 || branches_ok())) {
-      branch_mode = true;
-      int rc = stage_out_block(st);
-      if (rc == RL_OK) rc = stage_fuse(st);
-      if (rc == RL_OK) rc = fork(st);
-      if (rc == RL_OK && vr.res) { cs = 2; rc = stage_glyph(bst[1]); }
-      if (rc == RL_OK && vr.pho) { cs = 1; rc = stage_pho(bst[0]); }
-      cs = 0;
-      for (int g = 0; rc == RL_OK && g <= L.bert_groups; ++g) rc = stage_bert(st, g);
-      const int rj = join(st);
-      const int rs = join_side(st);
-      branch_mode = false;
-      return rc != RL_OK ? rc : (rj != RL_OK ? rj : rs);
-    }
-    for (int s = first; s <= last_stage; ++s) RL_TRY(run_stage(st, s));
-    return join_side(st);          // the caller's stream owns every gradient of these stages once this returns
+    return backward_pass(st, first, last_stage, nullptr);
   }
 };
 

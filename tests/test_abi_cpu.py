@@ -1,5 +1,8 @@
 """CPU checks of the boundary: the C-ABI library loads and exports every symbol the header declares;
-the parameter layout reproduces the reference's state_dict; the module shell refuses to run without a GPU."""
+the parameter layout reproduces the reference's state_dict; the module shell refuses to run without a GPU;
+the engine's shadow and workspace plans have the recorded sizes."""
+import ctypes as C
+import json
 import os
 import re
 
@@ -67,3 +70,53 @@ def test_module_shell_contract_without_gpu():
     assert torch.allclose(m.bert.embeddings.LayerNorm.bias, sd2["bert.embeddings.LayerNorm.bias"])
     with pytest.raises(_capi.RealiseHipError):
         m(synthetic_batch(2, 8, with_pho=False))                                     # no CPU fallback, fails loudly
+
+
+# (name, model_type, RealiseConfig keywords): SpellBert, Arch3, Arch3 on the CharResNet1 tower, and the switch settings of the
+# ablation goldens (tests/golden/abla_*)
+PLAN_VARIANTS = [
+    ("bert", "bert", {}),
+    ("arch3", "arch3", {}),
+    ("arch3_img1", "arch3", {"image_model_type": 1, "num_fonts": 1}),
+    ("abla_phono_resyes_gate", "arch3-abla", {"with_pho": "no", "with_res": "yes", "fusion": "gate"}),
+    ("abla_phoyes_resno_gate", "arch3-abla", {"with_pho": "yes", "with_res": "no", "fusion": "gate"}),
+    ("abla_phono_resno_gate", "arch3-abla", {"with_pho": "no", "with_res": "no", "fusion": "gate"}),
+    ("abla_phoyes_resyes_sum", "arch3-abla", {"with_pho": "yes", "with_res": "yes", "fusion": "sum"}),
+    ("abla_img1_phono_resyes_gate", "arch3-abla", {"image_model_type": 1, "num_fonts": 1, "with_pho": "no", "with_res": "yes", "fusion": "gate"}),
+]
+PLAN_SHAPES = [(2, 16, 4), (3, 40, 6), (64, 128, 8), (4, 512, 8), (256, 128, -1)]      # (B, S, Tp); Tp = -1: the glyph-only plan
+
+
+def plan_bytes_table():
+    """{"variant/dtype": {"shadow": bytes, "B,S,Tp": workspace bytes}}: planning makes no HIP call, so an engine over null arenas will do.
+    `python tests/test_abi_cpu.py` prints the table in the fixture's format."""
+    lib = _capi.load()
+    table = {}
+    for name, model_type, kw in PLAN_VARIANTS:
+        for dtype, dt in (("bf16", _capi.BF16), ("fp32", _capi.F32)):
+            c = _capi.make_config(RealiseConfig(**kw), model_type, dt)
+            e = lib.realise_engine_create(C.byref(c), None, None, None, None, None, None)
+            assert e, (name, dtype)
+            row = {"shadow": lib.realise_engine_shadow_bytes(e)}
+            for B, S, Tp in PLAN_SHAPES:
+                if Tp < 0 and not (model_type != "bert" and kw.get("with_res", "yes") == "yes"):
+                    continue                                                             # (no glyph branch: no glyph-only plan)
+                row["%d,%d,%d" % (B, S, Tp)] = lib.realise_engine_workspace_bytes(e, B, S, Tp)
+            lib.realise_engine_destroy(e)
+            table["%s/%s" % (name, dtype)] = row
+    return table
+
+
+def test_plan_sizes_are_the_recorded_ones(golden_dir):
+    """Nothing else notices a plan that silently grows: shadow and workspace byte counts of every model variant, both dtypes, against
+    tests/golden/plan_bytes.json (recorded before the backward scratch sets moved into Plan::sc alone)."""
+    with open(os.path.join(golden_dir, "plan_bytes.json")) as f:
+        recorded = json.load(f)
+    table = plan_bytes_table()
+    assert set(table) == set(recorded)
+    for key in sorted(recorded):
+        assert table[key] == recorded[key], key
+
+
+if __name__ == "__main__":
+    print(json.dumps(plan_bytes_table(), indent=1, sort_keys=True))
