@@ -143,6 +143,13 @@ typedef struct {
 } realise_gate;
 int realise_gate_fwd(void* stream, int dtype, const realise_gate* a);
 int realise_gate_bwd(void* stream, int dtype, const realise_gate* a);
+/* The fusion gate of SpellBertPho2ResArch4 (src/models.py:1139-1150): the same masked mean, gate_net and weighted sum, but the nsrc
+ * gates are ONE softmax over the gate_net outputs z (row maximum subtracted, fp32) instead of nsrc independent sigmoids, so g[t][0..nsrc)
+ * is a distribution over the modalities.  Same struct, same buffers, same nsrc / row_live rules as realise_gate_fwd. */
+int realise_gate_softmax_fwd(void* stream, int dtype, const realise_gate* a);
+/* Its backward (autograd of src/models.py:1139-1150): with dg_k = <d fused, src_k>, dz_k = g_k (dg_k - sum_j g_j dg_j); the source
+ * gradients g_d d fused + sum_k dz_k W[k][d], the mean's gradient and dW / dbias follow from dz exactly as in realise_gate_bwd. */
+int realise_gate_softmax_bwd(void* stream, int dtype, const realise_gate* a);
 /* Sum fusion of the ablation model (src/models_abla.py:278-279, fusion == "sum"): fused = (bert + pho) + res over rows x H, in fp32,
  * stored in `dtype`.  The backward hands the same d fused to each branch: dbert = dpho = dres = dfused (one launch, three copies -
  * the branch backwards run concurrently and two of them write into their incoming gradient buffer).  row_live (nullable, [rows]
@@ -193,7 +200,9 @@ int realise_argmax(void* stream, int dtype, const void* logits, int64_t ld, int 
  * (models.py:806-870) and their autograd (`loss.backward()`, run.py:200), one C call each.
  * ---------------------------------------------------------------------------------------- */
 typedef struct {
-  int32_t model_type;        /* 0 = SpellBert (BERT only), 1 = SpellBertPho2ResArch3, 2 = SpellBertPho2ResArch3Abla (models_abla.py:33-299) */
+  int32_t model_type;        /* 0 = SpellBert (BERT only), 1 = SpellBertPho2ResArch3, 2 = SpellBertPho2ResArch3Abla (models_abla.py:33-299),
+                              * 3 = SpellBertPho2ResArch4 (models.py:1023-1170): Arch3's tensors and schedule with the softmax gate; its
+                              * glyph table is the nn.Embedding [V, 1024] (models.py:1043,1134), so it needs num_fonts == 1, glyph_size == 32 */
   int32_t dtype;
   int32_t hidden, heads, intermediate, vocab, max_pos, type_vocab;
   int32_t bert_layers, pho_layers, out_layers;

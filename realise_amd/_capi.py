@@ -112,6 +112,8 @@ SYMBOLS = {
     "realise_gru_step_bwd": (_I, [_P, _I, C.POINTER(GruStep)]),
     "realise_gate_fwd": (_I, [_P, _I, C.POINTER(Gate)]),
     "realise_gate_bwd": (_I, [_P, _I, C.POINTER(Gate)]),
+    "realise_gate_softmax_fwd": (_I, [_P, _I, C.POINTER(Gate)]),
+    "realise_gate_softmax_bwd": (_I, [_P, _I, C.POINTER(Gate)]),
     "realise_sum_fuse_fwd": (_I, [_P, _I, _P, _P, _P, _P, _I, _I]),
     "realise_sum_fuse_bwd": (_I, [_P, _I, _P, _P, _P, _P, _I, _I, _P]),
     "realise_batchnorm_fwd": (_I, [_P, _I, _P, _I, _I, _P, _P, _F, _F, _P, _P, _P, _I, _I, _P, _P, _P, _P]),
@@ -211,7 +213,7 @@ def check(rc, what):
 
 def make_config(cfg, model_type, dtype, tie=True):
     c = Config()
-    c.model_type = {"bert": 0, "arch3": 1, "arch3-abla": 2}[model_type]
+    c.model_type = {"bert": 0, "arch3": 1, "arch3-abla": 2, "arch4": 3}[model_type]
     c.dtype = dtype
     c.hidden, c.heads, c.intermediate = cfg["hidden_size"], cfg["num_attention_heads"], cfg["intermediate_size"]
     c.vocab, c.max_pos, c.type_vocab = cfg["vocab_size"], cfg["max_position_embeddings"], cfg["type_vocab_size"]

@@ -52,8 +52,18 @@ class RealiseConfig(dict):
     def __setattr__(self, k, v):
         self[k] = v
 
-    def validate(self, glyph_branch=True):
-        """``glyph_branch``: the model being built has a glyph tower (a module passes what it knows; a bare config assumes one)."""
+    def validate(self, glyph_branch=True, model_type=None):
+        """``glyph_branch``: the model being built has a glyph tower (a module passes what it knows; a bare config assumes one).
+        ``model_type``: the module's ``model_type`` where one is being built ("arch4" has conditions of its own)."""
+        # SpellBertPho2ResArch4 hard-wires nn.Embedding(vocab_size, 1024) viewed as [N, 1, 32, 32] (models.py:1043,1134) whatever
+        # num_fonts says; a config that asks for anything else is refused instead of silently ignored
+        if model_type == "arch4":
+            if self["num_fonts"] != 1:
+                raise ValueError("SpellBertPho2ResArch4 reads one 32x32 glyph per character (char_images.weight [V, 1024]): it needs "
+                                 "num_fonts=1, got %d" % self["num_fonts"])
+            if self["glyph_size"] != 32:
+                raise ValueError("SpellBertPho2ResArch4 views its glyph table as [N, 1, 32, 32]: it needs glyph_size=32, got %d"
+                                 % self["glyph_size"])
         if self["hidden_size"] % self["num_attention_heads"] != 0:
             raise ValueError("hidden size must be a multiple of the head count (modeling_bert.py:199-202)")
         if self["hidden_size"] // self["num_attention_heads"] != 64:

@@ -302,6 +302,7 @@ template <typename T> GateArgs<T> to_gate(const realise_gate* g) {
   a.row_live = g->row_live; a.nsrc = g->nsrc == 0 ? 3 : g->nsrc;
   return a;
 }
+template <typename T> GateArgs<T> to_gate_softmax(const realise_gate* g) { GateArgs<T> a = to_gate<T>(g); a.softmax = true; return a; }
 template <typename T>
 int bn_fwd_t(hipStream_t st, const T* x, int P, int C, const float* gamma, const float* beta, float eps, float momentum, float* rmean, float* rvar,
              int64_t* nbt, int training, int relu, T* y, float* save_mean, float* save_rstd, float* scratch) {
@@ -342,6 +343,15 @@ int realise_gate_fwd(void* stream, int dtype, const realise_gate* a) {
 int realise_gate_bwd(void* stream, int dtype, const realise_gate* a) {
   if (!a) return RL_ERR_ARG;
   RL_BY_DTYPE(gate_bwd<bf16_t>((hipStream_t)stream, to_gate<bf16_t>(a)), gate_bwd<float>((hipStream_t)stream, to_gate<float>(a)));
+}
+// src/models.py:1139-1150 (SpellBertPho2ResArch4): softmax over the gate_net outputs; the struct is realise_gate as it is
+int realise_gate_softmax_fwd(void* stream, int dtype, const realise_gate* a) {
+  if (!a) return RL_ERR_ARG;
+  RL_BY_DTYPE(gate_fwd<bf16_t>((hipStream_t)stream, to_gate_softmax<bf16_t>(a)), gate_fwd<float>((hipStream_t)stream, to_gate_softmax<float>(a)));
+}
+int realise_gate_softmax_bwd(void* stream, int dtype, const realise_gate* a) {
+  if (!a) return RL_ERR_ARG;
+  RL_BY_DTYPE(gate_bwd<bf16_t>((hipStream_t)stream, to_gate_softmax<bf16_t>(a)), gate_bwd<float>((hipStream_t)stream, to_gate_softmax<float>(a)));
 }
 int realise_sum_fuse_fwd(void* stream, int dtype, const void* bert, const void* pho, const void* res, void* fused, int rows, int H) {
   hipStream_t st = (hipStream_t)stream;

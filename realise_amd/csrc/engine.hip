@@ -654,7 +654,10 @@ template <typename T> struct Engine : EngineBase {
       p.res_xhat = b.take(Tk * H * e); p.res_rstd = b.take(Tk * 4); p.res_h = b.take(Tk * H * e);
       tap("res_h", p.res_h, Tk * H);
       }
-      if (vr.gate) { p.gate_mean = b.take((int64_t)B * H * 4); p.gate_msum = b.take(B * 4 + 256); p.gate_g = b.take(Tk * 16); }
+      if (vr.gate) {
+        p.gate_mean = b.take((int64_t)B * H * 4); p.gate_msum = b.take(B * 4 + 256); p.gate_g = b.take(Tk * 16);
+        tap("gate.g", p.gate_g, Tk * 16 / (int64_t)sizeof(T));      // the saved [B*S][4] fp32 gates (what the reference's show_gate.py dumps)
+      }
       p.fused = b.take(Tk * H * e);
       tap("fused", p.fused, Tk * H);
       p.X1 = b.take(Tk * H * e);
@@ -1216,7 +1219,7 @@ template <typename T> struct Engine : EngineBase {
 
   GateArgs<T> gate_args() const {
     GateArgs<T> g;
-    g.B = pl.B; g.S = pl.S; g.H = H; g.nsrc = vr.nsrc;
+    g.B = pl.B; g.S = pl.S; g.H = H; g.nsrc = vr.nsrc; g.softmax = vr.gate_softmax;
     g.bert = wp<T>(pl.bert.layers.back().y2);
     g.pho = vr.pho ? wp<T>(pl.pho.layers.back().y2) : nullptr;
     g.res = vr.res ? wp<T>(pl.res_h) : nullptr;

@@ -69,28 +69,33 @@ struct Layout {
 inline int64_t align64(int64_t x) { return (x + 63) & ~(int64_t)63; }
 
 // What a configuration computes: SpellBert is the bert stack alone, SpellBertPho2ResArch3 has every branch, the ablation model
-// (model_type 2, src/models_abla.py:33-96) what its switches keep.  Every layout / engine decision reads this, not model_type.
+// (model_type 2, src/models_abla.py:33-96) what its switches keep, SpellBertPho2ResArch4 (model_type 3, models.py:1023-1170) every
+// branch with a softmax over the gates.  Every layout / engine decision reads this, not model_type.
 struct Variant {
-  bool arch = false;     // output_block behind a fusion of the branches (model_type 1, 2)
+  bool arch = false;     // output_block behind a fusion of the branches (model_type 1, 2, 3)
   bool pho = false;      // pinyin branch: pho_embeddings, pho_gru, pho_model
   bool res = false;      // glyph branch: glyph table, resnet, resnet_layernorm
   bool gate = false;     // gate fusion (gate_net); false on an arch model: sum fusion
   int nsrc = 1;          // fusion sources: bert + the present branches
+  bool gate_softmax = false;   // the gates are one softmax over the gate_net outputs (model_type 3, models.py:1143-1144), not sigmoids
 };
 inline Variant variant_of(const realise_config& c) {
   Variant v;
-  v.arch = c.model_type == 1 || c.model_type == 2;
+  v.arch = c.model_type == 1 || c.model_type == 2 || c.model_type == 3;
   if (!v.arch) return v;
   const bool abla = c.model_type == 2;
   v.pho = !abla || c.with_pho != 0;
   v.res = !abla || c.with_res != 0;
   v.gate = !abla || c.fusion == 0;
   v.nsrc = 1 + (v.pho ? 1 : 0) + (v.res ? 1 : 0);
+  v.gate_softmax = c.model_type == 3;
   return v;
 }
-// model_type 2 fields in range, sum fusion only with both branches (the reference's sum path adds None otherwise)
+// model_type 2 fields in range, sum fusion only with both branches (the reference's sum path adds None otherwise).  model_type 3 keeps
+// its glyph table as nn.Embedding(vocab, 1024) viewed as [N, 1, 32, 32] (models.py:1043,1134): one font, 32x32 glyphs, nothing else.
 inline bool variant_valid(const realise_config& c) {
-  if (c.model_type < 0 || c.model_type > 2) return false;
+  if (c.model_type < 0 || c.model_type > 3) return false;
+  if (c.model_type == 3) return c.num_fonts == 1 && c.glyph_size == 32;
   if (c.model_type != 2) return true;
   if ((c.with_pho != 0 && c.with_pho != 1) || (c.with_res != 0 && c.with_res != 1) || (c.fusion != 0 && c.fusion != 1)) return false;
   return c.fusion == 0 || (c.with_pho == 1 && c.with_res == 1);

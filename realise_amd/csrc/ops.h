@@ -134,7 +134,7 @@ template <typename T> struct GateArgs {
   const float* bias = nullptr;     // [3]
   float* mean = nullptr;           // [B][H]  (saved)
   float* msum = nullptr;           // [B]
-  float* g = nullptr;              // [B*S][4] sigmoid gates (saved)
+  float* g = nullptr;              // [B*S][4] gates (saved): sigmoids, or the softmax distribution with `softmax` set
   T* fused = nullptr;
   // backward
   const T* dfused = nullptr;
@@ -147,6 +147,9 @@ template <typename T> struct GateArgs {
   // number of gated sources (src/models_abla.py:239-275): bert, then pho and res where non-null (nsrc = 2: exactly one of them).
   // W is [nsrc][(nsrc + 1) H], bias [nsrc]; g / dz keep their row pitch of 4.  3 = SpellBertPho2ResArch3.
   int nsrc = 3;
+  // SpellBertPho2ResArch4 (models.py:1139-1150): the nsrc gates are one softmax over the gate_net outputs instead of nsrc sigmoids;
+  // backward dz_k = g_k (dg_k - sum_j g_j dg_j).  Everything else - the masked mean, W / dW layout, row_live - is the same.
+  bool softmax = false;
 };
 template <typename T> int gate_fwd(hipStream_t st, const GateArgs<T>& a);
 template <typename T> int gate_bwd(hipStream_t st, const GateArgs<T>& a);

@@ -1629,6 +1629,8 @@ __global__ void __launch_bounds__(256) gate_mean_kernel(GateArgs<T> a) {
 // The gate family is instantiated per number of sources NSRC (src/models_abla.py:239-275): bert, then pho and res where present.
 // W rows are (NSRC + 1) H wide, [src 0 | ... | src NSRC-1 | mean]; g / dz rows keep a pitch of 4 (unused slots hold 0).  NSRC = 3 is
 // SpellBertPho2ResArch3 and performs the same operations in the same order as the three-source kernels always did.
+// SM (GateArgs::softmax) selects the activation over the NSRC pre-activations z: false = independent sigmoids (models.py:843-848),
+// true = one softmax over them (SpellBertPho2ResArch4, models.py:1139-1150).  The sigmoid instantiations compile what they always did.
 template <typename T, int NSRC> __device__ __forceinline__ void gate_sources(const GateArgs<T>& a, const T* (&x)[NSRC]) {
   x[0] = a.bert;
   if constexpr (NSRC == 3) { x[1] = a.pho; x[2] = a.res; }
@@ -1640,7 +1642,7 @@ template <typename T, int NSRC> __device__ __forceinline__ void gate_grads(const
   if constexpr (NSRC == 2) d[1] = a.pho != nullptr ? a.dpho : a.dres;
 }
 
-template <typename T, int NSRC>
+template <typename T, int NSRC, bool SM>
 __global__ void __launch_bounds__(256) gate_fwd_kernel(GateArgs<T> a) {   // one wave per token
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + wave;
@@ -1677,7 +1679,19 @@ __global__ void __launch_bounds__(256) gate_fwd_kernel(GateArgs<T> a) {   // one
   }
   float gk[NSRC];
 #pragma unroll
-  for (int k = 0; k < NSRC; ++k) gk[k] = sigmoidf_(wave_sum(z[k]) + a.bias[k]);
+  for (int k = 0; k < NSRC; ++k) {
+    if constexpr (SM) gk[k] = wave_sum(z[k]) + a.bias[k];
+    else gk[k] = sigmoidf_(wave_sum(z[k]) + a.bias[k]);
+  }
+  if constexpr (SM) {      // softmax over the NSRC pre-activations, row maximum subtracted (torch.softmax): every exponent is <= 0
+    float zmax = gk[0], den = 0.f;
+#pragma unroll
+    for (int k = 1; k < NSRC; ++k) zmax = fmaxf(zmax, gk[k]);
+#pragma unroll
+    for (int k = 0; k < NSRC; ++k) { gk[k] = expf(gk[k] - zmax); den += gk[k]; }
+#pragma unroll
+    for (int k = 0; k < NSRC; ++k) gk[k] = gk[k] / den;
+  }
   if (lane == 0) {
 #pragma unroll
     for (int k = 0; k < 4; ++k) a.g[row * 4 + k] = k < NSRC ? gk[k < NSRC ? k : 0] : 0.f;
@@ -1703,10 +1717,18 @@ template <typename T> int gate_fwd(hipStream_t st, const GateArgs<T>& a) {
   if (!gate_args_ok(a)) return RL_ERR_ARG;
   hipLaunchKernelGGL((gate_mean_kernel<T>), dim3((a.H / 4 + 63) / 64, a.B), dim3(256), 0, st, a);
   const dim3 grid((a.B * a.S + 3) / 4);
-  switch (a.nsrc) {
-    case 3: hipLaunchKernelGGL((gate_fwd_kernel<T, 3>), grid, dim3(256), 0, st, a); break;
-    case 2: hipLaunchKernelGGL((gate_fwd_kernel<T, 2>), grid, dim3(256), 0, st, a); break;
-    default: hipLaunchKernelGGL((gate_fwd_kernel<T, 1>), grid, dim3(256), 0, st, a); break;
+  if (a.softmax) {
+    switch (a.nsrc) {
+      case 3: hipLaunchKernelGGL((gate_fwd_kernel<T, 3, true>), grid, dim3(256), 0, st, a); break;
+      case 2: hipLaunchKernelGGL((gate_fwd_kernel<T, 2, true>), grid, dim3(256), 0, st, a); break;
+      default: hipLaunchKernelGGL((gate_fwd_kernel<T, 1, true>), grid, dim3(256), 0, st, a); break;
+    }
+  } else {
+    switch (a.nsrc) {
+      case 3: hipLaunchKernelGGL((gate_fwd_kernel<T, 3, false>), grid, dim3(256), 0, st, a); break;
+      case 2: hipLaunchKernelGGL((gate_fwd_kernel<T, 2, false>), grid, dim3(256), 0, st, a); break;
+      default: hipLaunchKernelGGL((gate_fwd_kernel<T, 1, false>), grid, dim3(256), 0, st, a); break;
+    }
   }
   return RL_LAUNCH_CHECK();
 }
@@ -1714,7 +1736,7 @@ template int gate_fwd<bf16_t>(hipStream_t, const GateArgs<bf16_t>&);
 template int gate_fwd<float>(hipStream_t, const GateArgs<float>&);
 
 // backward, step 1 (per token): dz_k and the direct parts of the source gradients
-template <typename T, int NSRC>
+template <typename T, int NSRC, bool SM>
 __global__ void __launch_bounds__(256) gate_bwd_token_kernel(GateArgs<T> a) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + wave;
@@ -1759,7 +1781,15 @@ __global__ void __launch_bounds__(256) gate_bwd_token_kernel(GateArgs<T> a) {
 #pragma unroll
   for (int k = 0; k < NSRC; ++k) {
     gk[k] = a.g[row * 4 + k];
-    dz[k] = wave_sum(dg[k]) * gk[k] * (1.0f - gk[k]);
+    if constexpr (SM) dz[k] = wave_sum(dg[k]);
+    else dz[k] = wave_sum(dg[k]) * gk[k] * (1.0f - gk[k]);
+  }
+  if constexpr (SM) {      // softmax: dz_k = g_k (dg_k - sum_j g_j dg_j)
+    float dot = 0.f;
+#pragma unroll
+    for (int k = 0; k < NSRC; ++k) dot += gk[k] * dz[k];
+#pragma unroll
+    for (int k = 0; k < NSRC; ++k) dz[k] = gk[k] * (dz[k] - dot);
   }
   if (lane == 0) {
 #pragma unroll
@@ -1877,7 +1907,8 @@ __global__ void __launch_bounds__(256) gate_dw_kernel(GateArgs<T> a, int rows_pe
 }
 template <typename T, int NSRC> static void gate_bwd_launch(hipStream_t st, const GateArgs<T>& a) {
   const int T_ = a.B * a.S;
-  hipLaunchKernelGGL((gate_bwd_token_kernel<T, NSRC>), dim3((T_ + 3) / 4), dim3(256), 0, st, a);
+  if (a.softmax) hipLaunchKernelGGL((gate_bwd_token_kernel<T, NSRC, true>), dim3((T_ + 3) / 4), dim3(256), 0, st, a);
+  else hipLaunchKernelGGL((gate_bwd_token_kernel<T, NSRC, false>), dim3((T_ + 3) / 4), dim3(256), 0, st, a);
   hipLaunchKernelGGL((gate_bwd_mean_kernel<T, NSRC>), dim3((a.H / 4 + 63) / 64, a.B), dim3(256), 0, st, a);
   const int gx = (a.H + 127) / 128;
   int gy = 1024 / gx;

@@ -112,8 +112,14 @@ def tensor_specs(cfg, model_type="arch3"):
         specs.append((prefix + "pooler.dense.weight", (H, H), "normal"))
         specs.append((prefix + "pooler.dense.bias", (H,), "zeros"))
 
-    if model_type not in ("bert", "arch3", "arch3-abla"):
-        raise ValueError("model_type must be 'bert', 'arch3' or 'arch3-abla'")
+    if model_type not in ("bert", "arch3", "arch3-abla", "arch4"):
+        raise ValueError("model_type must be 'bert', 'arch3', 'arch3-abla' or 'arch4'")
+    # arch4 (src/models.py:1023-1170) is arch3 key for key with the one-font glyph table: nn.Embedding(vocab, 1024) is hard-wired there
+    if model_type == "arch4":
+        if cfg["num_fonts"] != 1:
+            raise ValueError("arch4 (SpellBertPho2ResArch4) keeps its glyphs in char_images.weight [V, 1024] (models.py:1043): it needs "
+                             "num_fonts=1, got %d" % cfg["num_fonts"])
+        model_type = "arch3"
     # arch3-abla (src/models_abla.py:33-96): the switches drop whole branches; (yes, yes, gate) is arch3 key for key
     arch = model_type != "bert"
     with_pho = not arch or model_type == "arch3" or cfg.get("with_pho", "yes") == "yes"

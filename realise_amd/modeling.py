@@ -62,7 +62,7 @@ class RealiseModule(nn.Module):
         if not isinstance(config, RealiseConfig):
             config = RealiseConfig(**{k: getattr(config, k) for k in RealiseConfig.DEFAULTS if hasattr(config, k)})
         self.config = config
-        config.validate(glyph_branch=self._has_glyph_branch())
+        config.validate(glyph_branch=self._has_glyph_branch(), model_type=self.model_type)
         self.vocab_size = config.vocab_size
         self.compute_dtype = compute_dtype or os.environ.get("REALISE_DTYPE", "bf16")
         if self.compute_dtype not in _DTYPES:
@@ -188,10 +188,14 @@ class RealiseModule(nn.Module):
         return self._arenas[0].device
 
     def _has_pinyin_branch(self):
-        return self.model_type == "arch3"
+        return self.model_type in ("arch3", "arch4")
 
     def _has_glyph_branch(self):
-        return self.model_type == "arch3"
+        return self.model_type in ("arch3", "arch4")
+
+    def _num_gates(self):
+        """number of fusion gates G (0: the model has no gate_net)"""
+        return 3 if self.model_type in ("arch3", "arch4") else 0
 
     # ------------------------------------------------------------------ reference-facing API
     def init_weights(self, seed=0, scheme="reference"):
@@ -480,6 +484,18 @@ class RealiseModule(nn.Module):
         off = ptr.value - self._ws.data_ptr()
         return self._ws[off:off + n.value * esz].view(_DTYPES[self.compute_dtype][1])
 
+    def gate_values(self):
+        """The fusion gates of the last forward as a [B, S, G] fp32 tensor (a copy): what the reference's show_gate.py dumps.  Column
+        order bert, pinyin, glyph (the present ones).  SpellBertPho2ResArch3: independent sigmoids; SpellBertPho2ResArch4: a distribution
+        over the modalities.  Rows a live-row step skipped (padding behind a sentence's last position) hold no meaningful value."""
+        G = self._num_gates()
+        if G == 0:
+            raise RuntimeError("this model has no fusion gate (model_type %r, fusion %r)" % (self.model_type, self.config.get("fusion")))
+        if self._engine is None or getattr(self, "_gate_gen", None) != self._fwd_gen:
+            raise RuntimeError("gate_values() reads the gates of the last forward; run one first")
+        B, S, _ = self._ws_key
+        return self.tap("gate.g").view(torch.float32).view(B, S, 4)[:, :, :G].clone()
+
     # ------------------------------------------------------------------ forward / backward
     def _dev(self, t):
         if not torch.is_tensor(t):
@@ -570,6 +586,7 @@ class RealiseModule(nn.Module):
             cb.logits_f32_out = wide.data_ptr()
         _capi.check(_capi.load().realise_engine_forward(self._engine, self._stream(), C.byref(cb)), "realise_engine_forward")
         self._last = keep
+        self._gate_gen = self._fwd_gen
         if no_logits:
             return (_EngineLoss.apply(self._anchor, loss, self), None)
         if wide is not None:

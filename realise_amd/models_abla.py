@@ -40,6 +40,9 @@ class SpellBertPho2ResArch3Abla(RealiseModule):
     def _has_glyph_branch(self):
         return self.config.get("with_res", "yes") == "yes"
 
+    def _num_gates(self):
+        return self.config["num_gates"] if self.config.get("fusion", "gate") == "gate" else 0
+
     def _require_glyph_branch(self, what):
         if not self._has_glyph_branch():
             raise RuntimeError("%s: this model has no glyph branch (with_res='no'; run.py:433 skips build_glyce_embed*)" % what)
