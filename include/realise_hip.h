@@ -108,6 +108,18 @@ int realise_layernorm_fwd(void* stream, int dtype, const void* x, const float* g
                           void* y, void* xhat, float* rstd, int rows, int H);
 int realise_layernorm_bwd(void* stream, int dtype, const void* dy, const void* xhat, const float* rstd,
                           const float* gamma, void* dx, float* dgamma, float* dbeta, int rows, int H);
+/* LayerNorm backward fused with the erf-GELU backward in front of it: the element-wise part of BertPredictionHeadTransform's
+ * backward (transformers/modeling_bert.py:419-431, dense -> erf GELU -> LayerNorm), between the decoder's data gradient and the
+ * transform's weight gradient.  For a row with upstream dy, saved xhat / rstd and the saved dense pre-activation z:
+ *   g = dy * gamma;  da = rstd * (g - mean(g) - xhat * mean(g * xhat));  dz = da * (Phi(z) + z * phi(z))   (fp32 statistics)
+ *   dgamma += sum_rows dy * xhat;  dbeta += sum_rows dy   (accumulated, fp32)
+ * dy / xhat / z / dz are `dtype`, H % 4 == 0 and H <= 1024 (anything else: REALISE_ERR_ARG, as realise_layernorm_bwd).
+ * n_rows_dev (nullable): a device-side row count - only rows [0, min(rows, *n_rows_dev)) are processed, dz rows beyond it are left
+ * as they are.  row_index (nullable, [rows] int32): xhat / rstd / z of row r are row row_index[r] of tensors with saved_rows rows
+ * (saved_rows == 0: rows) - the compacted gradient rows of a forward that saved every row. */
+int realise_layernorm_gelu_bwd(void* stream, int dtype, const void* dy, const void* xhat, const float* rstd, const void* z,
+                               const float* gamma, void* dz, float* dgamma, float* dbeta, int rows, int H,
+                               const int32_t* n_rows_dev, const int32_t* row_index, int saved_rows);
 /* CrossEntropyLoss over rows with loss_mask == 1 (src/models.py:862-869); dlogits nullable. */
 int realise_masked_ce(void* stream, int dtype, const void* logits, int64_t ld, const int64_t* labels,
                       const int64_t* loss_mask, int rows, int V, float* loss_out, float* count_scratch, void* dlogits);
@@ -202,7 +214,10 @@ int realise_argmax(void* stream, int dtype, const void* logits, int64_t ld, int 
 typedef struct {
   int32_t model_type;        /* 0 = SpellBert (BERT only), 1 = SpellBertPho2ResArch3, 2 = SpellBertPho2ResArch3Abla (models_abla.py:33-299),
                               * 3 = SpellBertPho2ResArch4 (models.py:1023-1170): Arch3's tensors and schedule with the softmax gate; its
-                              * glyph table is the nn.Embedding [V, 1024] (models.py:1043,1134), so it needs num_fonts == 1, glyph_size == 32 */
+                              * glyph table is the nn.Embedding [V, 1024] (models.py:1043,1134), so it needs num_fonts == 1, glyph_size == 32,
+                              * 4 = SpellBertPho2ResArch3MLM (models.py:874-1020): Arch3 with one font whose classifier is BertOnlyMLMHead
+                              * (cls.predictions.*: dense -> erf GELU -> LayerNorm -> untied decoder + bias); num_fonts == 1,
+                              * glyph_size == 32 and tie_classifier == 0 */
   int32_t dtype;
   int32_t hidden, heads, intermediate, vocab, max_pos, type_vocab;
   int32_t bert_layers, pho_layers, out_layers;

@@ -107,6 +107,7 @@ SYMBOLS = {
     "realise_mask_to_additive": (_I, [_P, _P, _P, _I]),
     "realise_layernorm_fwd": (_I, [_P, _I, _P, _P, _P, _F, _P, _P, _P, _I, _I]),
     "realise_layernorm_bwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _I, _I]),
+    "realise_layernorm_gelu_bwd": (_I, [_P, _I, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _I]),
     "realise_masked_ce": (_I, [_P, _I, _P, _L, _P, _P, _I, _I, _P, _P, _P]),
     "realise_gru_step_fwd": (_I, [_P, _I, C.POINTER(GruStep)]),
     "realise_gru_step_bwd": (_I, [_P, _I, C.POINTER(GruStep)]),
@@ -213,7 +214,7 @@ def check(rc, what):
 
 def make_config(cfg, model_type, dtype, tie=True):
     c = Config()
-    c.model_type = {"bert": 0, "arch3": 1, "arch3-abla": 2, "arch4": 3}[model_type]
+    c.model_type = {"bert": 0, "arch3": 1, "arch3-abla": 2, "arch4": 3, "arch3-mlm": 4}[model_type]
     c.dtype = dtype
     c.hidden, c.heads, c.intermediate = cfg["hidden_size"], cfg["num_attention_heads"], cfg["intermediate_size"]
     c.vocab, c.max_pos, c.type_vocab = cfg["vocab_size"], cfg["max_position_embeddings"], cfg["type_vocab_size"]

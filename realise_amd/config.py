@@ -54,7 +54,7 @@ class RealiseConfig(dict):
 
     def validate(self, glyph_branch=True, model_type=None):
         """``glyph_branch``: the model being built has a glyph tower (a module passes what it knows; a bare config assumes one).
-        ``model_type``: the module's ``model_type`` where one is being built ("arch4" has conditions of its own)."""
+        ``model_type``: the module's ``model_type`` where one is being built ("arch4" and "arch3-mlm" have conditions of their own)."""
         # SpellBertPho2ResArch4 hard-wires nn.Embedding(vocab_size, 1024) viewed as [N, 1, 32, 32] (models.py:1043,1134) whatever
         # num_fonts says; a config that asks for anything else is refused instead of silently ignored
         if model_type == "arch4":
@@ -63,6 +63,14 @@ class RealiseConfig(dict):
                                  "num_fonts=1, got %d" % self["num_fonts"])
             if self["glyph_size"] != 32:
                 raise ValueError("SpellBertPho2ResArch4 views its glyph table as [N, 1, 32, 32]: it needs glyph_size=32, got %d"
+                                 % self["glyph_size"])
+        # SpellBertPho2ResArch3MLM has the same hard-wired table (models.py:894,985)
+        if model_type == "arch3-mlm":
+            if self["num_fonts"] != 1:
+                raise ValueError("SpellBertPho2ResArch3MLM reads one 32x32 glyph per character (char_images.weight [V, 1024]): it needs "
+                                 "num_fonts=1, got %d" % self["num_fonts"])
+            if self["glyph_size"] != 32:
+                raise ValueError("SpellBertPho2ResArch3MLM views its glyph table as [N, 1, 32, 32]: it needs glyph_size=32, got %d"
                                  % self["glyph_size"])
         if self["hidden_size"] % self["num_attention_heads"] != 0:
             raise ValueError("hidden size must be a multiple of the head count (modeling_bert.py:199-202)")

@@ -248,6 +248,25 @@ int realise_layernorm_bwd(void* stream, int dtype, const void* dy, const void* x
   }
   return RL_ERR_ARG;
 }
+int realise_layernorm_gelu_bwd(void* stream, int dtype, const void* dy, const void* xhat, const float* rstd, const void* z, const float* gamma,
+                               void* dz, float* dgamma, float* dbeta, int rows, int H, const int32_t* n_rows_dev, const int32_t* row_index,
+                               int saved_rows) {
+  hipStream_t st = (hipStream_t)stream;
+  if (rows < 0 || saved_rows < 0) return RL_ERR_ARG;
+  if (dtype == REALISE_BF16) {
+    LnGeluBwdArgs<bf16_t> a; a.rows = rows; a.H = H; a.n_dev = n_rows_dev; a.idx = row_index; a.saved_rows = saved_rows;
+    a.dy = (const bf16_t*)dy; a.xhat = (const bf16_t*)xhat; a.rstd = rstd; a.z = (const bf16_t*)z; a.gamma = gamma; a.dz = (bf16_t*)dz;
+    a.dgamma = dgamma; a.dbeta = dbeta;
+    return ln_gelu_bwd<bf16_t>(st, a);
+  }
+  if (dtype == REALISE_F32) {
+    LnGeluBwdArgs<float> a; a.rows = rows; a.H = H; a.n_dev = n_rows_dev; a.idx = row_index; a.saved_rows = saved_rows;
+    a.dy = (const float*)dy; a.xhat = (const float*)xhat; a.rstd = rstd; a.z = (const float*)z; a.gamma = gamma; a.dz = (float*)dz;
+    a.dgamma = dgamma; a.dbeta = dbeta;
+    return ln_gelu_bwd<float>(st, a);
+  }
+  return RL_ERR_ARG;
+}
 int realise_layernorm_bwd_ex(void* stream, const void* dy, const void* xhat, const float* rstd, const float* gamma, void* dx, void* dx_drop,
                              uint32_t drop_seed, uint32_t drop_thresh, float drop_scale, float* dgamma, float* dbeta, float* slots, int rows, int H) {
   LnBwdArgs<bf16_t> a; a.rows = rows; a.H = H; a.dy = (const bf16_t*)dy; a.xhat = (const bf16_t*)xhat; a.rstd = rstd;

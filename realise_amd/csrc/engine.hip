@@ -136,6 +136,7 @@ template <typename T> struct Engine : EngineBase {
   std::vector<LayerSh> sh_bert, sh_pho, sh_out;
   BlockSh sh_blk[TOWER_MAX_BLOCKS];      // the first L.tower.nblocks are in use
   int64_t sh_cls_w = 0, sh_cls_wT = 0, sh_gru_hh = 0, sh_gru_hhT = 0, sh_glyph = 0;
+  int64_t sh_head_w = 0, sh_head_wT = 0;      // transform.dense of the MLM head (vr.mlm_head)
   int64_t shadow_total = 0;
   bool glyph_built = false, descs_built = false;
   int64_t sh_descs = 0, sh_fill = 0, sh_skip = 0;
@@ -174,6 +175,9 @@ template <typename T> struct Engine : EngineBase {
     std::vector<std::pair<int64_t, int64_t>> zero_once;      // (offset, bytes): self-cleaning accumulators, zero-filled when the plan is installed
     int64_t gru_dh, gru_dgi, gru_dgh, gru_onehot, gru_dtable;
     int64_t r_dout, r_dc2, r_dcs, r_dh1, r_dc1, r_dx;
+    // MLM head (vr.mlm_head; taken last: no other offset moves): saved dense pre-activation, GELU output / LayerNorm xhat (in place), rstd,
+    // LayerNorm output = the decoder's input; gathered head input rows, the fused backward's dz, the identity row map of the slab fold
+    int64_t head_z = 0, head_x = 0, head_rstd = 0, head_y = 0, head_xc = 0, head_dz = 0, head_ident = 0;
   } pl;
   std::map<std::string, std::pair<int64_t, int64_t>> taps;   // name -> (byte offset, numel)
 
@@ -324,6 +328,7 @@ template <typename T> struct Engine : EngineBase {
     sh_descs = b.take(256 * (int64_t)sizeof(CastDesc));      // device table for the one-launch refresh of the Linear weights
     sh_fill = b.take(FILL_MAX * (int64_t)sizeof(FillChunk));  // chunk table of the fresh-gradient zero fill
     sh_skip = b.take(ACHUNK_MAX * (int64_t)sizeof(FillChunk));   // chunk list of the parameters the tiled AdamW does NOT own (adamw_step)
+    if (vr.mlm_head) { sh_head_w = b.take((int64_t)H * H * e); sh_head_wT = b.take((int64_t)H * H * e); }      // (last: every other offset stays put)
     shadow_total = b.off;
   }
 
@@ -356,6 +361,7 @@ template <typename T> struct Engine : EngineBase {
     n_descs_a = (int)d.size(); desc_tiles_a = tiles;
     tiles = 0;                                   // second group: its own launch, tile ids restart
     add(L.cls_w, V, H, sh_cls_w, sh_cls_wT, Vp);
+    if (vr.mlm_head) add(L.head_w, H, H, sh_head_w, sh_head_wT);      // next to its decoder: the pipelined sweep steps the two in one piece
     if (vr.pho) add_stack(L.pho, sh_pho);
     if (vr.arch) add_stack(L.outb, sh_out);
     if (vr.pho) add(L.gru_w_hh, 3 * H, H, sh_gru_hh, sh_gru_hhT);
@@ -501,22 +507,23 @@ template <typename T> struct Engine : EngineBase {
         return adamw_cast_multi<T>(side, dd + a, b - a, tile_begin(b, false) - tile_begin(a, false), P, G, m, v, group_of_block, gs, norm_sq, max_norm, tile_begin(a, false));
       };
       const int nb = n_descs - n_descs_a;                      // group B: [0] = tied word table / classifier, then pinyin / output stacks, GRU
+      const int nc = vr.mlm_head ? 2 : 1;                      // the classifier's piece: [0], and with an MLM head [1] = its transform.dense
       opt_groups = (Lb + 1) / 2;
       RL_TRY(adamw_chunks(side, P, G, m, v, (const FillChunk*)(sh + sh_skip), n_achunks, group_of_block, gs, norm_sq, max_norm));
-      RL_TRY(adamw_cast_multi<T>(side, dd + n_descs_a, 1, tile_begin(1, true), P, G, m, v, group_of_block, gs, norm_sq, max_norm, 0));
+      RL_TRY(adamw_cast_multi<T>(side, dd + n_descs_a, nc, tile_begin(nc, true), P, G, m, v, group_of_block, gs, norm_sq, max_norm, 0));
       RL_TRY(bert_layers(0, 2));
       if (hipEventRecord(ev_opt[0], side) != hipSuccess) return RL_ERR_LAUNCH;
       for (int g = 1; g < opt_groups; ++g) {
         RL_TRY(bert_layers(2 * g, 2 * g + 2));
         if (hipEventRecord(ev_opt[g], side) != hipSuccess) return RL_ERR_LAUNCH;
-        if (g == 1 && nb > 1) {
-          RL_TRY(adamw_cast_multi<T>(side, dd + n_descs_a + 1, nb - 1, desc_tiles - tile_begin(1, true), P, G, m, v, group_of_block, gs, norm_sq, max_norm, tile_begin(1, true)));
+        if (g == 1 && nb > nc) {
+          RL_TRY(adamw_cast_multi<T>(side, dd + n_descs_a + nc, nb - nc, desc_tiles - tile_begin(nc, true), P, G, m, v, group_of_block, gs, norm_sq, max_norm, tile_begin(nc, true)));
           if (hipEventRecord(ev_opt[opt_groups], side) != hipSuccess) return RL_ERR_LAUNCH;
         }
       }
-      if (opt_groups < 2 || nb <= 1) {                          // (a one- or two-layer stack, or no other stacks: the last event still has to exist)
-        if (opt_groups < 2 && nb > 1)
-          RL_TRY(adamw_cast_multi<T>(side, dd + n_descs_a + 1, nb - 1, desc_tiles - tile_begin(1, true), P, G, m, v, group_of_block, gs, norm_sq, max_norm, tile_begin(1, true)));
+      if (opt_groups < 2 || nb <= nc) {                         // (a one- or two-layer stack, or no other stacks: the last event still has to exist)
+        if (opt_groups < 2 && nb > nc)
+          RL_TRY(adamw_cast_multi<T>(side, dd + n_descs_a + nc, nb - nc, desc_tiles - tile_begin(nc, true), P, G, m, v, group_of_block, gs, norm_sq, max_norm, tile_begin(nc, true)));
         if (hipEventRecord(ev_opt[opt_groups], side) != hipSuccess) return RL_ERR_LAUNCH;
       }
       opt_pending = true;
@@ -673,6 +680,12 @@ template <typename T> struct Engine : EngineBase {
         p.r_dout = b.take(big); p.r_dc2 = b.take(big); p.r_dcs = b.take(big); p.r_dh1 = b.take(big); p.r_dc1 = b.take(big);
         p.r_dx = b.take(big);
       }
+    }
+    if (vr.mlm_head && !glyph_only) {
+      p.head_z = b.take(Tk * H * e); p.head_x = b.take(Tk * H * e); p.head_rstd = b.take(Tk * 4); p.head_y = b.take(Tk * H * e);
+      p.head_xc = b.take(Tk * H * e); p.head_dz = b.take(Tk * H * e); p.head_ident = b.take(Tk * 4);
+      tap("head.z", p.head_z, Tk * H); tap("head.y", p.head_y, Tk * H);
+      tap("head.d_in", p.gA, Tk * H);      // d(head input) = d(top hidden) after stage_head
     }
     p.total = b.off;
     return p;
@@ -1252,7 +1265,28 @@ template <typename T> struct Engine : EngineBase {
     // leaves the activation rows of padding tokens as they are - what they hold must be finite wherever a later pass multiplies it by
     // an exact zero (masked mean, gate gradients).
     if (hipMemsetAsync(ws, 0, (size_t)pl.total, st) != hipSuccess) return RL_ERR_LAUNCH;
+    if (vr.mlm_head && pl.head_ident != 0) {      // row j -> j: the slab fold of the decoder's split-K data gradient keeps the compacted rows where they are
+      ident_keep.emplace_back((size_t)pl.B * pl.S);      // (a vector per install: stays alive while its upload is in flight)
+      std::vector<int>& id = ident_keep.back();
+      for (size_t i = 0; i < id.size(); ++i) id[i] = (int)i;
+      if (hipMemcpyAsync(ws + pl.head_ident, id.data(), id.size() * sizeof(int), hipMemcpyHostToDevice, st) != hipSuccess) return RL_ERR_LAUNCH;
+    }
     return RL_OK;
+  }
+  std::vector<std::vector<int>> ident_keep;
+  // ---------------------------------------------------------------- MLM head (vr.mlm_head; modeling_bert.py:419-462)
+  // transform of `rows` rows of x (n_dev, nullable: a device-side count of the rows that matter): dense + erf GELU in the GEMM's epilogue,
+  // then LayerNorm -> pl.head_y, the decoder's input.  A forward a backward can follow keeps the pre-activation and xhat (in place).
+  // The LayerNorm takes no device count: it also normalises the stale (finite) rows behind *n_dev, which nothing reads.
+  const T* dec_in_bwd = nullptr;           // the decoder's input rows / the head's input rows as the backward's weight gradients read them
+  const T* head_in_bwd = nullptr;
+  const int* head_idx = nullptr;           // compacted gradient rows of a forward that saved every row: compact row r = saved row head_idx[r]
+  int head_forward(hipStream_t st, const T* x, int rows, const int* n_dev) {
+    EpiParams<T> ep; ep.mode = EPI_GELU; ep.out = wp<T>(pl.head_x); ep.out2 = bwd_follows() ? wp<T>(pl.head_z) : nullptr; ep.ldo = H; ep.bias = pp(L.head_b);
+    RL_TRY(gemm_nt<T>(st, x, H, sp<T>(sh_head_w), H, rows, H, H, ep, n_dev));
+    LnFwdArgs<T> ln; ln.rows = rows; ln.H = H; ln.x = wp<T>(pl.head_x); ln.gamma = pp(L.head_ln_g); ln.beta = pp(L.head_ln_b); ln.eps = cfg.ln_eps;
+    ln.y = wp<T>(pl.head_y); ln.xhat = bwd_follows() ? wp<T>(pl.head_x) : nullptr; ln.rstd = wp<float>(pl.head_rstd);
+    return ln_fwd<T>(st, ln);
   }
   // the size conditions of a live-row step (g_live_rows): bf16 with the 16-row block lists, whole 64-row tiles in every GEMM dimension,
   // 32-bit byte offsets into the widest activation
@@ -1364,14 +1398,28 @@ template <typename T> struct Engine : EngineBase {
       cc.phase = 1;
       RL_TRY(ce_loss<T>(st, nullptr, Vp, b.tgt_idx, b.loss_masks, Tk, V, b.loss_out, wp<float>(pl.count), wp<T>(pl.dlogits),
                         wp<float>(pl.loss_internal), Vp, cc));
+      const T* dec_c = wp<T>(pl.cls_xc);
+      if (vr.mlm_head) {      // the transform over the rows that enter the loss only
+        RL_TRY(gather_rows<T>(st, cls_in, wp<int>(pl.cls_act), wp<int>(pl.cls_nact), Tk, H, wp<T>(pl.head_xc)));
+        RL_TRY(head_forward(st, wp<T>(pl.head_xc), Tk, wp<int>(pl.cls_nact)));
+        dec_c = wp<T>(pl.head_y);
+        dec_in_bwd = dec_c; head_in_bwd = wp<T>(pl.head_xc); head_idx = nullptr;
+      } else {
       RL_TRY(gather_rows<T>(st, cls_in, wp<int>(pl.cls_act), wp<int>(pl.cls_nact), Tk, H, wp<T>(pl.cls_xc)));
+      }
       EpiParams<T> ep; ep.mode = EPI_STORE; ep.out = wp<T>(pl.dlogits); ep.ldo = Vp; ep.bias = pp(L.cls_b);
-      RL_TRY(gemm_nt<T>(st, wp<T>(pl.cls_xc), H, sp<T>(sh_cls_w), H, Tk, V, H, ep, wp<int>(pl.cls_nact)));
+      RL_TRY(gemm_nt<T>(st, dec_c, H, sp<T>(sh_cls_w), H, Tk, V, H, ep, wp<int>(pl.cls_nact)));
       cc.phase = 2; cc.logits_compact = 1;
       RL_TRY(ce_loss<T>(st, wp<T>(pl.dlogits), Vp, b.tgt_idx, b.loss_masks, Tk, V, b.loss_out, wp<float>(pl.count), wp<T>(pl.dlogits),
                         wp<float>(pl.loss_internal), Vp, cc));
       have_fwd = b.training != 0;
       return RL_OK;
+    }
+    const T* head_in = cls_in;
+    if (vr.mlm_head) {      // logits of every row: the transform over every row; the decoder reads its output
+      RL_TRY(head_forward(st, cls_in, Tk, nullptr));
+      cls_in = wp<T>(pl.head_y);
+      dec_in_bwd = cls_in; head_in_bwd = head_in; head_idx = nullptr;
     }
     {  // tied vocabulary classifier (models.py:859)
       EpiParams<T> ep; ep.mode = EPI_STORE; ep.out = (T*)b.logits_out; ep.ldo = V; ep.bias = pp(L.cls_b);
@@ -1400,6 +1448,10 @@ template <typename T> struct Engine : EngineBase {
       RL_TRY(ce_loss<T>(st, (const T*)b.logits_out, V, b.tgt_idx, b.loss_masks, Tk, V, b.loss_out, wp<float>(pl.count),
                         b.want_dlogits ? wp<T>(pl.dlogits) : nullptr, wp<float>(pl.loss_internal), Vp, cc));
       if (cls_compact) RL_TRY(gather_rows<T>(st, cls_in, wp<int>(pl.cls_act), wp<int>(pl.cls_nact), Tk, H, wp<T>(pl.cls_xc)));
+      if (cls_compact && vr.mlm_head) {      // the transform's weight gradient reads its input rows compacted; the saved tensors stay where they are
+        RL_TRY(gather_rows<T>(st, head_in, wp<int>(pl.cls_act), wp<int>(pl.cls_nact), Tk, H, wp<T>(pl.head_xc)));
+        dec_in_bwd = wp<T>(pl.cls_xc); head_in_bwd = wp<T>(pl.head_xc); head_idx = wp<int>(pl.cls_act);
+      }
     }
     have_fwd = b.training && b.tgt_idx != nullptr && b.want_dlogits;
     return RL_OK;
@@ -1497,6 +1549,7 @@ template <typename T> struct Engine : EngineBase {
     const DropParams dfin = site(5000, cfg.hidden_dropout);
     const T* top = vr.arch ? wp<T>(pl.outb.layers.back().y2) : wp<T>(pl.bert.layers.back().y2);
     const T* cls_in = dfin.thresh ? wp<T>(pl.out_d) : top;
+    if (vr.mlm_head) return stage_head_mlm(la, dfin);
     if (cls_compact) {
       const int* n_act = wp<int>(pl.cls_nact);
       { TnEpi te; te.slab = wp<float>(la.sc->tn_slab); te.slab_elems = TN_SLAB_ELEMS; te.colsum = gp(L.cls_b); te.out = gp(L.cls_w); te.ldo = H;
@@ -1517,6 +1570,53 @@ template <typename T> struct Engine : EngineBase {
     { EpiParams<T> ep; ep.mode = EPI_STORE; ep.out = gA; ep.ldo = H;
       RL_TRY(gemm_nt<T>(st, dl, Vp, sp<T>(sh_cls_wT), Vp, Tk, H, Vp, ep)); }      // K = Vp: the padding columns are exact zeros on both sides
     if (loss_grad != nullptr) RL_TRY(scale_by_dev<T>(st, gA, (int64_t)Tk * H, loss_grad));      // (dense fallback: a pass over [T, H], not over the logits)
+    if (dfin.thresh) RL_TRY(dropout_apply<T>(st, gA, gA, Tk, H, dfin));
+    return RL_OK;
+  }
+
+  // The MLM head's backward (modeling_bert.py:419-462): decoder weight / bias / data gradient as the plain classifier's, then ONE row pass for
+  // LayerNorm' and GELU' (ln_gelu_bwd), the transform's weight gradient with its bias gradient as the column sum, its data gradient, and
+  // the scatter / final-dropout map.  The loss-gradient scalar reaches the decoder's weight and bias gradients in their epilogue, as
+  // before, and everything behind the decoder through the decoder's DATA gradient, which is scaled once where it is stored: dz, the
+  // transform's four gradients and d(top hidden) are linear in it and get no factor of their own.
+  int stage_head_mlm(const Lane& la, const DropParams& dfin) {
+    const hipStream_t st = la.st;
+    const int Tk = pl.B * pl.S;
+    const T* dl = wp<T>(pl.dlogits);
+    T* gA = wp<T>(pl.gA);
+    T* dy = wp<T>(pl.cls_gc);
+    T* dz = wp<T>(pl.head_dz);
+    const int* n_act = cls_compact ? wp<int>(pl.cls_nact) : nullptr;
+    { TnEpi te; te.slab = wp<float>(la.sc->tn_slab); te.slab_elems = TN_SLAB_ELEMS; te.colsum = gp(L.cls_b); te.out = gp(L.cls_w); te.ldo = H;
+      te.alpha_dev = loss_grad;
+      RL_TRY(gemm_tn<T>(st, dl, Vp, dec_in_bwd, H, Tk, V, H, te, n_act)); }
+    bool have_dy = false;
+    if constexpr (sizeof(T) == 2) {      // split-K over the vocabulary, the planes folded in plane order (and scaled) into the compacted rows
+      const int ns = g_cls_splitk;
+      if (cls_compact && ns >= 2 && pl.cls_slab != 0 && Tk >= 1024 &&
+          gemm_nt8_splitk(st, dl, Vp, sp<T>(sh_cls_wT), Vp, Tk, H, Vp, ns, wp<float>(pl.cls_slab), (int64_t)Tk * H, n_act) == RL_OK) {
+        RL_TRY(scatter_rows_drop_slab<T>(st, wp<float>(pl.cls_slab), ns, (int64_t)Tk * H, wp<int>(pl.head_ident), Tk, H, dy, DropParams(), loss_grad));
+        have_dy = true;
+      }
+    }
+    if (!have_dy) {
+      EpiParams<T> ep; ep.mode = EPI_STORE; ep.out = dy; ep.ldo = H; ep.m_dev = n_act;
+      RL_TRY(gemm_nt<T>(st, dl, Vp, sp<T>(sh_cls_wT), Vp, Tk, H, Vp, ep));      // K = Vp: the padding columns are exact zeros on both sides
+      if (loss_grad != nullptr) RL_TRY(scale_by_dev<T>(st, dy, (int64_t)Tk * H, loss_grad));
+    }
+    { LnGeluBwdArgs<T> a; a.rows = Tk; a.H = H; a.n_dev = n_act; a.idx = head_idx; a.saved_rows = Tk;
+      a.dy = dy; a.xhat = wp<T>(pl.head_x); a.rstd = wp<float>(pl.head_rstd); a.z = wp<T>(pl.head_z); a.gamma = pp(L.head_ln_g); a.dz = dz;
+      a.dgamma = gp(L.head_ln_g); a.dbeta = gp(L.head_ln_b); a.slots = ln_region(la, LN_FOLD_MAX);
+      RL_TRY(ln_gelu_bwd<T>(st, a)); }
+    { TnEpi te; te.slab = wp<float>(la.sc->tn_slab); te.slab_elems = TN_SLAB_ELEMS; te.colsum = gp(L.head_b); te.out = gp(L.head_w); te.ldo = H;
+      RL_TRY(gemm_tn<T>(st, dz, H, head_in_bwd, H, Tk, H, H, te, n_act)); }
+    if (cls_compact) {
+      EpiParams<T> ep; ep.mode = EPI_STORE; ep.out = dy; ep.ldo = H; ep.m_dev = n_act;      // (dy is consumed: its buffer takes d(head input), compacted)
+      RL_TRY(gemm_nt<T>(st, dz, H, sp<T>(sh_head_wT), H, Tk, H, H, ep));
+      return scatter_rows_drop<T>(st, dy, wp<int>(pl.cls_inv), Tk, H, gA, dfin, nullptr);      // rows outside the loss: zero; + the final dropout's map
+    }
+    { EpiParams<T> ep; ep.mode = EPI_STORE; ep.out = gA; ep.ldo = H;
+      RL_TRY(gemm_nt<T>(st, dz, H, sp<T>(sh_head_wT), H, Tk, H, H, ep)); }
     if (dfin.thresh) RL_TRY(dropout_apply<T>(st, gA, gA, Tk, H, dfin));
     return RL_OK;
   }

@@ -58,6 +58,7 @@ struct Layout {
   std::vector<std::pair<int64_t, int64_t>> buckets;    // [begin, end) in AR_TRAIN, backward completion order
   StackOff bert, pho, outb;
   int64_t cls_w = -1, cls_b = -1;
+  int64_t head_w = -1, head_b = -1, head_ln_g = -1, head_ln_b = -1;   // BertPredictionHeadTransform (Variant::mlm_head); cls_w / cls_b are then its decoder
   int64_t pho_emb = -1, gru_w_ih = -1, gru_w_hh = -1, gru_b_ih = -1, gru_b_hh = -1;
   int64_t res_ln_g = -1, res_ln_b = -1, gate_w = -1, gate_b = -1;
   int64_t glyph = -1;                                  // AR_FROZEN
@@ -70,18 +71,21 @@ inline int64_t align64(int64_t x) { return (x + 63) & ~(int64_t)63; }
 
 // What a configuration computes: SpellBert is the bert stack alone, SpellBertPho2ResArch3 has every branch, the ablation model
 // (model_type 2, src/models_abla.py:33-96) what its switches keep, SpellBertPho2ResArch4 (model_type 3, models.py:1023-1170) every
-// branch with a softmax over the gates.  Every layout / engine decision reads this, not model_type.
+// branch with a softmax over the gates, SpellBertPho2ResArch3MLM (model_type 4, models.py:874-1020) Arch3 with BertOnlyMLMHead as
+// its classifier.  Every layout / engine decision reads this, not model_type.
 struct Variant {
-  bool arch = false;     // output_block behind a fusion of the branches (model_type 1, 2, 3)
+  bool arch = false;     // output_block behind a fusion of the branches (model_type 1, 2, 3, 4)
   bool pho = false;      // pinyin branch: pho_embeddings, pho_gru, pho_model
   bool res = false;      // glyph branch: glyph table, resnet, resnet_layernorm
   bool gate = false;     // gate fusion (gate_net); false on an arch model: sum fusion
   int nsrc = 1;          // fusion sources: bert + the present branches
   bool gate_softmax = false;   // the gates are one softmax over the gate_net outputs (model_type 3, models.py:1143-1144), not sigmoids
+  bool mlm_head = false;       // the classifier is BertOnlyMLMHead (model_type 4, modeling_bert.py:419-462): dense -> erf GELU -> LayerNorm in
+                               // front of an untied decoder [V, H] + bias; keys cls.predictions.*, no classifier.*
 };
 inline Variant variant_of(const realise_config& c) {
   Variant v;
-  v.arch = c.model_type == 1 || c.model_type == 2 || c.model_type == 3;
+  v.arch = c.model_type == 1 || c.model_type == 2 || c.model_type == 3 || c.model_type == 4;
   if (!v.arch) return v;
   const bool abla = c.model_type == 2;
   v.pho = !abla || c.with_pho != 0;
@@ -89,13 +93,16 @@ inline Variant variant_of(const realise_config& c) {
   v.gate = !abla || c.fusion == 0;
   v.nsrc = 1 + (v.pho ? 1 : 0) + (v.res ? 1 : 0);
   v.gate_softmax = c.model_type == 3;
+  v.mlm_head = c.model_type == 4;
   return v;
 }
 // model_type 2 fields in range, sum fusion only with both branches (the reference's sum path adds None otherwise).  model_type 3 keeps
 // its glyph table as nn.Embedding(vocab, 1024) viewed as [N, 1, 32, 32] (models.py:1043,1134): one font, 32x32 glyphs, nothing else.
+// model_type 4 has the same table (models.py:894,985) and a decoder of its own (tie_cls_weight is a `pass`, models.py:915-917): untied only.
 inline bool variant_valid(const realise_config& c) {
-  if (c.model_type < 0 || c.model_type > 3) return false;
+  if (c.model_type < 0 || c.model_type > 4) return false;
   if (c.model_type == 3) return c.num_fonts == 1 && c.glyph_size == 32;
+  if (c.model_type == 4) return c.num_fonts == 1 && c.glyph_size == 32 && c.tie_classifier == 0;
   if (c.model_type != 2) return true;
   if ((c.with_pho != 0 && c.with_pho != 1) || (c.with_res != 0 && c.with_res != 1) || (c.fusion != 0 && c.fusion != 1)) return false;
   return c.fusion == 0 || (c.with_pho == 1 && c.with_res == 1);
@@ -184,8 +191,18 @@ inline Layout build_layout(const realise_config& c) {
   int64_t begin = 0;
   L.bert.layers.resize(c.bert_layers);
   // ---- bucket 0: classifier bias (+ untied weight), output_block
-  L.cls_b = add(AR_TRAIN, "classifier.bias", {V});
-  if (!c.tie_classifier) L.cls_w = add(AR_TRAIN, "classifier.weight", {V, H});
+  if (vr.mlm_head) {
+    // BertOnlyMLMHead (modeling_bert.py:419-462) in backward completion order: decoder bias and weight, the transform's LayerNorm, its dense
+    L.cls_b = add(AR_TRAIN, "cls.predictions.bias", {V});
+    L.cls_w = add(AR_TRAIN, "cls.predictions.decoder.weight", {V, H});
+    L.head_ln_g = add(AR_TRAIN, "cls.predictions.transform.LayerNorm.weight", {H});
+    L.head_ln_b = add(AR_TRAIN, "cls.predictions.transform.LayerNorm.bias", {H});
+    L.head_w = add(AR_TRAIN, "cls.predictions.transform.dense.weight", {H, H});
+    L.head_b = add(AR_TRAIN, "cls.predictions.transform.dense.bias", {H});
+  } else {
+    L.cls_b = add(AR_TRAIN, "classifier.bias", {V});
+    if (!c.tie_classifier) L.cls_w = add(AR_TRAIN, "classifier.weight", {V, H});
+  }
   if (vr.arch) {
     L.outb.layers.resize(c.out_layers);
     add_layers_desc(L.outb, "output_block.", c.out_layers - 1, 0);
@@ -246,7 +263,7 @@ inline Layout build_layout(const realise_config& c) {
   // ---- last bucket: bert embeddings (word table last: its gradient is complete last)
   add_emb(L.bert, "bert.", true);
   close_bucket(begin);
-  if (c.tie_classifier) {
+  if (c.tie_classifier && !vr.mlm_head) {
     L.cls_w = L.bert.word;
     alias("classifier.weight", AR_TRAIN, L.bert.word, {V, H});
   }

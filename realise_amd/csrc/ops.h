@@ -89,6 +89,25 @@ constexpr int LN_FOLD_MAX = 8;
 struct LnFoldSite { const float* recs; int nrec; float* dgamma; float* dbeta; };
 struct LnFoldSites { int n = 0; int H = 0; LnFoldSite s[LN_FOLD_MAX]; };
 int ln_fold_multi(hipStream_t st, const LnFoldSites& sites);
+// LayerNorm backward fused with the erf-GELU backward in front of it (BertPredictionHeadTransform, modeling_bert.py:419-431: dense ->
+// GELU -> LayerNorm): dz = LayerNorm'(dy) * gelu'(z), where z is the dense pre-activation the forward saved; dgamma / dbeta as ln_bwd.
+// One pass over the rows: no d(GELU output) matrix is written and read back.
+template <typename T> struct LnGeluBwdArgs {
+  int rows = 0, H = 0;
+  const int* n_dev = nullptr;      // optional device-side row count: only rows [0, min(rows, *n_dev)) are processed, the others left untouched
+  const int* idx = nullptr;        // optional: xhat / rstd / z of row r are row idx[r] of the saved tensors (clamped into [0, saved_rows))
+  int saved_rows = 0;              // rows of the saved tensors (0: rows)
+  const T* dy = nullptr;
+  const T* xhat = nullptr;
+  const float* rstd = nullptr;
+  const T* z = nullptr;
+  const float* gamma = nullptr;
+  T* dz = nullptr;
+  float* dgamma = nullptr;         // accumulated
+  float* dbeta = nullptr;
+  float* slots = nullptr;          // optional scratch of LN_SLOT_BYTES (per-workgroup records, fixed-order fold); nullptr: atomics
+};
+template <typename T> int ln_gelu_bwd(hipStream_t st, const LnGeluBwdArgs<T>& a);
 void set_ln_fast(int on);            // 1 (default): bf16 rows of 256 / 512 / 768 / 1024 columns take the half-wave-per-row kernels (16-byte accesses)
 void set_ln_v2(int on);              // 1 (default, round 5): DPP row reductions + ln_bwd16v2_kernel; 0: the round-4 kernels
 void set_ln_bwd_blocks(int n);       // workgroups of the fast LayerNorm backward (default 512)

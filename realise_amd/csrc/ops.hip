@@ -731,6 +731,262 @@ template int ln_bwd<bf16_t>(hipStream_t, const LnBwdArgs<bf16_t>&);
 template int ln_bwd<float>(hipStream_t, const LnBwdArgs<float>&);
 
 // ---------------------------------------------------------------------------------------------
+// LayerNorm backward fused with the erf-GELU backward (BertPredictionHeadTransform, modeling_bert.py:419-431): between the decoder's
+// data gradient and the transform's weight gradient there is no GEMM to carry an epilogue, so the two element-wise backwards are one
+// row pass:  g = dy * gamma;  da = rstd (g - mean(g) - xhat mean(g xhat));  dz = da * gelu'(z);  dgamma += dy xhat;  dbeta += dy.
+// Generic form (fp32 parity mode, any H % 4 == 0 up to 1024): a wave per row, grid-stride.
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ int lng_rows(const int rows, const int* n_dev) {
+  if (n_dev == nullptr) return rows;
+  const int n = *n_dev;
+  return n < 0 ? 0 : (n < rows ? n : rows);
+}
+template <typename T, int NV>
+__global__ void __launch_bounds__(256) ln_gelu_bwd_kernel(LnGeluBwdArgs<T> a) {
+  __shared__ float red[2][4][NV * 256];
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int H = a.H;
+  const int n = lng_rows(a.rows, a.n_dev);
+  floatx4 dg[NV], db[NV], gm[NV];
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    dg[i] = floatx4{0.f, 0.f, 0.f, 0.f};
+    db[i] = floatx4{0.f, 0.f, 0.f, 0.f};
+    const int c = (i * 64 + lane) * 4;
+    gm[i] = c < H ? *(const floatx4*)(a.gamma + c) : floatx4{0.f, 0.f, 0.f, 0.f};
+  }
+  for (int row = blockIdx.x * 4 + wave; row < n; row += gridDim.x * 4) {
+    int srow = a.idx != nullptr ? a.idx[row] : row;
+    srow = srow < 0 ? 0 : (srow >= a.saved_rows ? a.saved_rows - 1 : srow);
+    floatx4 dy[NV], xh[NV], z[NV];
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int c = (i * 64 + lane) * 4;
+      dy[i] = xh[i] = z[i] = floatx4{0.f, 0.f, 0.f, 0.f};
+      if (c < H) {
+        dy[i] = load4<T>(a.dy + (int64_t)row * H + c);
+        xh[i] = load4<T>(a.xhat + (int64_t)srow * H + c);
+        z[i] = load4<T>(a.z + (int64_t)srow * H + c);
+#pragma unroll
+        for (int j = 0; j < 4; ++j) {
+          const float t = dy[i][j] * gm[i][j];
+          s1 += t;
+          s2 += t * xh[i][j];
+          dg[i][j] += dy[i][j] * xh[i][j];
+          db[i][j] += dy[i][j];
+        }
+      }
+    }
+    s1 = wave_sum(s1) / (float)H;
+    s2 = wave_sum(s2) / (float)H;
+    const float rstd = a.rstd[srow];
+#pragma unroll
+    for (int i = 0; i < NV; ++i) {
+      const int c = (i * 64 + lane) * 4;
+      if (c < H) {
+        floatx4 o;
+#pragma unroll
+        for (int j = 0; j < 4; ++j) o[j] = rstd * (dy[i][j] * gm[i][j] - s1 - xh[i][j] * s2) * gelu_bwd<T>(z[i][j]);
+        store4<T>(a.dz + (int64_t)row * H + c, o);
+      }
+    }
+  }
+#pragma unroll
+  for (int i = 0; i < NV; ++i) {
+    const int c = (i * 64 + lane) * 4;
+#pragma unroll
+    for (int j = 0; j < 4; ++j) { red[0][wave][c + j] = dg[i][j]; red[1][wave][c + j] = db[i][j]; }
+  }
+  __syncthreads();
+  float* rec = a.slots != nullptr ? a.slots + (int64_t)blockIdx.x * 2 * H : nullptr;      // (a workgroup without rows writes a zero record: the fold adds them all)
+  for (int c = threadIdx.x; c < H; c += 256) {
+    const float g = red[0][0][c] + red[0][1][c] + red[0][2][c] + red[0][3][c];
+    const float b = red[1][0][c] + red[1][1][c] + red[1][2][c] + red[1][3][c];
+    if (rec != nullptr) { rec[c] = g; rec[H + c] = b; }
+    else if (n > 0) {
+      if (a.dgamma != nullptr) atomicAdd(a.dgamma + c, g);
+      if (a.dbeta != nullptr) atomicAdd(a.dbeta + c, b);
+    }
+  }
+}
+// bf16 fast path (H % 16 == 0, H <= 1024): ln_bwd16v2_kernel's skeleton with one more stream.  A wave owns rows row_first + k *
+// stride (k < nrow <= 64), a lane two 8-column chunks (16-byte accesses), four rows of a wave are in flight in statically named
+// register sets - row k + 4 is requested right after row k is processed -, every access of the row loop is a raw buffer access whose
+// vector offset is parked beyond the buffer for what must not happen (an idle lane, a row beyond the wave's last: loads return
+// zeros, stores are dropped), the dz stores are ln_store16 (inline asm: the compiler sees only loads pending and waits with exact
+// counts), row sums through DPP, [dgamma | dbeta] as one record per workgroup through one LDS barrier.  What is new:
+//   * z, the saved dense pre-activation, rides with xhat (6 instead of 4 16-byte loads per lane and row), and the GELU derivative
+//     Phi(z) + z phi(z) multiplies the LayerNorm gradient in registers before the one store;
+//   * the saved tensors may be addressed through a row index (the compacted classifier gradient of a dense forward): lane k holds
+//     the saved row of the wave's k-th row and its rstd, fetched once in the prologue; the row's scalar offset comes from a readlane;
+//   * the row count may live on the device (the rows that enter the loss): a wave's nrow follows it, workgroups beyond it only
+//     write their zero record.
+struct LnGRow { ln_u32x4 dy[2], xh[2], z[2]; };
+__global__ void __launch_bounds__(256, 1) ln_gelu_bwd16_kernel(LnGeluBwdArgs<bf16_t> a) {
+  extern __shared__ float ln_lds[];          // [4 waves][2 H]: epilogue only
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6), lane = threadIdx.x & 63;
+  const int H = a.H, HH = H >> 1;
+  const bool active = lane * 16 < H;
+  constexpr uint32_t OOB = 0xFFFFFF00u;
+  const int n = lng_rows(a.rows, a.n_dev);
+  const uint32_t nbytes = (uint32_t)a.rows * (uint32_t)H * 2u, sbytes = (uint32_t)a.saved_rows * (uint32_t)H * 2u;      // < 4 GiB - 256 (launcher)
+  const __amdgpu_buffer_rsrc_t rs_dy = __builtin_amdgcn_make_buffer_rsrc((void*)a.dy, 0, (int)nbytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_dz = __builtin_amdgcn_make_buffer_rsrc((void*)a.dz, 0, (int)nbytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_xh = __builtin_amdgcn_make_buffer_rsrc((void*)a.xhat, 0, (int)sbytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rs_z = __builtin_amdgcn_make_buffer_rsrc((void*)a.z, 0, (int)sbytes, 0x00020000);
+  const int c0 = active ? lane * 8 : 0, c1 = active ? HH + lane * 8 : 0;
+  const uint32_t lo0 = active ? (uint32_t)c0 * 2u : OOB, lo1 = active ? (uint32_t)c1 * 2u : OOB;
+  const int stride = gridDim.x * 4;
+  const int row_first = blockIdx.x * 4 + wave;
+  const int nrow = row_first < n ? (n - row_first + stride - 1) / stride : 0;      // <= 64 (launcher)
+  const uint32_t row_bytes = (uint32_t)H * 2u;
+  // ---- prologue: lane k = the saved row of the wave's k-th row and its rstd; gamma into registers
+  int srow_reg = 0;
+  float rstd_reg = 0.f;
+  if (lane < nrow) {
+    const int r = row_first + lane * stride;
+    int s = a.idx != nullptr ? a.idx[r] : r;
+    s = s < 0 ? 0 : (s >= a.saved_rows ? a.saved_rows - 1 : s);      // (a bad index must not leave the saved tensors: the scalar offset is not range-checked)
+    srow_reg = s;
+    rstd_reg = a.rstd[s];
+  }
+  float gm[2][8];
+#pragma unroll
+  for (int i = 0; i < 2; ++i) {
+    const int c = i ? c1 : c0;
+    *(floatx4*)&gm[i][0] = *(const floatx4*)(a.gamma + c); *(floatx4*)&gm[i][4] = *(const floatx4*)(a.gamma + c + 4);
+  }
+  const int srow_keep = srow_reg;
+  const float rstd_keep = rstd_reg;
+  // (bit-ands and selects, no short-circuit branches around the loads)
+  auto load = [&](int k, LnGRow& r) {
+    const int fetch = (int)(k < nrow);
+    const uint32_t row = (uint32_t)(row_first + k * stride);
+    const uint32_t srow = (uint32_t)__builtin_amdgcn_readlane(srow_keep, k & 63);
+    const uint32_t sb = fetch ? row * row_bytes : 0u, ss = fetch ? srow * row_bytes : 0u;
+    const uint32_t v0 = fetch ? lo0 : OOB, v1 = fetch ? lo1 : OOB;
+    r.dy[0] = __builtin_amdgcn_raw_buffer_load_b128(rs_dy, v0, sb, 0);
+    r.dy[1] = __builtin_amdgcn_raw_buffer_load_b128(rs_dy, v1, sb, 0);
+    r.xh[0] = __builtin_amdgcn_raw_buffer_load_b128(rs_xh, v0, ss, 0);
+    r.xh[1] = __builtin_amdgcn_raw_buffer_load_b128(rs_xh, v1, ss, 0);
+    r.z[0] = __builtin_amdgcn_raw_buffer_load_b128(rs_z, v0, ss, 0);
+    r.z[1] = __builtin_amdgcn_raw_buffer_load_b128(rs_z, v1, ss, 0);
+  };
+  LnGRow r0, r1, r2, r3;
+  load(0, r0); load(1, r1); load(2, r2); load(3, r3);
+  float dg[2][8], db[2][8];
+#pragma unroll
+  for (int i = 0; i < 2; ++i)
+#pragma unroll
+    for (int j = 0; j < 8; ++j) { dg[i][j] = 0.f; db[i][j] = 0.f; }
+  // a row beyond the wave's last: its loads were parked and returned zeros - it adds nothing and its store is parked too
+  auto process = [&](int k, const LnGRow& r) {
+    const int store = (int)(k < nrow);
+    const uint32_t row = (uint32_t)(row_first + k * stride);
+    float s1 = 0.f, s2 = 0.f;
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      float dy[8], xh[8];
+      unpack8(uint4{r.dy[i][0], r.dy[i][1], r.dy[i][2], r.dy[i][3]}, dy);
+      unpack8(uint4{r.xh[i][0], r.xh[i][1], r.xh[i][2], r.xh[i][3]}, xh);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        const float t = dy[j] * gm[i][j];
+        s1 += t;
+        s2 += t * xh[j];
+        dg[i][j] += dy[j] * xh[j];
+        db[i][j] += dy[j];
+      }
+    }
+    s1 = wave_sum_dpp(s1) / (float)H;
+    s2 = wave_sum_dpp(s2) / (float)H;
+    const float rstd = store ? __builtin_bit_cast(float, __builtin_amdgcn_readlane(__builtin_bit_cast(int, rstd_keep), k & 63)) : 0.f;
+    const uint32_t sbase = store ? row * row_bytes : 0u;
+    __builtin_amdgcn_sched_barrier(0);      // (the second unpack and the GELU terms are not to be hoisted above the reductions)
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      if (i) __builtin_amdgcn_sched_barrier(0);
+      float dy[8], xh[8], z[8], o[8];
+      unpack8(uint4{r.dy[i][0], r.dy[i][1], r.dy[i][2], r.dy[i][3]}, dy);
+      unpack8(uint4{r.xh[i][0], r.xh[i][1], r.xh[i][2], r.xh[i][3]}, xh);
+      unpack8(uint4{r.z[i][0], r.z[i][1], r.z[i][2], r.z[i][3]}, z);
+#pragma unroll
+      for (int j = 0; j < 8; ++j) o[j] = rstd * (dy[j] * gm[i][j] - s1 - xh[j] * s2) * gelu_bwd<bf16_t>(z[j]);
+      ln_store16(__builtin_bit_cast(ln_u32x4, pack8(o)), store ? (i ? lo1 : lo0) : OOB, sbase, rs_dz);
+    }
+  };
+#define RL_LNG_STEP(K, R) do { __builtin_amdgcn_sched_barrier(0); process(K, R); __builtin_amdgcn_sched_barrier(0); \
+    load((K) + 4, R); __builtin_amdgcn_sched_barrier(0); } while (0)
+  for (int k = 0; k < nrow; k += 4) {
+    RL_LNG_STEP(k, r0);
+    RL_LNG_STEP(k + 1, r1);
+    RL_LNG_STEP(k + 2, r2);
+    RL_LNG_STEP(k + 3, r3);
+  }
+#undef RL_LNG_STEP
+  // ---- epilogue: [dgamma | dbeta] of the workgroup = the four waves' partials added in wave order
+  float* mine = ln_lds + (size_t)wave * 2 * H;
+  if (active) {
+#pragma unroll
+    for (int i = 0; i < 2; ++i) {
+      const int c = i ? c1 : c0;
+      *(floatx4*)(mine + c) = *(const floatx4*)&dg[i][0]; *(floatx4*)(mine + c + 4) = *(const floatx4*)&dg[i][4];
+      *(floatx4*)(mine + H + c) = *(const floatx4*)&db[i][0]; *(floatx4*)(mine + H + c + 4) = *(const floatx4*)&db[i][4];
+    }
+  }
+  __syncthreads();
+  float* rec = a.slots != nullptr ? a.slots + (int64_t)blockIdx.x * 2 * H : nullptr;
+  if (rec == nullptr && blockIdx.x * 4 >= n) return;      // (no rows and no record to write; workgroup-uniform)
+  for (int q = threadIdx.x; q < 2 * H / 4; q += 256) {
+    const floatx4 v = ((*(const floatx4*)(ln_lds + 4 * q) + *(const floatx4*)(ln_lds + 2 * H + 4 * q)) + *(const floatx4*)(ln_lds + 4 * H + 4 * q)) +
+                      *(const floatx4*)(ln_lds + 6 * H + 4 * q);
+    if (rec != nullptr) *(floatx4*)(rec + 4 * q) = v;
+    else {
+      float* out = 4 * q < H ? a.dgamma : a.dbeta;
+      const int c = 4 * q < H ? 4 * q : 4 * q - H;
+      if (out != nullptr) {
+#pragma unroll
+        for (int j = 0; j < 4; ++j) atomicAdd(out + c + j, v[j]);
+      }
+    }
+  }
+}
+template <typename T> int ln_gelu_bwd(hipStream_t st, const LnGeluBwdArgs<T>& a) {
+  if (a.rows <= 0) return RL_OK;
+  if ((a.H & 3) || a.H > LN_MAXV * 256) return RL_ERR_ARG;      // the shapes ln_bwd refuses
+  if (!a.dy || !a.xhat || !a.rstd || !a.z || !a.gamma || !a.dz) return RL_ERR_ARG;
+  LnGeluBwdArgs<T> b = a;
+  if (b.saved_rows <= 0) b.saved_rows = a.rows;
+  if (a.idx == nullptr && b.saved_rows < a.rows) return RL_ERR_ARG;
+  int blocks = (a.rows + 3) / 4;
+  if constexpr (sizeof(T) == 2) {
+    const int64_t most = a.rows > b.saved_rows ? a.rows : b.saved_rows;
+    if (g_ln_fast && (a.H % 16) == 0 && (most + 8192) * a.H * 2 < (1ll << 32) - 4096) {
+      blocks = blocks < g_ln_bwd_blocks_v2 ? blocks : g_ln_bwd_blocks_v2;
+      if (blocks * 256 < a.rows) blocks = (a.rows + 255) / 256;       // a wave's rows must fit its 64 index lanes
+      if (blocks <= 96 || a.dgamma == nullptr || a.dbeta == nullptr) b.slots = nullptr;
+      if (b.slots != nullptr && blocks > 1024) return RL_ERR_ARG;     // (LN_SLOT_FLOATS holds 1024 records)
+      hipLaunchKernelGGL(ln_gelu_bwd16_kernel, dim3(blocks), dim3(256), (size_t)8 * a.H * sizeof(float), st, b);
+      if (b.slots != nullptr) hipLaunchKernelGGL(ln_fold_kernel, dim3((2 * a.H / 4 + 3) / 4), dim3(256), 0, st, b.slots, blocks, a.H, a.dgamma, a.dbeta);
+      return RL_LAUNCH_CHECK();
+    }
+  }
+  const int cap = a.H <= 512 ? 1024 : 768;
+  if (blocks > cap) blocks = cap;
+  if (blocks <= 96 || a.dgamma == nullptr || a.dbeta == nullptr) b.slots = nullptr;
+  const int nv = (a.H + 255) / 256;
+  if (nv == 1) hipLaunchKernelGGL((ln_gelu_bwd_kernel<T, 1>), dim3(blocks), dim3(256), 0, st, b);
+  else if (nv == 2) hipLaunchKernelGGL((ln_gelu_bwd_kernel<T, 2>), dim3(blocks), dim3(256), 0, st, b);
+  else if (nv == 3) hipLaunchKernelGGL((ln_gelu_bwd_kernel<T, 3>), dim3(blocks), dim3(256), 0, st, b);
+  else hipLaunchKernelGGL((ln_gelu_bwd_kernel<T, 4>), dim3(blocks), dim3(256), 0, st, b);
+  if (b.slots != nullptr) hipLaunchKernelGGL(ln_fold_kernel, dim3((2 * a.H / 4 + 3) / 4), dim3(256), 0, st, b.slots, blocks, a.H, a.dgamma, a.dbeta);
+  return RL_LAUNCH_CHECK();
+}
+template int ln_gelu_bwd<bf16_t>(hipStream_t, const LnGeluBwdArgs<bf16_t>&);
+template int ln_gelu_bwd<float>(hipStream_t, const LnGeluBwdArgs<float>&);
+
+// ---------------------------------------------------------------------------------------------
 // Embedding backward: thread owns 4 columns of one sequence position s and walks the batch.
 // ---------------------------------------------------------------------------------------------
 // Padded positions receive an exactly-zero gradient (masked as attention keys, excluded from the loss and from the

@@ -112,8 +112,15 @@ def tensor_specs(cfg, model_type="arch3"):
         specs.append((prefix + "pooler.dense.weight", (H, H), "normal"))
         specs.append((prefix + "pooler.dense.bias", (H,), "zeros"))
 
-    if model_type not in ("bert", "arch3", "arch3-abla", "arch4"):
-        raise ValueError("model_type must be 'bert', 'arch3', 'arch3-abla' or 'arch4'")
+    if model_type not in ("bert", "arch3", "arch3-abla", "arch4", "arch3-mlm"):
+        raise ValueError("model_type must be 'bert', 'arch3', 'arch3-abla', 'arch4' or 'arch3-mlm'")
+    # arch3-mlm (src/models.py:874-1020) is one-font arch3 up to the classifier, which is BertOnlyMLMHead (modeling_bert.py:419-462)
+    mlm = model_type == "arch3-mlm"
+    if mlm:
+        if cfg["num_fonts"] != 1:
+            raise ValueError("arch3-mlm (SpellBertPho2ResArch3MLM) keeps its glyphs in char_images.weight [V, 1024] (models.py:894): it "
+                             "needs num_fonts=1, got %d" % cfg["num_fonts"])
+        model_type = "arch3"
     # arch4 (src/models.py:1023-1170) is arch3 key for key with the one-font glyph table: nn.Embedding(vocab, 1024) is hard-wired there
     if model_type == "arch4":
         if cfg["num_fonts"] != 1:
@@ -165,6 +172,14 @@ def tensor_specs(cfg, model_type="arch3"):
             specs.append(("gate_net.weight", (G, (G + 1) * H), "normal"))
             specs.append(("gate_net.bias", (G,), "zeros"))
         bert("output_block.", cfg["out_layers"])
+    if mlm:      # init_weights (modeling_bert.py:496-506): Linear weights normal, biases zero, LayerNorm one / zero; the decoder has no bias of its own
+        specs.append(("cls.predictions.bias", (V,), "zeros"))
+        specs.append(("cls.predictions.transform.dense.weight", (H, H), "normal"))
+        specs.append(("cls.predictions.transform.dense.bias", (H,), "zeros"))
+        specs.append(("cls.predictions.transform.LayerNorm.weight", (H,), "ones"))
+        specs.append(("cls.predictions.transform.LayerNorm.bias", (H,), "zeros"))
+        specs.append(("cls.predictions.decoder.weight", (V, H), "normal"))
+        return specs
     specs.append(("classifier.weight", (V, H), "normal"))
     specs.append(("classifier.bias", (V,), "zeros"))
     return specs
@@ -188,6 +203,6 @@ def init_state_dict_numpy(cfg, model_type="arch3", seed=0, scheme="reference", t
             sd[name] = glyph
         else:
             sd[name] = tensor_init(name, shape, kind, cfg, seed, scheme)
-    if tie:
+    if tie and "classifier.weight" in sd:      # (arch3-mlm has no classifier.weight: its decoder is never tied, models.py:915-917)
         sd["classifier.weight"] = sd["bert.embeddings.word_embeddings.weight"]
     return sd

@@ -684,7 +684,7 @@ class RealiseModule(nn.Module):
     def _begin_gradient_pass(self):
         """detached gradients (our zero_grad(), or an optimizer's zero_grad(set_to_none=True)) mean "start from zero": the engine
         does that itself - a one-launch partial fill + overwriting weight-gradient GEMMs (realise_engine_set_grads_fresh)"""
-        sentinel = self._views["classifier.bias"][3]
+        sentinel = self._views["classifier.bias" if "classifier.bias" in self._views else "cls.predictions.bias"][3]
         if sentinel.grad is None or getattr(self, "_zero_pending", False):
             _capi.load().realise_engine_set_grads_fresh(self._engine, 1)
             self._zero_pending = False
