@@ -7,6 +7,8 @@ is no CPU or PyTorch fallback.
 import ctypes as C
 import os
 
+from .config import MODEL_TYPES
+
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "librealise_hip.so")
 
@@ -214,7 +216,7 @@ def check(rc, what):
 
 def make_config(cfg, model_type, dtype, tie=True):
     c = Config()
-    c.model_type = {"bert": 0, "arch3": 1, "arch3-abla": 2, "arch4": 3, "arch3-mlm": 4}[model_type]
+    c.model_type = MODEL_TYPES[model_type]
     c.dtype = dtype
     c.hidden, c.heads, c.intermediate = cfg["hidden_size"], cfg["num_attention_heads"], cfg["intermediate_size"]
     c.vocab, c.max_pos, c.type_vocab = cfg["vocab_size"], cfg["max_position_embeddings"], cfg["type_vocab_size"]

@@ -5,6 +5,7 @@ Mirrors the fields of the reference's ``BertConfig`` that the path reads
 pokes onto it (run.py:418-425).  A plain dict subclass so it serialises to the
 same ``config.json`` the reference writes.
 """
+import collections
 import copy
 import json
 import os
@@ -53,25 +54,21 @@ class RealiseConfig(dict):
         self[k] = v
 
     def validate(self, glyph_branch=True, model_type=None):
-        """``glyph_branch``: the model being built has a glyph tower (a module passes what it knows; a bare config assumes one).
-        ``model_type``: the module's ``model_type`` where one is being built ("arch4" and "arch3-mlm" have conditions of their own)."""
-        # SpellBertPho2ResArch4 hard-wires nn.Embedding(vocab_size, 1024) viewed as [N, 1, 32, 32] (models.py:1043,1134) whatever
-        # num_fonts says; a config that asks for anything else is refused instead of silently ignored
-        if model_type == "arch4":
+        """``model_type``: the module's ``model_type`` where one is being built; its variant then says whether there is a glyph tower.
+        ``glyph_branch``: the same for a bare config (which assumes one)."""
+        v = variant_of(self, model_type) if model_type is not None else None
+        if v is not None:
+            glyph_branch = v.res
+        # SpellBertPho2ResArch4 and SpellBertPho2ResArch3MLM hard-wire nn.Embedding(vocab_size, 1024) viewed as [N, 1, 32, 32]
+        # (models.py:1043,1134; models.py:894,985) whatever num_fonts says; a config that asks for anything else is refused instead
+        # of silently ignored
+        if v is not None and v.one_font:
             if self["num_fonts"] != 1:
-                raise ValueError("SpellBertPho2ResArch4 reads one 32x32 glyph per character (char_images.weight [V, 1024]): it needs "
-                                 "num_fonts=1, got %d" % self["num_fonts"])
+                raise ValueError("%s reads one 32x32 glyph per character (char_images.weight [V, 1024]): it needs "
+                                 "num_fonts=1, got %d" % (v.reference_class, self["num_fonts"]))
             if self["glyph_size"] != 32:
-                raise ValueError("SpellBertPho2ResArch4 views its glyph table as [N, 1, 32, 32]: it needs glyph_size=32, got %d"
-                                 % self["glyph_size"])
-        # SpellBertPho2ResArch3MLM has the same hard-wired table (models.py:894,985)
-        if model_type == "arch3-mlm":
-            if self["num_fonts"] != 1:
-                raise ValueError("SpellBertPho2ResArch3MLM reads one 32x32 glyph per character (char_images.weight [V, 1024]): it needs "
-                                 "num_fonts=1, got %d" % self["num_fonts"])
-            if self["glyph_size"] != 32:
-                raise ValueError("SpellBertPho2ResArch3MLM views its glyph table as [N, 1, 32, 32]: it needs glyph_size=32, got %d"
-                                 % self["glyph_size"])
+                raise ValueError("%s views its glyph table as [N, 1, 32, 32]: it needs glyph_size=32, got %d"
+                                 % (v.reference_class, self["glyph_size"]))
         if self["hidden_size"] % self["num_attention_heads"] != 0:
             raise ValueError("hidden size must be a multiple of the head count (modeling_bert.py:199-202)")
         if self["hidden_size"] // self["num_attention_heads"] != 64:
@@ -120,6 +117,32 @@ class RealiseConfig(dict):
         return c
 
 
-def num_gates(cfg):
-    """1 + [with_pho] + [with_res] (src/models_abla.py:40-45)"""
-    return 1 + (cfg.get("with_pho", "yes") == "yes") + (cfg.get("with_res", "yes") == "yes")
+# model_type -> (number in the C ABI, reference class, line of src/models.py where that class hard-wires the one-font glyph table
+# nn.Embedding(vocab_size, 1024), or None).  A new model is a row here and a case in variant_of.
+_MODELS = {
+    "bert": (0, "SpellBert", None),
+    "arch3": (1, "SpellBertPho2ResArch3", None),
+    "arch3-abla": (2, "SpellBertPho2ResArch3Abla", None),
+    "arch4": (3, "SpellBertPho2ResArch4", 1043),
+    "arch3-mlm": (4, "SpellBertPho2ResArch3MLM", 894),
+}
+MODEL_TYPES = {k: row[0] for k, row in _MODELS.items()}
+
+# What a model computes: csrc/layout.h's ``Variant`` field for field (``gates`` is G: 0 without a gate_net, otherwise its ``nsrc``),
+# then what only Python needs: ``one_font`` (the hard-wired [V, 1024] glyph table, at src/models.py:``one_font_line``) and the
+# reference class name for messages.  Every Python-side decision reads this, not ``model_type``.
+Variant = collections.namedtuple("Variant", "arch pho res gate gates gate_softmax mlm_head one_font one_font_line reference_class")
+
+
+def variant_of(cfg, model_type):
+    if model_type not in _MODELS:
+        raise ValueError("model_type must be 'bert', 'arch3', 'arch3-abla', 'arch4' or 'arch3-mlm'")
+    _, reference_class, one_font_line = _MODELS[model_type]
+    arch = model_type != "bert"
+    abla = model_type == "arch3-abla"      # src/models_abla.py:37-45: the switches drop whole branches; (yes, yes, gate) is arch3
+    pho = arch and (not abla or cfg.get("with_pho", "yes") == "yes")
+    res = arch and (not abla or cfg.get("with_res", "yes") == "yes")
+    gate = arch and (not abla or cfg.get("fusion", "gate") == "gate")
+    return Variant(arch=arch, pho=pho, res=res, gate=gate, gates=(1 + pho + res) if gate else 0,
+                   gate_softmax=model_type == "arch4", mlm_head=model_type == "arch3-mlm",
+                   one_font=one_font_line is not None, one_font_line=one_font_line, reference_class=reference_class)

@@ -15,6 +15,8 @@ import zlib
 
 import numpy as np
 
+from .config import variant_of
+
 
 def _rng(name, seed):
     key = (zlib.crc32(name.encode()) << 32) | (zlib.adler32(name.encode()) & 0xFFFFFFFF)
@@ -112,27 +114,14 @@ def tensor_specs(cfg, model_type="arch3"):
         specs.append((prefix + "pooler.dense.weight", (H, H), "normal"))
         specs.append((prefix + "pooler.dense.bias", (H,), "zeros"))
 
-    if model_type not in ("bert", "arch3", "arch3-abla", "arch4", "arch3-mlm"):
-        raise ValueError("model_type must be 'bert', 'arch3', 'arch3-abla', 'arch4' or 'arch3-mlm'")
-    # arch3-mlm (src/models.py:874-1020) is one-font arch3 up to the classifier, which is BertOnlyMLMHead (modeling_bert.py:419-462)
-    mlm = model_type == "arch3-mlm"
-    if mlm:
-        if cfg["num_fonts"] != 1:
-            raise ValueError("arch3-mlm (SpellBertPho2ResArch3MLM) keeps its glyphs in char_images.weight [V, 1024] (models.py:894): it "
-                             "needs num_fonts=1, got %d" % cfg["num_fonts"])
-        model_type = "arch3"
-    # arch4 (src/models.py:1023-1170) is arch3 key for key with the one-font glyph table: nn.Embedding(vocab, 1024) is hard-wired there
-    if model_type == "arch4":
-        if cfg["num_fonts"] != 1:
-            raise ValueError("arch4 (SpellBertPho2ResArch4) keeps its glyphs in char_images.weight [V, 1024] (models.py:1043): it needs "
-                             "num_fonts=1, got %d" % cfg["num_fonts"])
-        model_type = "arch3"
-    # arch3-abla (src/models_abla.py:33-96): the switches drop whole branches; (yes, yes, gate) is arch3 key for key
-    arch = model_type != "bert"
-    with_pho = not arch or model_type == "arch3" or cfg.get("with_pho", "yes") == "yes"
-    with_res = not arch or model_type == "arch3" or cfg.get("with_res", "yes") == "yes"
-    gate = model_type == "arch3" or cfg.get("fusion", "gate") == "gate"
-    G = 1 + int(with_pho) + int(with_res)
+    # which branches, which fusion, which head: config.variant_of (it refuses an unknown model_type)
+    v = variant_of(cfg, model_type)
+    # arch4 (src/models.py:1023-1170) is arch3 key for key with the one-font glyph table, arch3-mlm (src/models.py:874-1020) the same up
+    # to the classifier: nn.Embedding(vocab, 1024) is hard-wired in both
+    if v.one_font and cfg["num_fonts"] != 1:
+        msg = "%s (%s) keeps its glyphs in char_images.weight [V, 1024] (models.py:%d): it needs num_fonts=1, got %d"
+        raise ValueError(msg % (model_type, v.reference_class, v.one_font_line, cfg["num_fonts"]))
+    arch, with_pho, with_res, gate, G = v.arch, v.pho, v.res, v.gate, v.gates
     if arch and with_res:
         F_ = cfg["num_fonts"]
         if F_ == 1:      # models.py:674-676: the single-font model keeps the table as an nn.Embedding [V, 1024]
@@ -172,7 +161,7 @@ def tensor_specs(cfg, model_type="arch3"):
             specs.append(("gate_net.weight", (G, (G + 1) * H), "normal"))
             specs.append(("gate_net.bias", (G,), "zeros"))
         bert("output_block.", cfg["out_layers"])
-    if mlm:      # init_weights (modeling_bert.py:496-506): Linear weights normal, biases zero, LayerNorm one / zero; the decoder has no bias of its own
+    if v.mlm_head:      # BertOnlyMLMHead (modeling_bert.py:419-462); init_weights (modeling_bert.py:496-506): Linear weights normal, biases zero, LayerNorm one / zero; the decoder has no bias of its own
         specs.append(("cls.predictions.bias", (V,), "zeros"))
         specs.append(("cls.predictions.transform.dense.weight", (H, H), "normal"))
         specs.append(("cls.predictions.transform.dense.bias", (H,), "zeros"))

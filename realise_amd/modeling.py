@@ -13,6 +13,7 @@ raises.
 """
 import collections
 import ctypes as C
+import functools
 import json
 import os
 
@@ -21,7 +22,7 @@ import torch
 from torch import nn
 
 from . import _capi
-from .config import RealiseConfig
+from .config import RealiseConfig, variant_of
 from .init import tensor_init, tensor_specs, synth_glyph_table
 
 _DTYPES = {"bf16": (_capi.BF16, torch.bfloat16), "fp32": (_capi.F32, torch.float32)}
@@ -62,7 +63,10 @@ class RealiseModule(nn.Module):
         if not isinstance(config, RealiseConfig):
             config = RealiseConfig(**{k: getattr(config, k) for k in RealiseConfig.DEFAULTS if hasattr(config, k)})
         self.config = config
-        config.validate(glyph_branch=self._has_glyph_branch(), model_type=self.model_type)
+        self.variant = variant_of(config, self.model_type)      # which branches / fusion / head this model has: read here, not model_type
+        config.validate(model_type=self.model_type)
+        # m._bucket_comm_order(n): the static method below for this model's buckets (SpellBert, which has no branch buckets, keeps the default)
+        self._bucket_comm_order = functools.partial(RealiseModule._bucket_comm_order, pho=self.variant.pho or not self.variant.arch)
         self.vocab_size = config.vocab_size
         self.compute_dtype = compute_dtype or os.environ.get("REALISE_DTYPE", "bf16")
         if self.compute_dtype not in _DTYPES:
@@ -187,16 +191,6 @@ class RealiseModule(nn.Module):
     def device(self):
         return self._arenas[0].device
 
-    def _has_pinyin_branch(self):
-        return self.model_type in ("arch3", "arch4")
-
-    def _has_glyph_branch(self):
-        return self.model_type in ("arch3", "arch4")
-
-    def _num_gates(self):
-        """number of fusion gates G (0: the model has no gate_net)"""
-        return 3 if self.model_type in ("arch3", "arch4") else 0
-
     # ------------------------------------------------------------------ reference-facing API
     def init_weights(self, seed=0, scheme="reference"):
         """transformers/modeling_bert.py:496-506 + PyTorch defaults, from a torch-independent generator."""
@@ -295,6 +289,9 @@ class RealiseModule(nn.Module):
         traditional forms with OpenCC; neither ships with the tree, so ``font_paths`` (list of paths, or (path, traditional)
         pairs) and ``to_traditional`` (str -> str) can be given explicitly.  A pre-rendered table goes through
         ``set_glyph_table``."""
+        if self.variant.one_font:      # the reference class has build_glyce_embed (models.py:919-950, 1068-1099) and no multi-font method
+            raise AttributeError("%s has no build_glyce_embed_multifonts: its glyph table is the single-font "
+                                 "char_images.weight [V, 1024]; use build_glyce_embed(vocab_dir, font_path)" % self.variant.reference_class)
         from . import glyph
         if not isinstance(vocab_dir, (str, bytes, os.PathLike)):
             raise TypeError("build_glyce_embed_multifonts(vocab_dir, num_fonts, use_traditional_font): vocab_dir must be a path; "
@@ -488,7 +485,7 @@ class RealiseModule(nn.Module):
         """The fusion gates of the last forward as a [B, S, G] fp32 tensor (a copy): what the reference's show_gate.py dumps.  Column
         order bert, pinyin, glyph (the present ones).  SpellBertPho2ResArch3: independent sigmoids; SpellBertPho2ResArch4: a distribution
         over the modalities.  Rows a live-row step skipped (padding behind a sentence's last position) hold no meaningful value."""
-        G = self._num_gates()
+        G = self.variant.gates
         if G == 0:
             raise RuntimeError("this model has no fusion gate (model_type %r, fusion %r)" % (self.model_type, self.config.get("fusion")))
         if self._engine is None or getattr(self, "_gate_gen", None) != self._fwd_gen:
@@ -522,7 +519,7 @@ class RealiseModule(nn.Module):
         cb.src_idx, cb.masks = src.data_ptr(), masks.data_ptr()
         cb.tgt_idx = tgt.data_ptr() if tgt is not None else None
         cb.loss_masks = loss_masks.data_ptr() if loss_masks is not None else None
-        with_pho = self._has_pinyin_branch()
+        with_pho = self.variant.pho
         if with_pho and "pho_idx" not in batch and getattr(self, "_pho_table", None) is not None:
             batch = self.build_batch_device(batch)
         if with_pho and "_pho_device" in batch:
@@ -600,7 +597,7 @@ class RealiseModule(nn.Module):
     def glyph_forward(self, src_idx, training=None):
         """BASELINE configs[3]: the glyph ResNet alone - ``resnet(char_images_multifonts[src_idx])`` (src/models.py:829-836,
         src/char_cnn.py:46-55) -> [B, S, 768] in the compute dtype, before ``resnet_layernorm``."""
-        if not self._has_glyph_branch():
+        if not self.variant.res:
             raise RuntimeError("glyph_forward needs a model with the glyph branch")
         src = self._dev(src_idx)
         B, S = src.shape
@@ -684,7 +681,7 @@ class RealiseModule(nn.Module):
     def _begin_gradient_pass(self):
         """detached gradients (our zero_grad(), or an optimizer's zero_grad(set_to_none=True)) mean "start from zero": the engine
         does that itself - a one-launch partial fill + overwriting weight-gradient GEMMs (realise_engine_set_grads_fresh)"""
-        sentinel = self._views["classifier.bias" if "classifier.bias" in self._views else "cls.predictions.bias"][3]
+        sentinel = self._views["cls.predictions.bias" if self.variant.mlm_head else "classifier.bias"][3]
         if sentinel.grad is None or getattr(self, "_zero_pending", False):
             _capi.load().realise_engine_set_grads_fresh(self._engine, 1)
             self._zero_pending = False
@@ -726,9 +723,12 @@ class RealiseModule(nn.Module):
         self._attach_grads()
 
     @staticmethod
-    def _bucket_comm_order(n):
-        """order in which the buckets are all-reduced (the same on every rank).  arch3: output_block first, then the bert groups
-        interleaved with the shorter pinyin and glyph branches that run next to them, the embeddings (+ tied classifier) last"""
+    def _bucket_comm_order(n, pho=True):
+        """order in which the buckets are all-reduced (the same on every rank): output_block first, then the bert groups interleaved
+        with the shorter pinyin and glyph branches that run next to them, the embeddings (+ tied classifier) last"""
+        if not pho:
+            # no pinyin bucket: 0 output_block | 1 fusion (+ glyph ResNet) | 2 .. n-2 bert groups | n-1 embeddings
+            return list(range(n)) if n < 4 else [0, 2, 1] + list(range(3, n))
         if n < 5:
             return list(range(n))
         # buckets: 0 output_block | 1 gate + glyph | 2 pinyin | 3 .. n-2 bert groups (top layers first) | n-1 embeddings

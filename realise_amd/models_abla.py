@@ -13,7 +13,6 @@ Everything else is the Arch3 module: the same engine (``model_type`` 2 of the C 
 ``trainer.train`` / ``decode`` / ``save_pretrained`` / DDP unchanged.  ``MODEL_CLASSES`` below is run.py:40-51's table with the
 ``bert-pho2-res-arch3-abla`` entry (run.py:50); ``realise_amd.modeling.MODEL_CLASSES`` keeps the two models of models.py.
 """
-from .config import num_gates
 from .modeling import RealiseModule, SpellBert, SpellBertPho2ResArch3
 
 
@@ -27,24 +26,15 @@ class SpellBertPho2ResArch3Abla(RealiseModule):
         # carries them
         for k in ("with_pho", "with_res", "fusion"):
             self.config[k] = self.config.get(k, self.config.DEFAULTS[k])
-        self.config["num_gates"] = num_gates(self.config)
+        self.config["num_gates"] = 1 + self.variant.pho + self.variant.res
         if config is not self.config:
             try:
                 setattr(config, "num_gates", self.config["num_gates"])
             except (AttributeError, TypeError):
                 pass
 
-    def _has_pinyin_branch(self):
-        return self.config.get("with_pho", "yes") == "yes"
-
-    def _has_glyph_branch(self):
-        return self.config.get("with_res", "yes") == "yes"
-
-    def _num_gates(self):
-        return self.config["num_gates"] if self.config.get("fusion", "gate") == "gate" else 0
-
     def _require_glyph_branch(self, what):
-        if not self._has_glyph_branch():
+        if not self.variant.res:
             raise RuntimeError("%s: this model has no glyph branch (with_res='no'; run.py:433 skips build_glyce_embed*)" % what)
 
     def set_glyph_table(self, table):
@@ -62,15 +52,6 @@ class SpellBertPho2ResArch3Abla(RealiseModule):
 
     # models_abla.py:193-199: the batch always gets pho_idx / pho_lens, whether the pinyin branch reads them or not
     build_batch = staticmethod(SpellBertPho2ResArch3.build_batch)
-
-    def _bucket_comm_order(self, n):
-        """all-reduce order of the gradient buckets.  With the pinyin branch the layout is Arch3's; without it there is no pinyin
-        bucket: 0 output_block | 1 fusion (+ glyph ResNet) | 2 .. n-2 bert groups | n-1 embeddings"""
-        if self._has_pinyin_branch():
-            return RealiseModule._bucket_comm_order(n)
-        if n < 4:
-            return list(range(n))
-        return [0, 2, 1] + list(range(3, n))
 
 
 MODEL_CLASSES = {          # src/run.py:40-51

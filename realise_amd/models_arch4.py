@@ -17,11 +17,6 @@ class SpellBertPho2ResArch4(SpellBertPho2ResArch3):
     """src/models.py:1023-1170."""
     model_type = "arch4"
 
-    def build_glyce_embed_multifonts(self, *args, **kw):
-        """The reference class has build_glyce_embed (models.py:1068-1099) and no multi-font method."""
-        raise AttributeError("SpellBertPho2ResArch4 has no build_glyce_embed_multifonts: its glyph table is the single-font "
-                             "char_images.weight [V, 1024]; use build_glyce_embed(vocab_dir, font_path)")
-
 
 MODEL_CLASSES = {          # src/run.py:40-51
     "bert": SpellBert,

@@ -28,22 +28,8 @@ class SpellBertPho2ResArch3MLM(SpellBertPho2ResArch3):
         # the decoder is a parameter of its own whatever the caller asks for (models.py:915-917: tie_cls_weight is a `pass`)
         super().__init__(config, compute_dtype=compute_dtype, seed=seed, init_scheme=init_scheme, tie=False, logits_dtype=logits_dtype)
 
-    def _has_pinyin_branch(self):
-        return True
-
-    def _has_glyph_branch(self):
-        return True
-
-    def _num_gates(self):
-        return 3
-
     def tie_cls_weight(self):
         """src/models.py:915-917: a `pass` - cls.predictions.decoder.weight stays a tensor of its own."""
-
-    def build_glyce_embed_multifonts(self, *args, **kw):
-        """The reference class has build_glyce_embed (models.py:919-950) and no multi-font method."""
-        raise AttributeError("SpellBertPho2ResArch3MLM has no build_glyce_embed_multifonts: its glyph table is the single-font "
-                             "char_images.weight [V, 1024]; use build_glyce_embed(vocab_dir, font_path)")
 
 
 MODEL_CLASSES = {          # src/run.py:40-51

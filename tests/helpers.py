@@ -1,10 +1,12 @@
 """Shared helpers for the parity tests (test infrastructure)."""
+import ctypes
 import os
 
 import numpy as np
 import torch
 
-from realise_amd.config import RealiseConfig
+from realise_amd import _capi
+from realise_amd.config import RealiseConfig, variant_of
 from realise_amd.data import synthetic_batch
 from realise_amd.init import init_state_dict_numpy
 
@@ -40,7 +42,7 @@ def golden_case_inputs(g, model_type):
     B, S, seed, nl = int(g["meta/B"]), int(g["meta/S"]), int(g["meta/seed"]), int(g["meta/n_layers"])
     cfg = RealiseConfig(num_hidden_layers=nl, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0)
     sd_np = init_state_dict_numpy(cfg, model_type, seed=seed, scheme="perturbed")
-    batch = synthetic_batch(B, S, seed=seed, with_pho=(model_type == "arch3"))
+    batch = synthetic_batch(B, S, seed=seed, with_pho=variant_of(cfg, model_type).pho)
     return cfg, sd_np, batch
 
 
@@ -53,3 +55,167 @@ def oracle_state_dict(sd_np, requires_grad=False):
         sd[k] = t
     sd["classifier.weight"] = sd["bert.embeddings.word_embeddings.weight"]
     return sd
+
+
+# ------------------------------------------------------------------------------------------------ whole-model variant tests
+# (tests/test_{abla,arch4,mlm,resnet1}_gpu.py: one model variant each against the reference's fixtures of tools/make_golden_variants.py)
+FP32_LOGIT_TOL = 1e-3       # tests/test_engine_gpu.py
+TDT = {"fp32": torch.float32, "bf16": torch.bfloat16}
+DT = {"fp32": _capi.F32, "bf16": _capi.BF16}
+
+
+def stream():
+    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+
+
+def ptr(t):
+    return None if t is None else t.data_ptr()
+
+
+def variant_case_inputs(g, model_type, **cfg_kw):
+    """cfg / weights / batch of a variant fixture from its seeds; ``cfg_kw``: what the case sets beyond depth and dropout 0"""
+    cfg = RealiseConfig(num_hidden_layers=int(g["meta/n_layers"]), hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0, **cfg_kw)
+    sd_np = init_state_dict_numpy(cfg, model_type, seed=int(g["meta/seed"]), scheme="perturbed")
+    batch = synthetic_batch(int(g["meta/B"]), int(g["meta/S"]), seed=int(g["meta/seed"]), with_pho=True)
+    return cfg, sd_np, batch
+
+
+def build_model(cls, cfg, sd_np, dtype, train):
+    m = cls(cfg, compute_dtype=dtype)
+    m.load_state_dict({k: torch.from_numpy(np.ascontiguousarray(x)) for k, x in sd_np.items()})
+    m.to("cuda")
+    m.train(train)
+    return m
+
+
+def train_step(m, batch):
+    loss, logits = m(batch)
+    loss.backward()
+    torch.cuda.synchronize()
+    return loss.item(), logits, {n: p.grad.detach().clone() for n, p in m.named_parameters() if p.grad is not None}
+
+
+def cosine(a, b):
+    a, b = np.asarray(a, np.float64).ravel(), np.asarray(b, np.float64).ravel()
+    return float(a @ b / (np.linalg.norm(a) * np.linalg.norm(b) + 1e-30))
+
+
+def pinyin_batch(batch, tokenizer=None):
+    """build_batch stand-in (models.py:797-804 shape): a deterministic pinyin per id, lengths 1..4"""
+    ids = batch["src_idx"].reshape(-1)
+    lens = (ids % 4 + 1).to(torch.int64)
+    cols = torch.arange(4).unsqueeze(0)
+    batch["pho_idx"] = torch.where(cols < lens.unsqueeze(1), (ids.unsqueeze(1) + cols) % 32 + 1, torch.zeros_like(cols))
+    batch["pho_lens"] = lens.tolist()
+    return batch
+
+
+def flip_block(g, n_blocks=5):
+    """ReLU boundary flips: the deepest glyph block whose reference pre-ReLU inputs come within 2e-5 of zero; it and
+    the blocks upstream of it get the looser bars below (0: none)"""
+    near = [b for b in range(1, n_blocks + 1) if int(g.get("relu_near0/%d" % b, 0)) > 0]
+    return max(near) if near else 0
+
+
+def _flipped(n, flip):
+    return n.startswith("resnet.res_block") and int(n[len("resnet.res_block")]) <= flip
+
+
+def check_grads_fp32(g, grads, flip):
+    """fp32 gradients against the fixture's summaries: the golden-summary bar, the looser one for the glyph blocks at or upstream of a
+    reference ReLU near-flip.  A tensor the fixture does not hold is left out; returns how many were compared."""
+    checked = 0
+    tied = {"classifier.weight": "bert.embeddings.word_embeddings.weight"}      # one parameter: the reference lists it under the other name
+    for n, gr in grads.items():
+        gk = "grad/" + n
+        if gk + "/n" not in g:
+            gk = "grad/" + tied.get(n, n)
+        if gk + "/n" not in g:
+            continue
+        checked += 1
+        if _flipped(n, flip):
+            s, _, abssum = sample_of(gr)
+            assert cosine(s, g[gk + "/sample"]) >= 0.96, n
+            assert abs(abssum - float(g[gk + "/abssum"])) <= 0.1 * float(g[gk + "/abssum"]), n
+            continue
+        check_summary(g, gk, gr, atol=2e-6 + 5e-3 * float(g[gk + "/abssum"]) / int(g[gk + "/n"]), what="grad(golden)")
+    return checked
+
+
+def check_buffers(g, sd):
+    for k in g:
+        if k.startswith("buf/") and k.endswith("/n"):
+            name = k[len("buf/"):-len("/n")]
+            check_summary(g, "buf/" + name, sd[name].double(), 1e-4, what="buffer")
+
+
+def check_train_fixture_fp32(g, m, loss, logits, grads, n_blocks=5):
+    """One fp32 training step of module ``m`` (``train_step``'s result) against the reference's train fixture ``g``: loss, logits
+    summary, arg-max ids above the margin (that this is every position is the caller's to assert where it holds), the set of
+    parameters without a gradient, every gradient, the BatchNorm buffers.  Returns (flip_block, gradients compared, names of the
+    parameters without a gradient)."""
+    print("loss %.6f (golden %.6f)" % (loss, float(g["loss"])))
+    assert abs(loss - float(g["loss"])) < 1e-4
+    check_summary(g, "logits", logits.float(), FP32_LOGIT_TOL)
+    ids = logits.argmax(-1).cpu().numpy().astype(np.int32)
+    sure = g["margin"] > 1e-4
+    assert np.array_equal(ids[sure], g["argmax"][sure])
+    flip = flip_block(g, n_blocks)
+    ref_none = {k[len("gradnone/"):] for k in g if k.startswith("gradnone/")}
+    ours_none = {n for n, p in m.named_parameters() if n not in grads}
+    assert ours_none == ref_none
+    checked = check_grads_fp32(g, grads, flip)
+    check_buffers(g, m.state_dict())
+    return flip, checked, ref_none
+
+
+def check_train_step_bf16(mb, batch, loss, grads, flip):
+    """One bf16 training step of module ``mb`` against the fp32 engine run of the same model (``loss``, ``grads``): the loss band, the
+    same gradient set, cosine 0.99 outside the glyph tower, 0.96 inside it, 0.94 for the blocks at or upstream of a ReLU boundary flip
+    of the reference (pre-ReLU inputs within 2e-5 of zero, which bf16 rounding moves across the boundary)"""
+    lb, _, gb = train_step(mb, batch)
+    print("bf16 loss %.6f" % lb)
+    assert abs(lb - loss) < 5e-2
+    assert set(gb) == set(grads)
+    cos = sorted((cosine(gb[n].float().cpu().numpy(), grads[n].cpu().numpy()), n) for n in grads
+                 if grads[n].numel() >= 64 and grads[n].abs().max() >= 1e-7)
+    print("bf16 worst cosines", cos[:6])
+    worst_other = min([c for c, n in cos if not n.startswith("resnet.")] or [1.0])
+    assert worst_other > 0.99, [x for x in cos if not x[1].startswith("resnet.")][:8]
+    flipped = [x for x in cos if _flipped(x[1], flip)]
+    assert min([c for c, n in flipped] or [1.0]) > 0.94, flipped[:8]
+    assert min([x for x in cos if x not in flipped] or [(1.0, "")])[0] > 0.96, cos[:8]
+
+
+def check_live_row_step_equals_dense_step(cls, cfg, sd_np, batch, keep=lambda n: ".layer." in n):
+    """the bf16 training step over the live rows (the default on B*S % 64 == 0 batches) against the same step over every row: same
+    loss, the ``keep`` dense weight gradients bit-identical.  Returns their names."""
+    lib = _capi.load()
+    res = []
+    for on in (2, 0):
+        lib.realise_set_engine(10, on)
+        try:
+            loss, _, grads = train_step(build_model(cls, cfg, sd_np, "bf16", True), batch)
+        finally:
+            lib.realise_set_engine(10, 2)
+        res.append((loss, {n: g for n, g in grads.items() if keep(n) and n.endswith("dense.weight")}))
+    assert res[0][0] == res[1][0]
+    assert res[0][1] and set(res[0][1]) == set(res[1][1])
+    for n in res[0][1]:
+        assert torch.equal(res[0][1][n], res[1][1][n]), n
+    return set(res[0][1])
+
+
+def check_gradients_unmoved(ga, ga2, gb):
+    """``gb`` against ``ga``, where ``ga2`` is a second run of the model that gave ``ga``: bit-identical, except that tensors behind fp32
+    atomics (tests/test_round6_gpu.py:483-484; at these small bf16 shapes that includes the LayerNorm gamma / beta gradients and the
+    glyph ResNet's BatchNorm reductions) are held to the distance between the two runs of the same model"""
+    for n in ga:
+        atomics = ("embeddings" in n or n == "classifier.weight" or n.startswith("gate_net") or "layernorm" in n.lower()
+                   or n.startswith("resnet."))
+        if not atomics and torch.equal(ga[n], ga2[n]):
+            assert torch.equal(ga[n], gb[n]), n
+        else:
+            ref = (ga[n].float() - ga2[n].float()).norm().item()
+            d = (ga[n].float() - gb[n].float()).norm().item()
+            assert d <= 4.0 * ref + 1e-5 * ga[n].float().norm().item(), (n, d, ref)

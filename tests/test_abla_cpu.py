@@ -1,5 +1,5 @@
 """CPU checks of the ablation model SpellBertPho2ResArch3Abla (src/models_abla.py:33-299): the C layout of every variant against
-the reference's state_dict (tests/golden/abla_state_dicts.json, tools/make_golden_abla.py) and tensor_specs, the config contract,
+the reference's state_dict (tests/golden/abla_state_dicts.json, tools/make_golden_variants.py) and tensor_specs, the config contract,
 the module shell without a GPU and the gradient-bucket all-reduce order."""
 import json
 import os

@@ -1,5 +1,5 @@
 """CPU checks of SpellBertPho2ResArch4 (src/models.py:1023-1170): the C layout of model_type 3 against the reference's state_dict
-(tests/golden/arch4_state_dict.json, tools/make_golden_arch4.py) and against Arch3's one-font layout, the config contract, the
+(tests/golden/arch4_state_dict.json, tools/make_golden_variants.py) and against Arch3's one-font layout, the config contract, the
 module shell without a GPU, the checkpoint round trip and the fixtures' gates."""
 import json
 import os

@@ -1,5 +1,5 @@
 """CPU checks of SpellBertPho2ResArch3MLM (src/models.py:874-1020): the C layout of model_type 4 against the reference's state_dict
-(tests/golden/mlm_state_dict.json, tools/make_golden_mlm.py), the place of the six head tensors in bucket 0, the config contract,
+(tests/golden/mlm_state_dict.json, tools/make_golden_variants.py), the place of the six head tensors in bucket 0, the config contract,
 the module shell without a GPU and the checkpoint round trip."""
 import json
 import os

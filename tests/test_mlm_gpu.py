@@ -3,19 +3,18 @@
 * realise_layernorm_gelu_bwd against fp64 torch autograd of LayerNorm(gelu(z)) on the compute-dtype-rounded inputs (fp32 and bf16),
   with a device row count, a count of zero and a shuffled row index, under the bars of the gate-kernel test
   (tests/test_arch4_gpu.py::test_gate_softmax_kernels_against_autograd);
-* the whole model in fp32 against the reference's fixtures (tools/make_golden_mlm.py) with the bars of tests/test_arch4_gpu.py, the
+* the whole model in fp32 against the reference's fixtures (tools/make_golden_variants.py) with the bars of tests/test_arch4_gpu.py, the
   taps head.z / head.y against the stored samples, bf16 against the fp32 engine run;
 * no-logits forward == default forward, live-row step == dense step, gradient accumulation through the device loss scalar,
   trainer.train, the checkpoint round trip;
 * SpellBertPho2ResArch3 with one font stepped before and after an MLM step in the same process: nothing moves.
 """
-import ctypes as C
-
 import numpy as np
 import pytest
 import torch
 
-from helpers import check_summary, load_golden, sample_of
+from helpers import (DT, FP32_LOGIT_TOL, TDT, build_model, check_gradients_unmoved, check_live_row_step_equals_dense_step, check_summary,
+                     check_train_fixture_fp32, check_train_step_bf16, load_golden, pinyin_batch, ptr, stream, train_step, variant_case_inputs)
 from realise_amd import _capi
 from realise_amd.config import RealiseConfig
 from realise_amd.data import synthetic_batch
@@ -25,21 +24,10 @@ from realise_amd.models_mlm import SpellBertPho2ResArch3MLM
 
 pytestmark = pytest.mark.gpu
 
-FP32_LOGIT_TOL = 1e-3       # tests/test_arch4_gpu.py
-TDT = {"fp32": torch.float32, "bf16": torch.bfloat16}
-DT = {"fp32": _capi.F32, "bf16": _capi.BF16}
 P = "cls.predictions."
 HEAD = [P + "bias", P + "decoder.weight", P + "transform.LayerNorm.weight", P + "transform.LayerNorm.bias",
         P + "transform.dense.weight", P + "transform.dense.bias"]
 WORD = "bert.embeddings.word_embeddings.weight"
-
-
-def _st():
-    return C.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-def _p(t):
-    return None if t is None else t.data_ptr()
 
 
 # ------------------------------------------------------------------------------------------------ kernel
@@ -85,8 +73,8 @@ def test_layernorm_gelu_bwd_against_autograd(dtype, rows, H, variant):
     dz = torch.full((rows, H), 7.0, dtype=TDT[dtype], device="cuda")
     dgamma = torch.zeros(H, device="cuda"); dbeta = torch.zeros(H, device="cuda")
     dyc, xc, rc, zc, gc = dy.cuda(), xs.cuda(), rs.cuda(), zs.cuda(), gamma.cuda()
-    _capi.check(lib.realise_layernorm_gelu_bwd(_st(), DT[dtype], _p(dyc), _p(xc), _p(rc), _p(zc), _p(gc), _p(dz), _p(dgamma), _p(dbeta),
-                                               rows, H, _p(n_dev), _p(idx), saved_rows), "layernorm_gelu_bwd")
+    _capi.check(lib.realise_layernorm_gelu_bwd(stream(), DT[dtype], ptr(dyc), ptr(xc), ptr(rc), ptr(zc), ptr(gc), ptr(dz), ptr(dgamma), ptr(dbeta),
+                                               rows, H, ptr(n_dev), ptr(idx), saved_rows), "layernorm_gelu_bwd")
     torch.cuda.synchronize()
     tol = 2e-5 if dtype == "fp32" else 3e-2
     tol_p = 1e-4 if dtype == "fp32" else 3e-2
@@ -108,90 +96,32 @@ def test_layernorm_gelu_bwd_against_autograd(dtype, rows, H, variant):
 
 # ------------------------------------------------------------------------------------------------ whole model
 def _inputs(g):
-    cfg = RealiseConfig(num_hidden_layers=int(g["meta/n_layers"]), hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0,
-                        num_fonts=1, image_model_type=int(g["meta/image_model_type"]))
-    sd_np = init_state_dict_numpy(cfg, "arch3-mlm", seed=int(g["meta/seed"]), scheme="perturbed")
-    batch = synthetic_batch(int(g["meta/B"]), int(g["meta/S"]), seed=int(g["meta/seed"]), with_pho=True)
-    return cfg, sd_np, batch
-
-
-def _build(cls, cfg, sd_np, dtype, train):
-    m = cls(cfg, compute_dtype=dtype)
-    m.load_state_dict({k: torch.from_numpy(np.ascontiguousarray(x)) for k, x in sd_np.items()})
-    m.to("cuda")
-    m.train(train)
-    return m
-
-
-def _train_step(m, batch):
-    loss, logits = m(batch)
-    loss.backward()
-    torch.cuda.synchronize()
-    return loss.item(), logits, {n: p.grad.detach().clone() for n, p in m.named_parameters() if p.grad is not None}
-
-
-def _cos(a, b):
-    a, b = np.asarray(a, np.float64).ravel(), np.asarray(b, np.float64).ravel()
-    return float(a @ b / (np.linalg.norm(a) * np.linalg.norm(b) + 1e-30))
+    return variant_case_inputs(g, "arch3-mlm", num_fonts=1, image_model_type=int(g["meta/image_model_type"]))
 
 
 @pytest.mark.parametrize("name", ["mlm_b2s16_train", "mlm_img1_b2s16_train"])
 def test_train_step_fp32_matches_reference_and_bf16_within_band(golden_dir, name):
     g = load_golden(golden_dir, name)
     cfg, sd_np, batch = _inputs(g)
-    m = _build(SpellBertPho2ResArch3MLM, cfg, sd_np, "fp32", True)
-    loss, logits, grads = _train_step(m, batch)
-    print("loss %.6f (golden %.6f)" % (loss, float(g["loss"])))
-    assert abs(loss - float(g["loss"])) < 1e-4
-    check_summary(g, "logits", logits.float(), FP32_LOGIT_TOL)
-    ids = logits.argmax(-1).cpu().numpy().astype(np.int32)
-    sure = g["margin"] > 1e-4
-    assert sure.all()                                  # a case that leaves a position out is wrong
-    assert np.array_equal(ids[sure], g["argmax"][sure])
+    m = build_model(SpellBertPho2ResArch3MLM, cfg, sd_np, "fp32", True)
+    loss, logits, grads = train_step(m, batch)
+    assert (g["margin"] > 1e-4).all()                  # a case that leaves a position out is wrong
+    flip, checked, ref_none = check_train_fixture_fp32(g, m, loss, logits, grads)
+    assert len(ref_none) == 9
+    assert checked == len(grads)                       # the fixture holds every gradient this model has
+    assert set(HEAD) <= set(grads) and WORD in grads
     # the head's pre-activation and LayerNorm output (the default forward transforms every row)
     check_summary(g, "head_z", m.tap("head.z").float(), FP32_LOGIT_TOL, what="tap")
     check_summary(g, "head_y", m.tap("head.y").float(), FP32_LOGIT_TOL, what="tap")
     assert torch.isfinite(m.tap("head.d_in").float()).all() and m.tap("head.d_in").float().abs().max() > 0
-    near = [b for b in range(1, 6) if int(g.get("relu_near0/%d" % b, 0)) > 0]
-    flip_block = max(near) if near else 0
-    ref_none = {k[len("gradnone/"):] for k in g if k.startswith("gradnone/")}
-    ours_none = {n for n, p in m.named_parameters() if n not in grads}
-    assert ours_none == ref_none and len(ref_none) == 9
-    assert set(HEAD) <= set(grads) and WORD in grads
-    for n, gr in grads.items():
-        gk = "grad/" + n
-        assert gk + "/n" in g, n
-        if n.startswith("resnet.res_block") and int(n[len("resnet.res_block")]) <= flip_block:
-            s, _, abssum = sample_of(gr)
-            assert _cos(s, g[gk + "/sample"]) >= 0.96, n
-            assert abs(abssum - float(g[gk + "/abssum"])) <= 0.1 * float(g[gk + "/abssum"]), n
-            continue
-        check_summary(g, gk, gr, atol=2e-6 + 5e-3 * float(g[gk + "/abssum"]) / int(g[gk + "/n"]), what="grad(golden)")
-    sd = m.state_dict()
-    for k in g:
-        if k.startswith("buf/") and k.endswith("/n"):
-            name_ = k[len("buf/"):-len("/n")]
-            check_summary(g, "buf/" + name_, sd[name_].double(), 1e-4, what="buffer")
-    # bf16: against this fp32 engine run (tests/test_arch4_gpu.py bands)
-    mb = _build(SpellBertPho2ResArch3MLM, cfg, sd_np, "bf16", True)
-    lb, _, gb = _train_step(mb, batch)
-    print("bf16 loss %.6f" % lb)
-    assert abs(lb - loss) < 5e-2
-    assert set(gb) == set(grads)
-    cos = sorted((_cos(gb[n].float().cpu().numpy(), grads[n].cpu().numpy()), n) for n in grads
-                 if grads[n].numel() >= 64 and grads[n].abs().max() >= 1e-7)
-    print("bf16 worst cosines", cos[:4])
-    worst_other = min([c for c, n in cos if not n.startswith("resnet.")] or [1.0])
-    assert worst_other > 0.99, [x for x in cos if not x[1].startswith("resnet.")][:8]
-    flipped = [x for x in cos if x[1].startswith("resnet.res_block") and int(x[1][len("resnet.res_block")]) <= flip_block]
-    assert min([c for c, n in flipped] or [1.0]) > 0.94, flipped[:8]
-    assert min([x for x in cos if x not in flipped] or [(1.0, "")])[0] > 0.96, cos[:8]
+    # bf16: against this fp32 engine run
+    check_train_step_bf16(build_model(SpellBertPho2ResArch3MLM, cfg, sd_np, "bf16", True), batch, loss, grads, flip)
 
 
 def test_eval_forward_fp32_matches_reference_and_checkpoint_round_trip(golden_dir, tmp_path):
     g = load_golden(golden_dir, "mlm_b2s16_eval")
     cfg, sd_np, batch = _inputs(g)
-    m = _build(SpellBertPho2ResArch3MLM, cfg, sd_np, "fp32", False)
+    m = build_model(SpellBertPho2ResArch3MLM, cfg, sd_np, "fp32", False)
     with torch.no_grad():
         loss, logits = m(batch)
     print("loss %.6f (golden %.6f)" % (loss.item(), float(g["loss"])))
@@ -215,32 +145,11 @@ def test_eval_forward_fp32_matches_reference_and_checkpoint_round_trip(golden_di
 def test_live_row_step_equals_dense_step():
     """the bf16 training step over the live rows against the same step over every row: same loss, the transformer layers' weight
     gradients bit-identical - the head only ever sees the rows the classifier already saw"""
-    lib = _capi.load()
     cfg = RealiseConfig(num_hidden_layers=2, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0, num_fonts=1)
     sd_np = init_state_dict_numpy(cfg, "arch3-mlm", seed=12, scheme="perturbed")
-    batch = synthetic_batch(4, 32, seed=12)
-    res = []
-    for on in (2, 0):
-        lib.realise_set_engine(10, on)
-        try:
-            loss, _, grads = _train_step(_build(SpellBertPho2ResArch3MLM, cfg, sd_np, "bf16", True), batch)
-        finally:
-            lib.realise_set_engine(10, 2)
-        res.append((loss, {n: g for n, g in grads.items() if (".layer." in n or n in HEAD) and n.endswith("dense.weight")}))
-    assert res[0][0] == res[1][0]
-    assert res[0][1] and set(res[0][1]) == set(res[1][1]) and HEAD[4] in res[0][1]
-    for n in res[0][1]:
-        assert torch.equal(res[0][1][n], res[1][1][n]), n
-
-
-def _pinyin_batch(batch, tokenizer=None):
-    """build_batch stand-in (models.py:952-959 shape): a deterministic pinyin per id, lengths 1..4"""
-    ids = batch["src_idx"].reshape(-1)
-    lens = (ids % 4 + 1).to(torch.int64)
-    cols = torch.arange(4).unsqueeze(0)
-    batch["pho_idx"] = torch.where(cols < lens.unsqueeze(1), (ids.unsqueeze(1) + cols) % 32 + 1, torch.zeros_like(cols))
-    batch["pho_lens"] = lens.tolist()
-    return batch
+    same = check_live_row_step_equals_dense_step(SpellBertPho2ResArch3MLM, cfg, sd_np, synthetic_batch(4, 32, seed=12),
+                                                 keep=lambda n: ".layer." in n or n in HEAD)
+    assert HEAD[4] in same
 
 
 # gradients the backward accumulates with fp32 atomics (or, at these row counts, LayerNorm records folded by atomics): two runs of the
@@ -257,11 +166,11 @@ def test_trainer_steps_and_no_logits_forward_equals_default():
     sb = synthetic_batch(2, 16, seed=9, with_pho=False)
     items = [{"src_idx": sb["src_idx"][i].tolist(), "tgt_idx": sb["tgt_idx"][i].tolist(), "lengths": int(sb["lengths"][i])}
              for i in range(2)]
-    m = _build(SpellBertPho2ResArch3MLM, cfg, init_state_dict_numpy(cfg, "arch3-mlm", seed=9, scheme="perturbed"), "bf16", True)
+    m = build_model(SpellBertPho2ResArch3MLM, cfg, init_state_dict_numpy(cfg, "arch3-mlm", seed=9, scheme="perturbed"), "bf16", True)
     before = {k: m.state_dict()[k].clone() for k in (HEAD[1], HEAD[4])}
     log = []
     # one batch of two sentences, three epochs = three optimizer steps on the same sentences: AdamW must bring the loss down
-    trainer.train(m, items, batch_size=2, max_seq_length=16, epochs=3, lr=1e-4, build_batch=_pinyin_batch, logging_steps=1,
+    trainer.train(m, items, batch_size=2, max_seq_length=16, epochs=3, lr=1e-4, build_batch=pinyin_batch, logging_steps=1,
                   log_fn=log.append, seed=3)
     losses = [float(s.rsplit("Loss: ", 1)[1]) for s in log]
     print("losses", losses)
@@ -279,12 +188,12 @@ def test_trainer_steps_and_no_logits_forward_equals_default():
     w16 = after[HEAD[4]].to(torch.bfloat16)
     tail = kept[-2 * H * H * 2:].view(torch.bfloat16)
     assert torch.equal(tail[:H * H].view(H, H), w16) and torch.equal(tail[H * H:].view(H, H), w16.t().contiguous())
-    _capi.check(lib.realise_engine_refresh_shadows(m._engine, _st()), "refresh_shadows")
+    _capi.check(lib.realise_engine_refresh_shadows(m._engine, stream()), "refresh_shadows")
     torch.cuda.synchronize()
     assert torch.equal(kept[-2 * H * H * 2:], m._shadow[-2 * H * H * 2:])      # (the convolution weights' copies are re-derived by the next forward, not by the optimizer)
     # on the trained weights, the same step in both forms: the no-logits training forward (the transform over the compacted loss rows)
     # and the default one (the transform over every row, the backward reading the saved tensors through the row index)
-    batch = _pinyin_batch(trainer.make_features(items, 16))
+    batch = pinyin_batch(trainer.make_features(items, 16))
     out = []
     for train_logits in (False, True, True):
         m.train_logits = train_logits
@@ -316,7 +225,7 @@ def test_gradient_accumulation_through_the_loss_scalar(dtype, B, S):
                         num_fonts=1)
     sd_np = init_state_dict_numpy(cfg, "arch3-mlm", seed=21, scheme="perturbed")
     batch = synthetic_batch(B, S, seed=21)
-    m = _build(SpellBertPho2ResArch3MLM, cfg, sd_np, dtype, True)
+    m = build_model(SpellBertPho2ResArch3MLM, cfg, sd_np, dtype, True)
     m.zero_grad()
     m(batch)[0].backward()
     torch.cuda.synchronize()
@@ -341,20 +250,11 @@ def test_arch3_one_font_does_not_move_around_an_mlm_step(dtype):
     sd_np = init_state_dict_numpy(cfg, "arch3", seed=31, scheme="perturbed")
     sd_mlm = init_state_dict_numpy(cfg, "arch3-mlm", seed=31, scheme="perturbed")
     batch = synthetic_batch(4, 32, seed=31)
-    la, xa, ga = _train_step(_build(SpellBertPho2ResArch3, cfg, sd_np, dtype, True), batch)
-    ga2 = _train_step(_build(SpellBertPho2ResArch3, cfg, sd_np, dtype, True), batch)[2]
-    lm, xm, gm = _train_step(_build(SpellBertPho2ResArch3MLM, cfg, sd_mlm, dtype, True), batch)
-    lb, xb, gb = _train_step(_build(SpellBertPho2ResArch3, cfg, sd_np, dtype, True), batch)
+    la, xa, ga = train_step(build_model(SpellBertPho2ResArch3, cfg, sd_np, dtype, True), batch)
+    ga2 = train_step(build_model(SpellBertPho2ResArch3, cfg, sd_np, dtype, True), batch)[2]
+    lm, xm, gm = train_step(build_model(SpellBertPho2ResArch3MLM, cfg, sd_mlm, dtype, True), batch)
+    lb, xb, gb = train_step(build_model(SpellBertPho2ResArch3, cfg, sd_np, dtype, True), batch)
     assert lm != la and set(HEAD) <= set(gm)
     assert la == lb and torch.equal(xa, xb)
     assert set(ga) == set(gb)
-    for n in ga:
-        # tests/test_arch4_gpu.py: tensors behind fp32 atomics are held to the distance between two runs of the same model
-        atomics = ("embeddings" in n or n == "classifier.weight" or n.startswith("gate_net") or "layernorm" in n.lower()
-                   or n.startswith("resnet."))
-        if not atomics and torch.equal(ga[n], ga2[n]):
-            assert torch.equal(ga[n], gb[n]), n
-        else:
-            ref = (ga[n].float() - ga2[n].float()).norm().item()
-            d = (ga[n].float() - gb[n].float()).norm().item()
-            assert d <= 4.0 * ref + 1e-5 * ga[n].float().norm().item(), (n, d, ref)
+    check_gradients_unmoved(ga, ga2, gb)

@@ -1,5 +1,5 @@
 """CPU checks of image_model_type 1, the CharResNet1 glyph encoder (src/char_cnn.py:57-75; run.py:292,419-421): the C layout against
-the reference's state_dict (tests/golden/resnet1_state_dicts.json, tools/make_golden_resnet1.py) and tensor_specs, the type-0
+the reference's state_dict (tests/golden/resnet1_state_dicts.json, tools/make_golden_variants.py) and tensor_specs, the type-0
 layouts against the digests recorded before the field existed (tests/golden/layout_type0_digests.json), the config contract, the
 module shell without a GPU, the from_pretrained key report and the gradient-bucket order."""
 import hashlib
