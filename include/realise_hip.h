@@ -94,6 +94,11 @@ int realise_conv_tn(void* stream, int dtype, const void* A, int64_t lda, const r
  * q/k/v: [B*S][ldq] token-major, head h at columns 64h..64h+63; ctx [B*S][ldc]; lse [B][nh][S].
  * S <= 128: one workgroup per (batch, head), the whole score tile in registers; S > 128 (max_seq_length 256 / 512, run.py:304): tiles of
  * 128 keys / queries, the forward with a running row maximum and sum (B * nh * S * S < 2^32). */
+/* lse[b][h][q] = log sum_{k < S} exp(q.k / 8 + mask_add[b][k]) in fp32, the mask added as the FINITE number it is: a masked key keeps its
+ * term exp(.. - 10000), which underflows to an exact zero next to any live key, and a query whose every key is masked gets the softmax
+ * over q.k / 8 - 10000 (finite, as the reference's) - there is no -inf and no special case.  The backward recomputes the probabilities as
+ * exp(score - lse); rowdot[b][h][q] = sum_d dctx . ctx is its other saved row term (written for every q < S).  In a sentence with at
+ * least one live key the dk / dv rows of masked keys are exact zeros. */
 int realise_attention_fwd(void* stream, int dtype, const void* q, const void* k, const void* v, int64_t ldq,
                           const float* mask_add, void* ctx, int64_t ldc, float* lse, int B, int nh, int S,
                           uint32_t drop_seed, uint32_t drop_thresh, float drop_scale);
@@ -103,7 +108,10 @@ int realise_attention_bwd(void* stream, int dtype, const void* q, const void* k,
                           uint32_t drop_seed, uint32_t drop_thresh, float drop_scale);
 int realise_mask_to_additive(void* stream, const int64_t* masks, float* out, int n);
 
-/* torch.nn.LayerNorm over the last dim (eps inside the sqrt), y/xhat of `dtype`, rstd fp32. */
+/* torch.nn.LayerNorm over the last dim (eps inside the sqrt), y/xhat of `dtype`, rstd fp32.  Two-pass statistics in fp32 (mean, then the
+ * centred squares): a constant row gives xhat == 0 and y == beta exactly and rstd = 1 / sqrt(eps).  H % 4 == 0, H <= 1024.
+ * realise_layernorm_bwd: dx is written; dgamma / dbeta are ACCUMULATED (+=, fp32 atomics or an ordered fold) onto what the buffers hold -
+ * the caller zero-fills them once per step, not per call. */
 int realise_layernorm_fwd(void* stream, int dtype, const void* x, const float* gamma, const float* beta, float eps,
                           void* y, void* xhat, float* rstd, int rows, int H);
 int realise_layernorm_bwd(void* stream, int dtype, const void* dy, const void* xhat, const float* rstd,
@@ -120,7 +128,15 @@ int realise_layernorm_bwd(void* stream, int dtype, const void* dy, const void* x
 int realise_layernorm_gelu_bwd(void* stream, int dtype, const void* dy, const void* xhat, const float* rstd, const void* z,
                                const float* gamma, void* dz, float* dgamma, float* dbeta, int rows, int H,
                                const int32_t* n_rows_dev, const int32_t* row_index, int saved_rows);
-/* CrossEntropyLoss over rows with loss_mask == 1 (src/models.py:862-869); dlogits nullable. */
+/* CrossEntropyLoss over rows with loss_mask == 1 (src/models.py:862-869); dlogits nullable.  A row enters the loss when loss_mask == 1 and
+ * its label is not -100 (CrossEntropyLoss's default ignore_index): loss_out = the mean of those rows' terms, count_scratch[0] = how many,
+ * dlogits (rows of pitch ld, like logits) = (softmax - onehot) / count on those rows and exact zeros on every other row.  The row maximum
+ * is subtracted before the exponentials.  With ld > V the logits tail [V, ld) is never read and the dlogits tail [V, ld) is written as
+ * exact zeros, so a padded gradient row can feed a GEMM as it is.  EMPTY SELECTION: when no row enters the loss, loss_out = 0,
+ * count_scratch[0] = 0 and dlogits is all zeros - a deliberate difference from torch, whose mean over an empty selection is NaN (a
+ * step whose batch happens to hold no loss position then adds a zero gradient instead of poisoning the weights).  Through this entry
+ * point the rows' terms are added to loss_out by fp32 atomics: the loss is reproducible to rounding, not to the bit (the engine's
+ * ordered fold is).  tests/test_row_edges_gpu.py pins all of this. */
 int realise_masked_ce(void* stream, int dtype, const void* logits, int64_t ld, const int64_t* labels,
                       const int64_t* loss_mask, int rows, int V, float* loss_out, float* count_scratch, void* dlogits);
 

@@ -95,6 +95,16 @@ def train_step(m, batch):
     return loss.item(), logits, {n: p.grad.detach().clone() for n, p in m.named_parameters() if p.grad is not None}
 
 
+def close(out, ref, tol, what):
+    """one bar per tensor (tests/test_kernels_gpu.py): max|out - ref| <= tol * max|ref|"""
+    out = out.float().cpu()
+    ref = ref.float().cpu()
+    scale = ref.abs().max().item() + 1e-12
+    err = (out - ref).abs().max().item()
+    assert np.isfinite(err), what + ": non-finite output"
+    assert err <= tol * scale, "%s: max err %.3e > %.1e * scale %.3e" % (what, err, tol, scale)
+
+
 def cosine(a, b):
     a, b = np.asarray(a, np.float64).ravel(), np.asarray(b, np.float64).ravel()
     return float(a @ b / (np.linalg.norm(a) * np.linalg.norm(b) + 1e-30))
@@ -219,3 +229,74 @@ def check_gradients_unmoved(ga, ga2, gb):
             ref = (ga[n].float() - ga2[n].float()).norm().item()
             d = (ga[n].float() - gb[n].float()).norm().item()
             assert d <= 4.0 * ref + 1e-5 * ga[n].float().norm().item(), (n, d, ref)
+
+
+# ------------------------------------------------------------------------------------------------ element-wise comparison of row kernels
+# (tests/test_row_edges_gpu.py, tests/test_compare_helpers_cpu.py; DESIGN section 3, "Element-wise bars of the row kernels")
+# A row kernel's outputs span orders of magnitude (a cross-entropy gradient row: one entry of 1 / n next to 21127 of softmax / n), so one
+# bar per tensor sees only the largest.  Here every element has its own bar  u * cond_terms + TINY  built from the float64 reference's
+# own terms: cond_terms = the sum of the absolute values of the terms the reference adds to produce that element.
+U_FP32 = 1e-4               # the project's fp32 bar (tests/test_kernels_gpu.py), now per element; also every fp32 output of a bf16 run
+U_BF16 = 2.0 ** -8          # an output stored in bf16: its one rounding (bf16 keeps 8 significand bits: unit roundoff 2^-8) and nothing more
+TINY = 1e-30                # only keeps exact zeros comparable
+EPS32 = 2.0 ** -24          # unit roundoff of fp32
+GUARD = 64                  # sentinel elements in front of and behind a guarded buffer
+
+
+def u_stored(dt):
+    """u of an output stored in the run's dtype"""
+    return U_BF16 if dt == "bf16" else U_FP32
+
+
+def elem_bound(u, cond_terms):
+    return u * cond_terms.to(torch.float64).abs() + TINY
+
+
+def close_elementwise(out, ref64, bound64, what):
+    """|out - ref64| <= bound64 for EVERY element (float64 on the CPU; a non-finite output never passes).  Returns the worst
+    error / bound ratio; the failure names the worst element's index, value, reference and bound."""
+    assert ref64.dtype == torch.float64 and bound64.dtype == torch.float64, what + ": reference and bound are float64"
+    o = out.detach().to("cpu", torch.float64)
+    ref = ref64.detach().cpu()
+    assert o.shape == ref.shape, "%s: shape %s against reference %s" % (what, tuple(o.shape), tuple(ref.shape))
+    bound = bound64.detach().cpu().expand_as(ref)
+    err = (o - ref).abs()
+    ratio = torch.where(torch.isfinite(err), err / bound, torch.full_like(err, float("inf")))
+    if ratio.numel() == 0:
+        return 0.0
+    if not bool((err <= bound).all()):
+        flat = int(torch.where(err <= bound, torch.zeros_like(ratio), ratio).reshape(-1).argmax())
+        idx = tuple(int(i) for i in np.unravel_index(flat, tuple(ref.shape))) if ref.dim() else ()
+        n_bad = int((~(err <= bound)).sum())
+        raise AssertionError("%s: %d of %d elements beyond their bar; worst at %s: got %.9e, reference %.9e, |diff| %.3e > bound %.3e"
+                             % (what, n_bad, ref.numel(), idx, o.reshape(-1)[flat].item(), ref.reshape(-1)[flat].item(),
+                                err.reshape(-1)[flat].item(), bound.reshape(-1)[flat].item()))
+    return float(ratio.max())
+
+
+_BITS = {1: torch.int8, 2: torch.int16, 4: torch.int32, 8: torch.int64}
+
+
+def guarded(shape, dtype, fill, device=None):
+    """An output buffer with GUARD sentinel elements in front and behind: returns (view of `shape` filled with `fill`, check) where
+    check(what) asserts that both guards are bit-unchanged.  The view starts GUARD elements into the allocation (128 bytes or more:
+    every alignment the kernels ask for)."""
+    if device is None:
+        device = "cuda" if torch.cuda.is_available() else "cpu"
+    shape = (shape,) if isinstance(shape, int) else tuple(shape)
+    n = int(np.prod(shape)) if shape else 1
+    buf = torch.empty(n + 2 * GUARD, dtype=dtype, device=device)
+    sentinel = -24320.0 if dtype.is_floating_point else -23131       # (exact in bf16; nothing a kernel here would write)
+    buf[:GUARD] = sentinel
+    buf[GUARD + n:] = sentinel
+    buf[GUARD:GUARD + n] = fill
+    bits = _BITS[buf.element_size()]
+    want = buf[:GUARD].view(bits).cpu().clone()
+
+    def check(what):
+        for name, g in (("in front of", buf[:GUARD]), ("behind", buf[GUARD + n:])):
+            got = g.view(bits).cpu()
+            if not torch.equal(got, want):
+                k = int((got != want).nonzero()[0])
+                raise AssertionError("%s: guard element %d %s the buffer was overwritten (now %r)" % (what, k, name, g[k].item()))
+    return buf[GUARD:GUARD + n].view(shape), check
