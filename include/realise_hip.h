@@ -26,7 +26,12 @@ extern "C" {
  * ---------------------------------------------------------------------------------------- */
 
 /* Epilogue of realise_gemm_nt / realise_conv_nt.  mode: 0 store(+bias,+accumulate), 1 bias+erf-GELU
- * (out2 = pre-activation), 2 dropout(acc+bias)+aux (residual), 4 acc * gelu'(aux). */
+ * (out2 = pre-activation), 2 dropout(acc+bias)+aux (residual), 4 acc * gelu'(aux).
+ * The mode-2 mask is recomputed from a counter, never stored: element (row, col) of the M x N output has the counter
+ * idx = (row * N + col) mod 2^32 - N the logical width, not the pitch ldo, and row the ORIGINAL row of the output (the live-row
+ * launch forms address a listed row by its position in the matrix, not in the list) - and is kept when the 16-bit lane idx & 3 of
+ * the hash of quad idx >> 2 is >= drop_thresh >> 16 (drop_thresh == 0: everything is kept, unscaled).  The LayerNorm backward
+ * (realise_layernorm_bwd_ex, dx_drop) applies the same mask with N = H. */
 typedef struct {
   int32_t mode;
   int32_t accumulate;

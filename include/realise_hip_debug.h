@@ -43,7 +43,14 @@ void realise_set_engine(int key, int value);
  * overwrite != 0: out = result instead of out += result. */
 /* realise_gemm_nt bounded by a DEVICE-side row count, as the GRU steps of a device-built batch launch it: rows at or beyond
  * *rows_dev contribute zeros (an accumulating epilogue leaves them unchanged, a storing one writes bias-only rows in the last live
- * tile and nothing beyond it). */
+ * tile and nothing beyond it).  The contract as observed on both kernels a bf16 launch can reach (tests/test_gemm_edges_gpu.py,
+ * counts 0, 1, 128, 129, M - 1, M; the A rows at or beyond the count hold NaN and are never read into anything):
+ *   8-wave 128 x 192 with exact row masking (M >= 1024, N >= 256, K % 64 == 0; realise_debug_nt_path 11) and the 4-wave 128-row
+ *   tiles (every other shape; paths 2 / 3), alike: rows below the count are the dense launch's; with accumulate every row at or
+ *   beyond the count keeps its bits; without it the rows from the count to the end of the 128-row tile that holds the last live row
+ *   (or to M) are overwritten with the bias-only row alpha * 0 + bias - finite whatever A holds there -, and every row of a later
+ *   tile, every row when the count is 0, keeps what it held.  A caller that reads rows beyond the count after a storing launch
+ *   must expect either. */
 int realise_gemm_nt_rows(void* stream, int dtype, const void* A, int64_t lda, const void* B, int64_t ldb, int M, int N, int K,
                          const realise_epilogue* ep, const int* rows_dev);
 /* realise_gemm_nt (bf16, K % 64 == 0, M % 16 == 0) over a device-side LIST of 16-row blocks, as a training step launches the layer GEMMs of
@@ -144,6 +151,14 @@ int realise_profile_dump_ex(int kernel_family, int max_records, float* ms_out, d
 /* Host-side support predicate of the listed weight-gradient launches, exported so that a CPU test can pin it: bytes of LDS a listed
  * TN launch reserves for `entries` live blocks, -1 when the list does not fit (the engine then runs dense reductions). */
 int realise_debug_tn_list_lds(int64_t entries);
+/* Which kernel realise_gemm_nt (rows_dev_given = 0) or realise_gemm_nt_rows (1) reaches for a shape, an epilogue (alpha = 1) and the
+ * knobs as they stand (realise_set_nt_variant, realise_set_nt_allow_n96): the host function the launcher itself acts on, exported so
+ * that tests can pin the kernel a case is meant for.  -1 refused (argument error), 0 nothing to launch; 4-wave kernels: 1 256 x 64,
+ * 2 128 x 128, 3 128 x 96, 4 256 x 128 with spread fetches; 8-wave kernels: 5 256 x 192, 6 128 x 192 three-stage, 7 128 x 192
+ * two-per-CU, 8 the ragged-K instantiation; 9 persistent 256 x 192, 10 the same bounded by the device-side row count; 11 8-wave
+ * 128 x 192 two-per-CU with exact row masking under a device-side row count. */
+int realise_debug_nt_path(int dtype, int M, int N, int K, int mode, int accumulate, int has_aux, int64_t lda, int64_t ldb, int64_t ldo,
+                          int64_t ldaux, int rows_dev_given);
 
 /* how many workspace plans the engine has installed (= whole-workspace zero fills) since it was created: a loop that alternates
  * batch shapes over per-shape workspace buffers (realise_engine_forget_workspace in realise_hip.h) must count one per shape */

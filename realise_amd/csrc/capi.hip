@@ -515,6 +515,17 @@ int realise_engine_bind(realise_engine* e, void* shadow, void* workspace, int64_
   return e ? e->impl->bind(shadow, workspace, workspace_bytes) : RL_ERR_ARG;
 }
 int realise_debug_tn_list_lds(int64_t entries) { return tn_list_lds_bytes(entries); }
+int realise_debug_nt_path(int dtype, int M, int N, int K, int mode, int accumulate, int has_aux, int64_t lda, int64_t ldb, int64_t ldo,
+                          int64_t ldaux, int rows_dev_given) {
+  static const uint64_t some_operand[2] = {0, 0};      // (only compared with nullptr)
+  realise_epilogue e;
+  memset(&e, 0, sizeof(e));
+  e.mode = mode; e.accumulate = accumulate; e.out = (void*)some_operand; e.ldo = ldo; e.aux = has_aux ? (const void*)some_operand : nullptr;
+  e.ldaux = ldaux; e.alpha = 1.0f; e.drop_scale = 1.0f;
+  if (dtype == REALISE_BF16) return gemm_nt_path<bf16_t>(M, N, K, to_epi<bf16_t>(&e), lda, ldb, rows_dev_given != 0);
+  if (dtype == REALISE_F32) return gemm_nt_path<float>(M, N, K, to_epi<float>(&e), lda, ldb, rows_dev_given != 0);
+  return NT_PATH_REFUSED;
+}
 int64_t realise_engine_plan_installs(const realise_engine* e) { return e ? e->impl->plan_install_count() : -1; }
 void realise_engine_forget_workspace(realise_engine* e, void* workspace) { if (e) e->impl->forget_workspace(workspace); }
 int realise_engine_refresh_shadows(realise_engine* e, void* stream) { return e ? e->impl->refresh_shadows((hipStream_t)stream) : RL_ERR_ARG; }

@@ -417,6 +417,18 @@ void set_nt8_live_gc(int gc);      // live-row GEMMs: 0 (default) column groups 
 void set_nt8p_order(int o);
 int gemm_nt8(hipStream_t st, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, int M, int N, int K,
              const EpiParams<bf16_t>& ep, int tile);
+int nt8_tile(int N, int K, int tile);      // the tile gemm_nt8 runs for `tile` (2 / 4 / 6), 8: the ragged-K instantiation
+// Which kernel gemm_nt / realise_gemm_nt_rows reaches (realise_debug_nt_path): the choice launch_nt itself acts on, as a pure host function
+enum NtPath {
+  NT_PATH_REFUSED = -1,      // RL_ERR_ARG
+  NT_PATH_NONE = 0,          // an empty problem: nothing is launched
+  NT_PATH_4W_256x64 = 1, NT_PATH_4W_128x128 = 2, NT_PATH_4W_128x96 = 3, NT_PATH_4W_256x128 = 4,       // gemm.hip (256x128: 8 waves, fetches spread)
+  NT_PATH_8W_256x192 = 5, NT_PATH_8W_128x192 = 6, NT_PATH_8W_128x192Q = 7, NT_PATH_8W_KTAIL = 8,      // gemm_nt8.hip
+  NT_PATH_8P = 9, NT_PATH_8P_MDEV = 10,                                                               // gemm_nt8p.hip
+  NT_PATH_8W_MEXACT = 11,    // gemm_nt8.hip, 128x192 two-per-CU bounded by a device-side row count with exact row masking
+};
+template <typename T>
+int gemm_nt_path(int M, int N, int K, const EpiParams<T>& ep, int64_t lda, int64_t ldb, bool rows_dev);
 void set_nt8_group_m(int g);       // tile order of the 8-wave NT kernels: 0/1 row-major, g > 1: g tile rows per column step (L2 blocking)
 
 void tn_fold_launch(hipStream_t st, const TnEpi& ep, int nsplit, int I, int J);     // out += alpha * sum of the split slabs, fixed order

@@ -261,12 +261,13 @@ static int launch_nt_tile(hipStream_t st, const ALoader& la, const DenseLoader<T
   return hipGetLastError() == hipSuccess ? RL_OK : RL_ERR_LAUNCH;
 }
 
-template <typename T, typename ALoader>
-static int launch_nt(hipStream_t st, const ALoader& la, const T* B, int64_t ldb, int M, int N, int K, const EpiParams<T>& ep) {
-  if (M <= 0 || N <= 0 || K <= 0) return RL_OK;
-  if ((N & 3) || (K % Geo<T>::VEC) || (ldb % Geo<T>::VEC)) return RL_ERR_ARG;
-  DenseLoader<T> lb{B, ldb, N, K};
-  if (N <= 64) return launch_nt_tile<T, ALoader, 4, 1>(st, la, lb, M, N, K, ep);
+// Which kernel a launch reaches: ONE pure host function of the shape, the epilogue and the knobs (g_nt_variant, g_nt_n96), called by
+// launch_nt itself and exported as realise_debug_nt_path (NtPath, gemm.h) so that a test can pin the choice it relies on.
+template <typename T>
+static int nt_path(bool dense, bool rows_dev, int M, int N, int K, const EpiParams<T>& ep, int64_t lda, int64_t ldb) {
+  if (M <= 0 || N <= 0 || K <= 0) return NT_PATH_NONE;
+  if ((N & 3) || (K % Geo<T>::VEC) || (ldb % Geo<T>::VEC)) return NT_PATH_REFUSED;
+  if (N <= 64) return NT_PATH_4W_256x64;
   // Tile width by chip balance: 256 CUs x 2 resident workgroups.  The column count per tile (128 or 96) is chosen to
   // minimise  width x f(tiles per CU)  with f(1) = 1 and f(n) = 0.75 n (two co-resident tiles overlap each other's
   // stalls): e.g. M = 8192, N = 768 -> 8 x 96 columns = 512 tiles, two per CU on every CU, instead of 384 tiles of
@@ -276,51 +277,100 @@ static int launch_nt(hipStream_t st, const ALoader& la, const T* B, int64_t ldb,
     const long tpc = (tiles + 255) / 256;
     return bn * (tpc == 1 ? 1.0 : 0.75 * (double)tpc);
   };
-  if constexpr (sizeof(typename ALoader::KPos) == sizeof(typename DenseLoader<T>::KPos) && sizeof(T) == 2) {
-    // Production path for the big dense GEMMs: the ping-pong 8-wave kernel (gemm_nt8.hip), tile by chip fill.  Variants 12 / 14 / 16
-    // force one of its tiles, variant 9 forces the 4-wave kernel below (tools/nt8_probe.cpp).
-    // Wide outputs (qkv, FFN-up + GELU, FFN-down data gradient + GELU', the classifier: >= 1.5 tiles of 256 x 192 per CU): the persistent
-    // kernel, whose register epilogue and next-tile prologue overlap what the one-tile kernels leave exposed (gemm_nt8p.hip).
-    // Variant 50 forces it wherever it is supported, variant 51 keeps it off.
-    if (la.rows_dev == nullptr && (g_nt_variant == 50 || (g_nt_variant == 0 && M >= 1024 && (long)((M + 255) / 256) * ((N + 191) / 192) >= 384)) &&
-        nt8p_supported(M, N, K, ep, la.ld, ldb))
-      return gemm_nt8p(st, la.base, la.ld, B, ldb, M, N, K, ep);
-    if (ep.out_f32 != nullptr) return RL_ERR_ARG;        // (the fp32 copy exists in the persistent kernel's epilogue only: the caller casts)
-    if (la.rows_dev == nullptr && ((g_nt_variant == 0 && M >= 1024 && N >= 256) || (g_nt_variant != 0 && g_nt_variant != 9))) {
-      if (nt8_supported(M, N, K, ep, la.ld, ldb)) return gemm_nt8(st, la.base, la.ld, B, ldb, M, N, K, ep, (g_nt_variant >= 12 && g_nt_variant <= 16) ? g_nt_variant - 10 : 0);
+  if constexpr (sizeof(T) == 2) {
+    if (dense) {
+      // Production path for the big dense GEMMs: the ping-pong 8-wave kernel (gemm_nt8.hip), tile by chip fill.  Variants 12 / 14 / 16
+      // force one of its tiles, variant 9 forces the 4-wave kernel below (tools/nt8_probe.cpp).
+      // Wide outputs (qkv, FFN-up + GELU, FFN-down data gradient + GELU', the classifier: >= 1.5 tiles of 256 x 192 per CU): the persistent
+      // kernel, whose register epilogue and next-tile prologue overlap what the one-tile kernels leave exposed (gemm_nt8p.hip).
+      // Variant 50 forces it wherever it is supported, variant 51 keeps it off.
+      const bool wide_out = M >= 1024 && (long)((M + 255) / 256) * ((N + 191) / 192) >= 384;
+      if (!rows_dev && (g_nt_variant == 50 || (g_nt_variant == 0 && wide_out)) && nt8p_supported(M, N, K, ep, lda, ldb)) return NT_PATH_8P;
+      if (ep.out_f32 != nullptr) return NT_PATH_REFUSED;   // (the fp32 copy exists in the persistent kernel's epilogue only: the caller casts)
+      if (!rows_dev && ((g_nt_variant == 0 && M >= 1024 && N >= 256) || (g_nt_variant != 0 && g_nt_variant != 9))) {
+        if (nt8_supported(M, N, K, ep, lda, ldb)) {
+          switch (nt8_tile(N, K, (g_nt_variant >= 12 && g_nt_variant <= 16) ? g_nt_variant - 10 : 0)) {
+            case 2: return NT_PATH_8W_256x192;
+            case 4: return NT_PATH_8W_128x192;
+            case 6: return NT_PATH_8W_128x192Q;
+            case 8: return NT_PATH_8W_KTAIL;
+            default: return NT_PATH_REFUSED;
+          }
+        }
+      }
+      // a device-side row bound on a wide output (round 6: the training classifier over the loss rows): the persistent kernel, which
+      // shrinks its tile walk to the live tile rows on the device
+      if (rows_dev && ep.m_dev == nullptr && g_nt_variant == 0 && wide_out && nt8p_supported(M, N, K, ep, lda, ldb)) return NT_PATH_8P_MDEV;
+      // a device-side row bound (the GRU steps of a device-built batch: nominal M = B*S, the alive count lives on the device): the
+      // 8-wave kernel with exact row masking - tiles beyond the count leave at once, rows beyond it inside the last live tile read zeros
+      if (rows_dev && ep.m_dev == nullptr && g_nt_variant == 0 && M >= 1024 && N >= 256 && (K % 64) == 0 && nt8_supported(M, N, K, ep, lda, ldb))
+        return NT_PATH_8W_MEXACT;
+      // very wide outputs (the 21128-column classifier: > 20 rounds of 128x128 tiles): 8-wave 256x128 tiles cut the
+      // operand traffic per flop by a third; three stages and the fetches spread between the MFMA groups keep the single
+      // resident workgroup fed (730 vs 644 TF, tools/nt_probe.cpp).  Below ~8 rounds the 4-wave tiles win.
+      if ((long)((M + 127) / 128) * ((N + 127) / 128) >= 4096 && (K % Geo<T>::BK) == 0) return NT_PATH_4W_256x128;
     }
-    // a device-side row bound on a wide output (round 6: the training classifier over the loss rows): the persistent kernel, which
-    // shrinks its tile walk to the live tile rows on the device
-    if (la.rows_dev != nullptr && ep.m_dev == nullptr && g_nt_variant == 0 && M >= 1024 &&
-        (long)((M + 255) / 256) * ((N + 191) / 192) >= 384 && nt8p_supported(M, N, K, ep, la.ld, ldb)) {
-      EpiParams<T> e2 = ep;
-      e2.m_dev = la.rows_dev;
-      return gemm_nt8p(st, la.base, la.ld, B, ldb, M, N, K, e2);
-    }
-    // a device-side row bound (the GRU steps of a device-built batch: nominal M = B*S, the alive count lives on the device): the
-    // 8-wave kernel with exact row masking - tiles beyond the count leave at once, rows beyond it inside the last live tile read zeros
-    if (la.rows_dev != nullptr && ep.m_dev == nullptr && g_nt_variant == 0 && M >= 1024 && N >= 256 && (K % 64) == 0 &&
-        nt8_supported(M, N, K, ep, la.ld, ldb)) {
-      EpiParams<T> e2 = ep;
-      e2.m_dev = la.rows_dev; e2.m_exact = 1;
-      return gemm_nt8(st, la.base, la.ld, B, ldb, M, N, K, e2, 0);
-    }
-    // very wide outputs (the 21128-column classifier: > 20 rounds of 128x128 tiles): 8-wave 256x128 tiles cut the
-    // operand traffic per flop by a third; three stages and the fetches spread between the MFMA groups keep the single
-    // resident workgroup fed (730 vs 644 TF, tools/nt_probe.cpp).  Below ~8 rounds the 4-wave tiles win.
-    if ((long)((M + 127) / 128) * ((N + 127) / 128) >= 4096 && (K % Geo<T>::BK) == 0)
-      return launch_nt_tile<T, ALoader, 4, 2, 3, 4, true>(st, la, lb, M, N, K, ep);
   }
-  if (g_nt_n96 && cost(96) < cost(128)) return launch_nt_tile<T, ALoader, 2, 2, 2, 3>(st, la, lb, M, N, K, ep);
-  return launch_nt_tile<T, ALoader, 2, 2>(st, la, lb, M, N, K, ep);
+  if (g_nt_n96 && cost(96) < cost(128)) return NT_PATH_4W_128x96;
+  return NT_PATH_4W_128x128;
 }
+
+template <typename T, typename ALoader>
+static int launch_nt(hipStream_t st, const ALoader& la, const T* B, int64_t ldb, int M, int N, int K, const EpiParams<T>& ep) {
+  constexpr bool kDense = sizeof(typename ALoader::KPos) == sizeof(typename DenseLoader<T>::KPos);
+  int64_t lda = 0;
+  if constexpr (kDense) lda = la.ld;
+  const int path = nt_path<T>(kDense, la.rows_dev != nullptr, M, N, K, ep, lda, ldb);
+  if (path == NT_PATH_NONE) return RL_OK;
+  if (path == NT_PATH_REFUSED) return RL_ERR_ARG;
+  DenseLoader<T> lb{B, ldb, N, K};
+  if constexpr (kDense && sizeof(T) == 2) {
+    switch (path) {
+      case NT_PATH_8P: return gemm_nt8p(st, la.base, la.ld, B, ldb, M, N, K, ep);
+      case NT_PATH_8W_256x192: case NT_PATH_8W_128x192: case NT_PATH_8W_128x192Q: case NT_PATH_8W_KTAIL:
+        return gemm_nt8(st, la.base, la.ld, B, ldb, M, N, K, ep, (g_nt_variant >= 12 && g_nt_variant <= 16) ? g_nt_variant - 10 : 0);
+      case NT_PATH_8P_MDEV: {
+        EpiParams<T> e2 = ep;
+        e2.m_dev = la.rows_dev;
+        return gemm_nt8p(st, la.base, la.ld, B, ldb, M, N, K, e2);
+      }
+      case NT_PATH_8W_MEXACT: {
+        EpiParams<T> e2 = ep;
+        e2.m_dev = la.rows_dev; e2.m_exact = 1;
+        return gemm_nt8(st, la.base, la.ld, B, ldb, M, N, K, e2, 0);
+      }
+      case NT_PATH_4W_256x128: return launch_nt_tile<T, ALoader, 4, 2, 3, 4, true>(st, la, lb, M, N, K, ep);
+      default: break;
+    }
+  }
+  switch (path) {
+    case NT_PATH_4W_256x64: return launch_nt_tile<T, ALoader, 4, 1>(st, la, lb, M, N, K, ep);
+    case NT_PATH_4W_128x96: return launch_nt_tile<T, ALoader, 2, 2, 2, 3>(st, la, lb, M, N, K, ep);
+    case NT_PATH_4W_128x128: return launch_nt_tile<T, ALoader, 2, 2>(st, la, lb, M, N, K, ep);
+    default: return RL_ERR_ARG;
+  }
+}
+
+// the argument checks of gemm_nt, then the choice of launch_nt (dense operands)
+template <typename T>
+static bool gemm_nt_args_ok(int64_t lda, const EpiParams<T>& ep) {
+  if (lda % Geo<T>::VEC) return false;
+  if (ep.out_f32 != nullptr && sizeof(T) != 2) return false;
+  if (ep.col_scale != nullptr && ep.mode != EPI_AFFINE) return false;
+  return true;
+}
+template <typename T>
+int gemm_nt_path(int M, int N, int K, const EpiParams<T>& ep, int64_t lda, int64_t ldb, bool rows_dev) {
+  if (!gemm_nt_args_ok<T>(lda, ep)) return NT_PATH_REFUSED;
+  return nt_path<T>(true, rows_dev, M, N, K, ep, lda, ldb);
+}
+template int gemm_nt_path<bf16_t>(int, int, int, const EpiParams<bf16_t>&, int64_t, int64_t, bool);
+template int gemm_nt_path<float>(int, int, int, const EpiParams<float>&, int64_t, int64_t, bool);
 
 template <typename T>
 int gemm_nt(hipStream_t st, const T* A, int64_t lda, const T* B, int64_t ldb, int M, int N, int K, const EpiParams<T>& ep,
             const int* rows_dev) {
-  if (lda % Geo<T>::VEC) return RL_ERR_ARG;
-  if (ep.out_f32 != nullptr && sizeof(T) != 2) return RL_ERR_ARG;
-  if (ep.col_scale != nullptr && ep.mode != EPI_AFFINE) return RL_ERR_ARG;
+  if (!gemm_nt_args_ok<T>(lda, ep)) return RL_ERR_ARG;
   DenseLoader<T> la{A, lda, M, K};
   la.rows_dev = rows_dev;
   return launch_nt<T, DenseLoader<T>>(st, la, B, ldb, M, N, K, ep);

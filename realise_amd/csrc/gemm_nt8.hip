@@ -567,18 +567,24 @@ int gemm_nt8_splitk(hipStream_t st, const bf16_t* A, int64_t lda, const bf16_t* 
   return launch_nt8_cfg<Cfg128x192q>(st, A, lda, B, ldb, M, N, K, ep);
 }
 
-// tile: 0 = from the shape, 2 = 256x192, 4 = 128x192 (three stages), 6 = 128x192 two workgroups per CU
-int gemm_nt8(hipStream_t st, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, int M, int N, int K,
-             const EpiParams<bf16_t>& ep, int tile) {
-  if (!nt8_supported(M, N, K, ep, lda, ldb)) return RL_ERR_ARG;
-  if (K % 64) return launch_nt8_cfg<Cfg128x192, true>(st, A, lda, B, ldb, M, N, K, ep);     // ragged K: one tile shape carries the tail code
+// tile: 0 = from the shape, 2 = 256x192, 4 = 128x192 (three stages), 6 = 128x192 two workgroups per CU.  Returns the tile that runs;
+// 8: the ragged-K instantiation (one tile shape, 128x192 three stages, carries the tail code)
+int nt8_tile(int N, int K, int tile) {
+  if (K % 64) return 8;
   // outputs up to a few thousand columns: the two-workgroups-per-CU shape.  Its smaller tile fetches 43 % more bytes per flop
   // than 256x192, but the second workgroup's MFMAs run under the first one's output write (a third of a K = 768 GEMM's time with
   // one workgroup per CU) and under its fetch waits: qkv 39.6 -> 35.0 us, ffn1+GELU 56.1 -> 51.3, attn-out 14.6 -> 14.3, the
   // K = 2304 / 3072 shapes equal (tools/nt8_probe.cpp ws, profiles/round2_nt8_probe.log).  Wider outputs the persistent kernel does
   // not take: 256 x 192, one workgroup per CU.
   if (tile == 0) tile = N < 4096 ? 6 : 2;
-  switch (tile) {
+  return tile;
+}
+
+int gemm_nt8(hipStream_t st, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, int M, int N, int K,
+             const EpiParams<bf16_t>& ep, int tile) {
+  if (!nt8_supported(M, N, K, ep, lda, ldb)) return RL_ERR_ARG;
+  switch (nt8_tile(N, K, tile)) {
+    case 8: return launch_nt8_cfg<Cfg128x192, true>(st, A, lda, B, ldb, M, N, K, ep);
     case 2: return launch_nt8_cfg<Cfg256x192>(st, A, lda, B, ldb, M, N, K, ep);
     case 6: return launch_nt8_cfg<Cfg128x192q>(st, A, lda, B, ldb, M, N, K, ep);
     case 4: return launch_nt8_cfg<Cfg128x192>(st, A, lda, B, ldb, M, N, K, ep);

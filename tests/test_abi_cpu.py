@@ -30,6 +30,16 @@ def test_library_exports_every_declared_symbol():
     assert b"gfx950" in lib.realise_version()
 
 
+def test_debug_nt_path_answers_without_a_gpu():
+    """realise_debug_nt_path (include/realise_hip_debug.h) is a pure host function: ids -1 (refused) .. 11; the shapes are pinned in
+    tests/test_gemm_cases_cpu.py"""
+    lib = _capi.load()
+    assert lib.realise_debug_nt_path(_capi.BF16, 128, 128, 64, 0, 0, 0, 64, 64, 128, 128, 0) in (2, 3)
+    assert lib.realise_debug_nt_path(_capi.F32, 128, 60, 64, 0, 0, 0, 64, 64, 60, 60, 0) == 1
+    assert lib.realise_debug_nt_path(_capi.BF16, 128, 128, 64, 0, 0, 0, 63, 64, 128, 128, 0) == -1          # lda % 8
+    assert lib.realise_debug_nt_path(7, 128, 128, 64, 0, 0, 0, 64, 64, 128, 128, 0) == -1                   # no such dtype
+
+
 @pytest.mark.parametrize("model_type,count", [("arch3", 427), ("bert", 201)])
 def test_layout_matches_reference_state_dict(model_type, count):
     cfg = RealiseConfig()

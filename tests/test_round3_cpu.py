@@ -3,21 +3,7 @@ drop_mult) restated in numpy - keep rate, uniformity of the 16-bit lanes, indepe
 across seeds (the reference uses torch's Philox dropout, transformers/modeling_bert.py:190,253,276,342; only the statistics can match)."""
 import numpy as np
 
-M32 = np.uint64(0xFFFFFFFF)
-
-
-def rng_hash4(seed, quad):
-    seed, quad = np.uint64(seed), quad.astype(np.uint64)
-    m1 = ((quad ^ seed) & M32) * np.uint64(0x9E3779B1)
-    x = ((m1 & M32) ^ (m1 >> np.uint64(32)) ^ ((seed * np.uint64(0x632BE5AB)) & M32)) & M32
-    m2 = x * np.uint64(0x85EBCA77)
-    m3 = ((x ^ np.uint64(0x27D4EB2F)) & M32) * np.uint64(0xC2B2AE3D)
-    return ((m2 >> np.uint64(32)) ^ (m3 & M32)) & M32, ((m3 >> np.uint64(32)) ^ (m2 & M32)) & M32
-
-
-def lanes16(seed, n):
-    o0, o1 = rng_hash4(seed, np.arange(n // 4, dtype=np.uint64))
-    return np.stack([o0 & np.uint64(0xFFFF), o0 >> np.uint64(16), o1 & np.uint64(0xFFFF), o1 >> np.uint64(16)], 1).reshape(-1).astype(np.int64)
+from gemm_cases import lanes16
 
 
 def test_dropout_mixer_statistics():
