@@ -73,7 +73,12 @@ int realise_conv_dgrad_s2(void* stream, int dtype, const realise_conv_geom* a, c
                           const realise_epilogue* ep);
 /* out[I,J] += sum_p A[p,i] * B[p,j] (fp32) - nn.Linear weight gradient.  The reduction over p is split
  * over workgroups; `scratch` (fp32, scratch_elems >= I*J, ideally several times that) receives the partial
- * slabs that a second kernel folds into `out`.  scratch == NULL falls back to fp32 atomics. */
+ * slabs that a second kernel folds into `out` in a fixed order (two launches agree bit for bit; so does the unsplit launch, which
+ * adds in place); scratch == NULL falls back to fp32 atomics (reproducible to rounding only).  The column sums are always atomics.
+ * NOT READ, whatever they hold: the columns of A from I to lda and of B from J to ldb, every row at or beyond P.  The columns of out
+ * between J and ldo are not written; ldo % 4 != 0 takes a scalar epilogue.  I, J, lda, ldb must be multiples of 8 (bf16) / 4 (fp32),
+ * else the call is refused.  tests/test_tn_edges_gpu.py pins all of this element by element (P = 1, one vector of columns, ragged
+ * tiles, every output form, NaN in everything that is not read). */
 int realise_gemm_tn(void* stream, int dtype, const void* A, int64_t lda, const void* B, int64_t ldb,
                     int P, int I, int J, float* out, int64_t ldo, float* scratch, int64_t scratch_elems,
                     float* colsum_out /* nullable: colsum_out[i] += sum_p A[p,i], the matching bias gradient */);
@@ -81,7 +86,9 @@ int realise_gemm_tn(void* stream, int dtype, const void* A, int64_t lda, const v
  * layer: BertSelfAttention q/k/v packed, BertSelfOutput.dense, BertIntermediate.dense, BertOutput.dense,
  * modeling_bert.py:221-232,273,326,339 under loss.backward(), run.py:200): every workgroup owns one 128x128 tile of one
  * problem over the whole reduction, so there is no reduction split, no scratch and no fold pass.
- * out_k[I_k, J_k] += A_k^T B_k, colsum_k[i] += sum_p A_k[p,i] (nullable).  ldo % 4 == 0. */
+ * out_k[I_k, J_k] += A_k^T B_k, colsum_k[i] += sum_p A_k[p,i] (nullable).  ldo % 4 == 0.  n < 1, n > 4, ldo % 4 != 0 or an I / J / pitch
+ * that is no multiple of 8 (bf16) / 4 (fp32) is refused and nothing is written; padding columns and rows at or beyond P are not read
+ * (tests/test_tn_edges_gpu.py). */
 typedef struct realise_tn_problem {
   const void* A; int64_t lda;      /* dY [P, I] */
   const void* B; int64_t ldb;      /* X  [P, J] */
@@ -90,7 +97,11 @@ typedef struct realise_tn_problem {
   float* colsum;
 } realise_tn_problem;
 int realise_gemm_tn_grouped(void* stream, int dtype, int n, const realise_tn_problem* problems, int P);
-/* Conv2d weight gradient into the reference's [Co][Ci][KH][KW] layout. */
+/* Conv2d weight gradient into the reference's [Co][Ci][KH][KW] layout: out += dY^T im2col(X) (A = dY [P, Co] with pitch lda, b the
+ * forward geometry with C = the padded channel count of X; the columns of the padding channels Ci .. C - 1 are dropped).  Not read:
+ * the padding columns of A, rows at or beyond P, table images img_index does not select, anything outside an image (the padding
+ * taps, and in the 64-channel 16x16 kernel the halo rows above the first and below the last image row, are zeros that come from no
+ * address).  tests/test_tn_edges_gpu.py pins it onto a non-zero `out`, on both kernels. */
 int realise_conv_tn(void* stream, int dtype, const void* A, int64_t lda, const realise_conv_geom* b,
                     int P, int Co, int Ci, float* out, float* scratch, int64_t scratch_elems);
 /* A/B knobs, probe modes and the per-launch timing hooks live in include/realise_hip_debug.h (diagnostics, not operators). */

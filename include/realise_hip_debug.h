@@ -40,7 +40,10 @@ void realise_set_engine(int key, int value);
 /* realise_gemm_tn_grouped over a list of live reduction blocks, as the engine's backward calls it: live[k] (device, ascending) = index
  * of the k-th block of `list_rows` rows that holds anything but exact zeros in the A operands, *n_live (device) = how many; the other
  * blocks are not read.  list_rows = 64 (bf16) / 32 (fp32): whole reduction tiles; 16 (bf16): four live blocks form a reduction tile.
- * overwrite != 0: out = result instead of out += result. */
+ * overwrite != 0: out = result instead of out += result (an empty list then stores exact zeros and leaves the column sums alone).
+ * fp32 takes list_rows = 32 only; P must be a multiple of 64 (bf16) / 32 (fp32) and P / list_rows at most 4096 entries (16 KB of LDS;
+ * beyond 1024 the launch reserves more than its default 4 KB), else the call is refused.  Pinned by tests/test_tn_edges_gpu.py with
+ * NaN in the dead blocks of A and B and dead-block indices behind the count: neither is read. */
 /* realise_gemm_nt bounded by a DEVICE-side row count, as the GRU steps of a device-built batch launch it: rows at or beyond
  * *rows_dev contribute zeros (an accumulating epilogue leaves them unchanged, a storing one writes bias-only rows in the last live
  * tile and nothing beyond it).  The contract as observed on both kernels a bf16 launch can reach (tests/test_gemm_edges_gpu.py,
@@ -151,6 +154,35 @@ int realise_profile_dump_ex(int kernel_family, int max_records, float* ms_out, d
 /* Host-side support predicate of the listed weight-gradient launches, exported so that a CPU test can pin it: bytes of LDS a listed
  * TN launch reserves for `entries` live blocks, -1 when the list does not fit (the engine then runs dense reductions). */
 int realise_debug_tn_list_lds(int64_t entries);
+/* What an ungrouped weight-gradient launch decides on the host, with the knobs as they stand (realise_set_tn_split,
+ * realise_set_conv_c64): the host functions the launchers themselves act on, exported so that tests can pin the path a case is meant
+ * for (tests/tn_cases.py, tests/test_tn_edges_gpu.py; invariants swept in tests/test_tn_cases_cpu.py).
+ * kind: 0 dense B operand (realise_gemm_tn), 1 gathered (realise_conv_tn), 2 gathered and the geometry is the 64 -> 64 channel 3x3 /
+ * stride 1 / pad 1 convolution on 16x16 maps without img_index (the caller vouches for the geometry; dtype, P, I, the scratch and the
+ * knob are checked here).  Cin > 0: the conv-weight output mapping with that many input channels (0: plain rows).
+ * tile: 0 nothing to launch, 1 64 x 256, 2 128 x 128, 3 conv_wgrad_c64.  nsplit workgroups along the reduction, each owning pchunk rows
+ * (before a device-side bound re-splits them inside the kernel).  form: 0 direct (out read-modify-written in place), 1 one slab plane
+ * per split + fold, 2 fp32 atomics.  fold: 0 none, 1 tn_fold_plain_kernel, 2 tn_fold_convw_kernel, fold_sb its split-lane count
+ * (1, 2, 4, 8, 16).  conv_wgrad_c64 always writes slab planes (form 1), a single split included.  Returns 0, or non-zero where the
+ * launch would be refused. */
+typedef struct realise_tn_plan { int32_t tile, nsplit, pchunk, form, fold, fold_sb; } realise_tn_plan;
+int realise_debug_tn_plan(int dtype, int kind, int P, int I, int J, int Cin, int scratch_given, int64_t scratch_elems, realise_tn_plan* plan);
+/* realise_gemm_tn exactly as the engine launches it, with the TnEpi fields the operator boundary hides: out (+)= alpha * *alpha_dev *
+ * A^T B (alpha_dev: device scalar, nullable - the incoming loss gradient of the classifier's weight gradient), the reduction bounded by
+ * *rows_dev (device, nullable: GRU alive count, loss rows, glyph dedup; rows at or beyond it are not read and the splits are re-cut
+ * over the live rows inside the kernel), overwrite != 0: out = result (honoured by the direct form only, as in the engine), conv_KHW >
+ * 0: the conv-weight output mapping out[(i * conv_Cin + ci) * conv_KHW + tap + tap0] for column j = tap * conv_Cpad + ci (the centre
+ * tap of a 3x3 convolution on a 1x1 map is the dense launch J = conv_Cpad, conv_KHW = 9, tap0 = 4; the other taps are not touched).
+ * tests/test_tn_edges_gpu.py: bounds 0, 1, BP, BP + 1, P - 1, P, P + 5 with NaN in the rows at or behind the bound, through the fold,
+ * the atomics and the column sums. */
+int realise_gemm_tn_ex(void* stream, int dtype, const void* A, int64_t lda, const void* B, int64_t ldb, int P, int I, int J,
+                       float* out, int64_t ldo, float* scratch, int64_t scratch_elems, float* colsum_out, float alpha,
+                       const float* alpha_dev, const int* rows_dev, int overwrite, int conv_Cin, int conv_Cpad, int conv_KHW, int tap0);
+/* realise_conv_tn likewise: alpha, alpha_dev, the device-side bound on the pixel rows (whole images) and, with img_index, the number
+ * of images in the table (the 32-bit span check; 0 = not checked). */
+int realise_conv_tn_ex(void* stream, int dtype, const void* A, int64_t lda, const realise_conv_geom* b, int P, int Co, int Ci,
+                       float* out, float* scratch, int64_t scratch_elems, float alpha, const float* alpha_dev, const int* rows_dev,
+                       int64_t index_rows);
 /* Which kernel realise_gemm_nt (rows_dev_given = 0) or realise_gemm_nt_rows (1) reaches for a shape, an epilogue (alpha = 1) and the
  * knobs as they stand (realise_set_nt_variant, realise_set_nt_allow_n96): the host function the launcher itself acts on, exported so
  * that tests can pin the kernel a case is meant for.  -1 refused (argument error), 0 nothing to launch; 4-wave kernels: 1 256 x 64,

@@ -52,6 +52,10 @@ class TnProblem(C.Structure):
                 ("out", C.c_void_p), ("ldo", C.c_int64), ("colsum", C.c_void_p)]
 
 
+class TnPlan(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("tile", "nsplit", "pchunk", "form", "fold", "fold_sb")]
+
+
 class Config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("model_type", "dtype", "hidden", "heads", "intermediate", "vocab", "max_pos",
                                          "type_vocab", "bert_layers", "pho_layers", "out_layers", "num_fonts",
@@ -142,6 +146,9 @@ SYMBOLS = {
     "realise_engine_forget_workspace": (None, [_P, _P]),
     "realise_engine_plan_installs": (_L, [_P]),
     "realise_debug_tn_list_lds": (_I, [_L]),
+    "realise_debug_tn_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, _L, C.POINTER(TnPlan)]),
+    "realise_gemm_tn_ex": (_I, [_P, _I, _P, _L, _P, _L, _I, _I, _I, _P, _L, _P, _L, _P, _F, _P, _P, _I, _I, _I, _I, _I]),
+    "realise_conv_tn_ex": (_I, [_P, _I, _P, _L, C.POINTER(ConvGeom), _I, _I, _I, _P, _P, _L, _F, _P, _P, _L]),
     "realise_debug_nt_path": (_I, [_I, _I, _I, _I, _I, _I, _I, _L, _L, _L, _L, _I]),
     "realise_engine_bind": (_I, [_P, _P, _P, _L]),
     "realise_engine_refresh_shadows": (_I, [_P, _P]),

@@ -515,6 +515,36 @@ int realise_engine_bind(realise_engine* e, void* shadow, void* workspace, int64_
   return e ? e->impl->bind(shadow, workspace, workspace_bytes) : RL_ERR_ARG;
 }
 int realise_debug_tn_list_lds(int64_t entries) { return tn_list_lds_bytes(entries); }
+int realise_debug_tn_plan(int dtype, int kind, int P, int I, int J, int Cin, int scratch_given, int64_t scratch_elems, realise_tn_plan* plan) {
+  if (!plan || (dtype != REALISE_BF16 && dtype != REALISE_F32) || kind < 0 || kind > 2) return RL_ERR_ARG;
+  TnPlan pl;
+  const int rc = tn_plan(dtype == REALISE_BF16 ? 2 : 4, kind == 2, P, I, J, Cin > 0, Cin, scratch_given != 0, scratch_elems, pl);
+  plan->tile = pl.tile; plan->nsplit = pl.nsplit; plan->pchunk = pl.pchunk; plan->form = pl.how; plan->fold = pl.fold; plan->fold_sb = pl.fold_sb;
+  return rc;
+}
+int realise_gemm_tn_ex(void* stream, int dtype, const void* A, int64_t lda, const void* B, int64_t ldb, int P, int I, int J,
+                       float* out, int64_t ldo, float* scratch, int64_t scratch_elems, float* colsum_out, float alpha,
+                       const float* alpha_dev, const int* rows_dev, int overwrite, int conv_Cin, int conv_Cpad, int conv_KHW, int tap0) {
+  hipStream_t st = (hipStream_t)stream;
+  TnEpi te; te.out = out; te.ldo = ldo; te.slab = scratch; te.slab_elems = scratch_elems; te.colsum = colsum_out;
+  te.alpha = alpha; te.alpha_dev = alpha_dev; te.overwrite = overwrite;
+  if (conv_KHW > 0) { te.mode = TN_CONVW; te.Cin = conv_Cin; te.Cpad = conv_Cpad; te.KHW = conv_KHW; te.tap0 = tap0; }
+  if (dtype == REALISE_BF16) return gemm_tn<bf16_t>(st, (const bf16_t*)A, lda, (const bf16_t*)B, ldb, P, I, J, te, rows_dev);
+  if (dtype == REALISE_F32) return gemm_tn<float>(st, (const float*)A, lda, (const float*)B, ldb, P, I, J, te, rows_dev);
+  return RL_ERR_ARG;
+}
+int realise_conv_tn_ex(void* stream, int dtype, const void* A, int64_t lda, const realise_conv_geom* b, int P, int Co, int Ci,
+                       float* out, float* scratch, int64_t scratch_elems, float alpha, const float* alpha_dev, const int* rows_dev,
+                       int64_t index_rows) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!b) return RL_ERR_ARG;
+  TnEpi te; te.mode = TN_CONVW; te.out = out; te.Cin = Ci; te.Cpad = b->C; te.KHW = b->KH * b->KW;
+  te.slab = scratch; te.slab_elems = scratch_elems; te.alpha = alpha; te.alpha_dev = alpha_dev;
+  const int J = b->KH * b->KW * b->C;
+  if (dtype == REALISE_BF16) { ConvLoader<bf16_t> g = to_geom<bf16_t>(b); g.rows_dev = rows_dev; g.index_rows = index_rows; return gemm_tn_conv<bf16_t>(st, (const bf16_t*)A, lda, g, P, Co, J, te); }
+  if (dtype == REALISE_F32) { ConvLoader<float> g = to_geom<float>(b); g.rows_dev = rows_dev; g.index_rows = index_rows; return gemm_tn_conv<float>(st, (const float*)A, lda, g, P, Co, J, te); }
+  return RL_ERR_ARG;
+}
 int realise_debug_nt_path(int dtype, int M, int N, int K, int mode, int accumulate, int has_aux, int64_t lda, int64_t ldb, int64_t ldo,
                           int64_t ldaux, int rows_dev_given) {
   static const uint64_t some_operand[2] = {0, 0};      // (only compared with nullptr)

@@ -146,16 +146,23 @@ conv_wgrad_c64_kernel(const bf16_t* __restrict__ dY, const bf16_t* __restrict__ 
       *(floatx4*)(out + (i * 16 + l15) * 576 + tap * 64 + c0 + 4 * g) = acc[i][tap];
 }
 
+// workgroups (= slab planes) the reduction over `rows` pixels is split into: one per [64][576] plane the slab holds, at most 512, at
+// most one per 64-pixel tile (realise_debug_tn_plan reports it)
+int conv_wgrad_c64_splits(int rows, int64_t slab_elems) {
+  int nsplit = (int)(slab_elems / (64 * 576));
+  if (nsplit > 512) nsplit = 512;
+  const int ntiles = rows / 64;
+  if (nsplit > ntiles) nsplit = ntiles;
+  return nsplit;
+}
+
 // dW (reference layout [64][64][3][3], fp32) += conv weight gradient; dY [rows][64], X [rows][64] NHWC over 16x16 maps (rows = images * 256,
 // optionally bounded on the device).  te: TN_CONVW epilogue (Cin = Cpad = 64, KHW = 9) with its slab.
 int conv_wgrad_c64(hipStream_t st, const bf16_t* dY, const bf16_t* X, int rows, const int* rows_dev, const TnEpi& te) {
   if (rows <= 0) return RL_OK;
   if ((rows % CW_PIX) || te.mode != TN_CONVW || te.Cin != 64 || te.Cpad != 64 || te.KHW != 9 || te.slab == nullptr) return RL_ERR_ARG;
   if ((int64_t)rows * 128 >= (int64_t)CW_RECORDS) return RL_ERR_ARG;                 // 32-bit buffer offsets
-  int nsplit = (int)(te.slab_elems / (64 * 576));
-  if (nsplit > 512) nsplit = 512;
-  const int ntiles = rows / 64;
-  if (nsplit > ntiles) nsplit = ntiles;
+  const int nsplit = conv_wgrad_c64_splits(rows, te.slab_elems);
   if (nsplit < 1) return RL_ERR_ARG;
   const int lds = CW_NST * CW_STAGE + 256;        // + slack: the masked x-wrap elements of the last stage's last rows are read one row past the tile
   static bool attr = false;

@@ -432,6 +432,21 @@ int gemm_nt_path(int M, int N, int K, const EpiParams<T>& ep, int64_t lda, int64
 void set_nt8_group_m(int g);       // tile order of the 8-wave NT kernels: 0/1 row-major, g > 1: g tile rows per column step (L2 blocking)
 
 void tn_fold_launch(hipStream_t st, const TnEpi& ep, int nsplit, int I, int J);     // out += alpha * sum of the split slabs, fixed order
+// What an ungrouped weight-gradient launch decides on the host (realise_debug_tn_plan): the choices launch_tn / gemm_tn_conv,
+// tn_fold_launch and conv_wgrad_c64 themselves act on, as pure host functions
+enum TnTile { TN_TILE_NONE = 0, TN_TILE_64x256 = 1, TN_TILE_128x128 = 2, TN_TILE_C64 = 3 };
+enum TnFold { TN_FOLD_NONE = 0, TN_FOLD_PLAIN = 1, TN_FOLD_CONVW = 2 };
+struct TnPlan {
+  int tile = TN_TILE_NONE;
+  int nsplit = 1, pchunk = 0;      // workgroups along the reduction and the rows each owns (a multiple of the reduction tile)
+  int how = 0;                     // TnOut: 0 direct, 1 slab + fold, 2 atomics
+  int fold = TN_FOLD_NONE, fold_sb = 0;      // the fold kernel behind a slab launch and its split-lane count SB
+};
+struct TnFoldPlan { bool convw = false; int sb = 1, blocks = 1; };
+TnFoldPlan tn_fold_plan(bool convw_mode, int Cin, int nsplit, int I, int J);
+// elem_bytes 2 (bf16) / 4 (fp32); c64_geom: the launch is a gathered one whose geometry and epilogue are conv_wgrad_c64's.  RL_ERR_ARG: refused
+int tn_plan(int elem_bytes, bool c64_geom, int P, int I, int J, bool convw_mode, int Cin, bool slab_given, int64_t slab_elems, TnPlan& pl);
+int conv_wgrad_c64_splits(int rows, int64_t slab_elems);      // conv_wgrad_c64.hip
 void set_conv_c64(int on);          // 1 (default): 64-channel 3x3 s1 conv forward / dgrad / wgrad on 16x16 maps via the LDS-resident kernels
 int conv_c64_nt(hipStream_t st, const bf16_t* X, const bf16_t* Wt, bf16_t* out, int rows, const int* rows_dev, int flip,
                 const float* col_scale = nullptr, const float* col_shift = nullptr, const bf16_t* aux = nullptr, int relu = 0);         // conv_c64_nt.hip

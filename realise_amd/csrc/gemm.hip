@@ -782,15 +782,23 @@ __global__ void __launch_bounds__(256) tn_fold_convw_kernel(TnEpi ep, int nsplit
   }
 }
 
-void tn_fold_launch(hipStream_t st, const TnEpi& ep, int nsplit, int I, int J) {
+TnFoldPlan tn_fold_plan(bool convw_mode, int Cin, int nsplit, int I, int J) {
+  TnFoldPlan f;
   // the per-(co, ci) form pays off once there are enough pairs to fill blocks; tiny gradients (64 x 3 x 9) go through the float4 form
-  const bool convw = ep.mode != TN_PLAIN && (int64_t)I * ep.Cin >= 16384;
-  const int64_t items = convw ? (int64_t)I * ep.Cin : (int64_t)I * J / 4;
+  f.convw = convw_mode && (int64_t)I * Cin >= 16384;
+  const int64_t items = f.convw ? (int64_t)I * Cin : (int64_t)I * J / 4;
   // split lanes: as many as keep >= ~1024 blocks' worth of items busy, at most 16 and at most the split count
-  int sb = 1;
-  while (sb < 16 && sb * 2 <= nsplit && items * sb < 256 * 1024) sb *= 2;
-  int blocks = (int)((items + 256 / sb - 1) / (256 / sb));
-  if (blocks > 4096) blocks = 4096;
+  f.sb = 1;
+  while (f.sb < 16 && f.sb * 2 <= nsplit && items * f.sb < 256 * 1024) f.sb *= 2;
+  f.blocks = (int)((items + 256 / f.sb - 1) / (256 / f.sb));
+  if (f.blocks > 4096) f.blocks = 4096;
+  return f;
+}
+
+void tn_fold_launch(hipStream_t st, const TnEpi& ep, int nsplit, int I, int J) {
+  const TnFoldPlan f = tn_fold_plan(ep.mode != TN_PLAIN, ep.Cin, nsplit, I, J);
+  const bool convw = f.convw;
+  const int sb = f.sb, blocks = f.blocks;
 #define RL_FOLD(SBV) \
   if (convw) hipLaunchKernelGGL(tn_fold_convw_kernel<SBV>, dim3(blocks), dim3(256), 0, st, ep, nsplit, I, J); \
   else hipLaunchKernelGGL(tn_fold_plain_kernel<SBV>, dim3(blocks), dim3(256), 0, st, ep, nsplit, I, J);
@@ -807,34 +815,68 @@ void tn_fold_launch(hipStream_t st, const TnEpi& ep, int nsplit, int I, int J) {
 static int g_tn_tr = 1;   // ds_read_b64_tr_b16 verified on MI355X (tests/test_kernels_gpu.py::test_gemm_tn)
 void set_tn_transpose_read(int use_tr) { g_tn_tr = use_tr; }
 
-template <typename T, typename BLoader, int WI, int WJ>
-static int launch_tn_tile(hipStream_t st, const T* A, int64_t lda, const BLoader& lb, int P, int I, int J, const TnEpi& ep_) {
-  typedef TnGeo<T> G;
-  const TnEpi& ep = ep_;
-  constexpr int BI = 64 * WI, BJ = 64 * WJ;
+// The reduction split of an ungrouped launch over tiles of BI x BJ outputs and BP reduction rows, as a pure host function
+// (realise_debug_tn_plan): the chip holds 512 workgroups (256 CUs x 2).  Pick the split count that minimises
+//   rounds(split) x rows per workgroup + split x (slab write + fold read, in row-times)
+// - a split that spills a few workgroups into a second round costs a whole extra pass (e.g. 144 tiles: 3 splits =
+// 432 workgroups beat 4 splits = 576 by 25 %, tools/nt_probe.cpp sweep).
+static void tn_split_plan(int BP, int BI, int BJ, int P, int I, int J, bool slab_given, int64_t slab_elems, TnPlan& pl) {
   const int tiles_i = (I + BI - 1) / BI, tiles_j = (J + BJ - 1) / BJ, ntiles = tiles_i * tiles_j;
-  // Reduction split: the chip holds 512 workgroups (256 CUs x 2).  Pick the split count that minimises
-  //   rounds(split) x rows per workgroup + split x (slab write + fold read, in row-times)
-  // - a split that spills a few workgroups into a second round costs a whole extra pass (e.g. 144 tiles: 3 splits =
-  // 432 workgroups beat 4 splits = 576 by 25 %, tools/nt_probe.cpp sweep).
-  const int max_split = (P + 4 * G::BP - 1) / (4 * G::BP);
+  const int max_split = (P + 4 * BP - 1) / (4 * BP);
   int64_t cap = max_split;
-  if (ep.slab != nullptr && ep.slab_elems / ((int64_t)I * J) < cap) cap = ep.slab_elems / ((int64_t)I * J);
+  if (slab_given && slab_elems / ((int64_t)I * J) < cap) cap = slab_elems / ((int64_t)I * J);
   if (cap < 1) cap = 1;
-  int nsplit = 1, pchunk = ((P + G::BP - 1) / G::BP) * G::BP;
+  int nsplit = 1, pchunk = ((P + BP - 1) / BP) * BP;
   {
     double best = 1e30;
     const double slab_rows = 1e-4 * (double)I * (double)J;
     for (int ns = 1; ns <= (int)cap; ++ns) {
       if (g_tn_split > 0 && ns != (g_tn_split < (int)cap ? g_tn_split : (int)cap)) continue;
-      const int pc = (((P + ns - 1) / ns + G::BP - 1) / G::BP) * G::BP;
+      const int pc = (((P + ns - 1) / ns + BP - 1) / BP) * BP;
       const int ne = (P + pc - 1) / pc;
       const double rounds = (double)(((int64_t)ntiles * ne + 511) / 512);
       const double c = rounds * pc + (ne > 1 ? ne * slab_rows : 0.0);
       if (c < best) { best = c; nsplit = ne; pchunk = pc; }
     }
   }
-  const int how = nsplit == 1 ? TN_OUT_DIRECT : (ep.slab != nullptr ? TN_OUT_SLAB : TN_OUT_ATOMIC);
+  pl.nsplit = nsplit; pl.pchunk = pchunk;
+  pl.how = nsplit == 1 ? TN_OUT_DIRECT : (slab_given ? TN_OUT_SLAB : TN_OUT_ATOMIC);
+}
+
+// the 64 -> 64 channel 3x3 / stride 1 / pad 1 convolution on 16x16 maps goes to conv_wgrad_c64 (geom_ok: the loader and the epilogue
+// are that convolution's, dense rows, alpha 1)
+static bool tn_c64_ok(bool geom_ok, int P, int I, bool slab_given, int64_t slab_elems) {
+  return g_conv_c64 && geom_ok && I == 64 && P > 0 && (P % 256) == 0 && slab_given && slab_elems >= 64 * 576 && (int64_t)P * 128 < 0xFFFFFE00ll;
+}
+
+int tn_plan(int elem_bytes, bool c64_geom, int P, int I, int J, bool convw_mode, int Cin, bool slab_given, int64_t slab_elems, TnPlan& pl) {
+  pl = TnPlan();
+  const int BP = elem_bytes == 2 ? TnGeo<bf16_t>::BP : TnGeo<float>::BP, VEC = elem_bytes == 2 ? TnGeo<bf16_t>::VEC : TnGeo<float>::VEC;
+  if (P <= 0 || I <= 0 || J <= 0) return RL_OK;              // nothing to launch (tile 0)
+  if (elem_bytes == 2 && tn_c64_ok(c64_geom, P, I, slab_given, slab_elems)) {
+    pl.tile = TN_TILE_C64;
+    pl.nsplit = conv_wgrad_c64_splits(P, slab_elems);
+    pl.pchunk = ((P / 64 + pl.nsplit - 1) / pl.nsplit) * 64;
+    pl.how = TN_OUT_SLAB;                  // (a single split writes its slab plane too: the fold owns the [Co][Ci][3][3] mapping)
+  } else {
+    if ((I % VEC) || (J % VEC)) return RL_ERR_ARG;
+    pl.tile = I <= 64 ? TN_TILE_64x256 : TN_TILE_128x128;
+    tn_split_plan(BP, I <= 64 ? 64 : 128, I <= 64 ? 256 : 128, P, I, J, slab_given, slab_elems, pl);
+  }
+  if (pl.how == TN_OUT_SLAB) {
+    const TnFoldPlan f = tn_fold_plan(convw_mode, Cin, pl.nsplit, I, J);
+    pl.fold = f.convw ? TN_FOLD_CONVW : TN_FOLD_PLAIN; pl.fold_sb = f.sb;
+  }
+  return RL_OK;
+}
+
+template <typename T, typename BLoader, int WI, int WJ>
+static int launch_tn_tile(hipStream_t st, const T* A, int64_t lda, const BLoader& lb, int P, int I, int J, const TnEpi& ep_, const TnPlan& pl) {
+  typedef TnGeo<T> G;
+  const TnEpi& ep = ep_;
+  constexpr int BI = 64 * WI, BJ = 64 * WJ;
+  const int tiles_i = (I + BI - 1) / BI, tiles_j = (J + BJ - 1) / BJ, ntiles = tiles_i * tiles_j;
+  const int nsplit = pl.nsplit, pchunk = pl.pchunk, how = pl.how;
   const int list_lds = ep.tile_list != nullptr ? tn_list_lds_bytes((int64_t)P / (ep.list_rows ? ep.list_rows : G::BP)) : 0;
   if (list_lds < 0) return RL_ERR_ARG;
   const size_t lds = 2 * (size_t)G::BP * (BI + BJ) * sizeof(T) + (size_t)list_lds;
@@ -862,9 +904,12 @@ template <typename T, typename BLoader>
 static int launch_tn(hipStream_t st, const T* A, int64_t lda, const BLoader& lb, int P, int I, int J, const TnEpi& ep) {
   if (P <= 0 || I <= 0 || J <= 0) return RL_OK;
   typedef TnGeo<T> G;
-  if ((lda % G::VEC) || (I % G::VEC) || (J % G::VEC)) return RL_ERR_ARG;
-  if (I <= 64) return launch_tn_tile<T, BLoader, 1, 4>(st, A, lda, lb, P, I, J, ep);
-  return launch_tn_tile<T, BLoader, 2, 2>(st, A, lda, lb, P, I, J, ep);
+  if (lda % G::VEC) return RL_ERR_ARG;
+  TnPlan pl;
+  const int rc = tn_plan((int)sizeof(T), false, P, I, J, ep.mode != TN_PLAIN, ep.Cin, ep.slab != nullptr, ep.slab_elems, pl);
+  if (rc != RL_OK) return rc;
+  if (pl.tile == TN_TILE_64x256) return launch_tn_tile<T, BLoader, 1, 4>(st, A, lda, lb, P, I, J, ep, pl);
+  return launch_tn_tile<T, BLoader, 2, 2>(st, A, lda, lb, P, I, J, ep, pl);
 }
 
 template <typename T>
@@ -928,10 +973,10 @@ int gemm_tn_conv(hipStream_t st, const T* A, int64_t lda, const ConvLoader<T>& l
   if (lb.K != J || !lb.span_ok()) return RL_ERR_ARG;
   if constexpr (sizeof(T) == 2) {
     // 64 -> 64 channels, 3x3 / stride 1 / pad 1 on 16x16 maps (glyph ResNet block 1): the LDS-resident-input kernel
-    if (g_conv_c64 && lb.C == 64 && lb.KH == 3 && lb.KW == 3 && lb.stride == 1 && lb.pad == 1 && lb.mode == 0 && lb.Hr == 16 &&
-        lb.Wr == 16 && lb.Hs == 16 && lb.Ws == 16 && lb.img_index == nullptr && I == 64 && lda == 64 && P == lb.rows && (P % 256) == 0 &&
-        ep.mode == TN_CONVW && ep.Cin == 64 && ep.Cpad == 64 && ep.KHW == 9 && ep.tap0 == 0 && ep.alpha == 1.0f && ep.alpha_dev == nullptr && ep.slab != nullptr &&
-        ep.slab_elems >= 64 * 576 && (int64_t)P * 128 < 0xFFFFFE00ll)
+    const bool c64_geom = lb.C == 64 && lb.KH == 3 && lb.KW == 3 && lb.stride == 1 && lb.pad == 1 && lb.mode == 0 && lb.Hr == 16 &&
+        lb.Wr == 16 && lb.Hs == 16 && lb.Ws == 16 && lb.img_index == nullptr && lda == 64 && P == lb.rows &&
+        ep.mode == TN_CONVW && ep.Cin == 64 && ep.Cpad == 64 && ep.KHW == 9 && ep.tap0 == 0 && ep.alpha == 1.0f && ep.alpha_dev == nullptr;
+    if (tn_c64_ok(c64_geom, P, I, ep.slab != nullptr, ep.slab_elems))
       return conv_wgrad_c64(st, A, lb.src, P, lb.rows_dev, ep);
   }
   if (lb.img_index == nullptr) return launch_tn<T, ConvLoaderDirect<T>>(st, A, lda, ConvLoaderDirect<T>(lb), P, I, J, ep);      // (every engine call)

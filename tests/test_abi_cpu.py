@@ -40,6 +40,19 @@ def test_debug_nt_path_answers_without_a_gpu():
     assert lib.realise_debug_nt_path(7, 128, 128, 64, 0, 0, 0, 64, 64, 128, 128, 0) == -1                   # no such dtype
 
 
+def test_debug_tn_plan_answers_without_a_gpu():
+    """realise_debug_tn_plan (include/realise_hip_debug.h) is a pure host function: the host choices of the weight-gradient launchers;
+    its invariants and the shapes are pinned in tests/test_tn_cases_cpu.py"""
+    lib = _capi.load()
+    pl = _capi.TnPlan()
+    assert lib.realise_debug_tn_plan(_capi.BF16, 0, 520, 72, 136, 0, 0, 0, C.byref(pl)) == 0
+    assert pl.tile == 2 and pl.nsplit * pl.pchunk >= 520 and pl.pchunk % 64 == 0 and (pl.form == 0) == (pl.nsplit == 1) and pl.fold == 0
+    assert lib.realise_debug_tn_plan(_capi.BF16, 2, 768, 64, 576, 64, 1, 5 * 64 * 576, C.byref(pl)) == 0
+    assert (pl.tile, pl.nsplit, pl.pchunk, pl.form, pl.fold) == (3, 5, 192, 1, 1)          # conv_wgrad_c64: slab planes + the float4 fold
+    assert lib.realise_debug_tn_plan(_capi.BF16, 0, 64, 68, 64, 0, 0, 0, C.byref(pl)) != 0           # I % 8
+    assert lib.realise_debug_tn_plan(7, 0, 64, 64, 64, 0, 0, 0, C.byref(pl)) != 0                    # no such dtype
+
+
 @pytest.mark.parametrize("model_type,count", [("arch3", 427), ("bert", 201)])
 def test_layout_matches_reference_state_dict(model_type, count):
     cfg = RealiseConfig()
