@@ -20,6 +20,12 @@ extern "C" {
 
 #define REALISE_F32 0
 #define REALISE_BF16 1
+/* fp32 buffers; the dense (Linear) GEMMs split every operand value x in registers into hi = bf16(x), lo = bf16(x - hi) and form
+ * hi.hi + hi.lo + lo.hi on the bf16 MFMA with fp32 accumulation (the lo.lo term is not computed).  Accepted by realise_gemm_nt,
+ * realise_gemm_nt_rows, realise_gemm_tn, realise_gemm_tn_grouped (+ _live) and the realise_debug_* calls that describe them, and as
+ * realise_config.dtype (every other kernel of that engine - convolutions, attention, row kernels - is the REALISE_F32 one); every
+ * other operator refuses it. */
+#define REALISE_F32_BF16X3 2
 
 /* ------------------------------------------------------------------------------------------
  * Fine-grained operators (each one kernel family).  Used by the engine and by the parity tests.

@@ -13,6 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "librealise_hip.so")
 
 F32, BF16 = 0, 1
+F32_BF16X3 = 2      # fp32 buffers, split-bf16 Linear GEMMs (REALISE_F32_BF16X3)
 EPI_STORE, EPI_GELU, EPI_DROP_RESID, EPI_GELU_BWD = 0, 1, 2, 4
 
 

@@ -24,6 +24,8 @@ template <typename T> EpiParams<T> to_epi(const realise_epilogue* e) {
   p.drop_seed = e->drop_seed; p.drop_thresh = e->drop_thresh; p.drop_scale = e->drop_scale;
   return p;
 }
+// REALISE_F32_BF16X3: fp32 buffers, the dense GEMMs multiply split-bf16 (EpiParams::x3 / TnEpi::x3)
+EpiParams<float> to_epi_x3(const realise_epilogue* e) { EpiParams<float> p = to_epi<float>(e); p.x3 = 1; return p; }
 template <typename T> ConvLoader<T> to_geom(const realise_conv_geom* g) {
   ConvLoader<T> c;
   c.src = (const T*)g->src; c.img_index = g->img_index; c.rows = g->rows; c.Hr = g->Hr; c.Wr = g->Wr; c.Hs = g->Hs; c.Ws = g->Ws;
@@ -60,14 +62,14 @@ static int conv_dgrad_s2(hipStream_t st, const realise_conv_geom* a, const T* B,
 
 template <typename T>
 static int tn_grouped(hipStream_t st, int n, const realise_tn_problem* pr, int P, const int* live = nullptr, const int* n_live = nullptr,
-                      int list_rows = 0, int overwrite = 0) {
+                      int list_rows = 0, int overwrite = 0, int x3 = 0) {
   if (n < 1 || n > TN_GROUP_MAX || pr == nullptr) return RL_ERR_ARG;
   TnGroupProblem<T> g[TN_GROUP_MAX];
   for (int k = 0; k < n; ++k) {
     g[k].A = (const T*)pr[k].A; g[k].lda = pr[k].lda; g[k].B = (const T*)pr[k].B; g[k].ldb = pr[k].ldb;
     g[k].I = pr[k].I; g[k].J = pr[k].J; g[k].out = pr[k].out; g[k].ldo = pr[k].ldo; g[k].colsum = pr[k].colsum;
   }
-  return gemm_tn_group<T>(st, n, g, P, 1.0f, overwrite, live, n_live, list_rows);
+  return gemm_tn_group<T>(st, n, g, P, 1.0f, overwrite, live, n_live, list_rows, x3);
 }
 
 template <typename T>
@@ -87,6 +89,7 @@ int realise_gemm_nt(void* stream, int dtype, const void* A, int64_t lda, const v
   if (!ep || !ep->out) return RL_ERR_ARG;
   if (dtype == REALISE_BF16) return gemm_nt<bf16_t>(st, (const bf16_t*)A, lda, (const bf16_t*)B, ldb, M, N, K, to_epi<bf16_t>(ep));
   if (dtype == REALISE_F32) return gemm_nt<float>(st, (const float*)A, lda, (const float*)B, ldb, M, N, K, to_epi<float>(ep));
+  if (dtype == REALISE_F32_BF16X3) return gemm_nt<float>(st, (const float*)A, lda, (const float*)B, ldb, M, N, K, to_epi_x3(ep));
   return RL_ERR_ARG;
 }
 int realise_conv_nt(void* stream, int dtype, const realise_conv_geom* a, const void* B, int64_t ldb, int M, int N, int K,
@@ -111,12 +114,14 @@ int realise_gemm_tn(void* stream, int dtype, const void* A, int64_t lda, const v
   TnEpi te; te.out = out; te.ldo = ldo; te.slab = scratch; te.slab_elems = scratch_elems; te.colsum = colsum_out;
   if (dtype == REALISE_BF16) return gemm_tn<bf16_t>(st, (const bf16_t*)A, lda, (const bf16_t*)B, ldb, P, I, J, te);
   if (dtype == REALISE_F32) return gemm_tn<float>(st, (const float*)A, lda, (const float*)B, ldb, P, I, J, te);
+  if (dtype == REALISE_F32_BF16X3) { te.x3 = 1; return gemm_tn<float>(st, (const float*)A, lda, (const float*)B, ldb, P, I, J, te); }
   return RL_ERR_ARG;
 }
 int realise_gemm_tn_grouped(void* stream, int dtype, int n, const realise_tn_problem* problems, int P) {
   hipStream_t st = (hipStream_t)stream;
   if (dtype == REALISE_BF16) return tn_grouped<bf16_t>(st, n, problems, P);
   if (dtype == REALISE_F32) return tn_grouped<float>(st, n, problems, P);
+  if (dtype == REALISE_F32_BF16X3) return tn_grouped<float>(st, n, problems, P, nullptr, nullptr, 0, 0, 1);
   return RL_ERR_ARG;
 }
 int realise_gemm_nt_rows(void* stream, int dtype, const void* A, int64_t lda, const void* B, int64_t ldb, int M, int N, int K,
@@ -125,6 +130,7 @@ int realise_gemm_nt_rows(void* stream, int dtype, const void* A, int64_t lda, co
   if (!ep || !ep->out || !rows_dev) return RL_ERR_ARG;
   if (dtype == REALISE_BF16) return gemm_nt<bf16_t>(st, (const bf16_t*)A, lda, (const bf16_t*)B, ldb, M, N, K, to_epi<bf16_t>(ep), rows_dev);
   if (dtype == REALISE_F32) return gemm_nt<float>(st, (const float*)A, lda, (const float*)B, ldb, M, N, K, to_epi<float>(ep), rows_dev);
+  if (dtype == REALISE_F32_BF16X3) return gemm_nt<float>(st, (const float*)A, lda, (const float*)B, ldb, M, N, K, to_epi_x3(ep), rows_dev);
   return RL_ERR_ARG;
 }
 int realise_gemm_nt_live(void* stream, const void* A, int64_t lda, const void* B, int64_t ldb, int M, int N, int K,
@@ -151,6 +157,7 @@ int realise_gemm_tn_grouped_live(void* stream, int dtype, int n, const realise_t
   if (live == nullptr || n_live == nullptr) return RL_ERR_ARG;
   if (dtype == REALISE_BF16) return tn_grouped<bf16_t>(st, n, problems, P, live, n_live, list_rows, overwrite);
   if (dtype == REALISE_F32) return tn_grouped<float>(st, n, problems, P, live, n_live, list_rows, overwrite);
+  if (dtype == REALISE_F32_BF16X3) return tn_grouped<float>(st, n, problems, P, live, n_live, list_rows, overwrite, 1);
   return RL_ERR_ARG;
 }
 int realise_conv_tn(void* stream, int dtype, const void* A, int64_t lda, const realise_conv_geom* b, int P, int Co, int Ci,
@@ -516,7 +523,7 @@ int realise_engine_bind(realise_engine* e, void* shadow, void* workspace, int64_
 }
 int realise_debug_tn_list_lds(int64_t entries) { return tn_list_lds_bytes(entries); }
 int realise_debug_tn_plan(int dtype, int kind, int P, int I, int J, int Cin, int scratch_given, int64_t scratch_elems, realise_tn_plan* plan) {
-  if (!plan || (dtype != REALISE_BF16 && dtype != REALISE_F32) || kind < 0 || kind > 2) return RL_ERR_ARG;
+  if (!plan || (dtype != REALISE_BF16 && dtype != REALISE_F32 && dtype != REALISE_F32_BF16X3) || kind < 0 || kind > 2) return RL_ERR_ARG;
   TnPlan pl;
   const int rc = tn_plan(dtype == REALISE_BF16 ? 2 : 4, kind == 2, P, I, J, Cin > 0, Cin, scratch_given != 0, scratch_elems, pl);
   plan->tile = pl.tile; plan->nsplit = pl.nsplit; plan->pchunk = pl.pchunk; plan->form = pl.how; plan->fold = pl.fold; plan->fold_sb = pl.fold_sb;
@@ -531,6 +538,7 @@ int realise_gemm_tn_ex(void* stream, int dtype, const void* A, int64_t lda, cons
   if (conv_KHW > 0) { te.mode = TN_CONVW; te.Cin = conv_Cin; te.Cpad = conv_Cpad; te.KHW = conv_KHW; te.tap0 = tap0; }
   if (dtype == REALISE_BF16) return gemm_tn<bf16_t>(st, (const bf16_t*)A, lda, (const bf16_t*)B, ldb, P, I, J, te, rows_dev);
   if (dtype == REALISE_F32) return gemm_tn<float>(st, (const float*)A, lda, (const float*)B, ldb, P, I, J, te, rows_dev);
+  if (dtype == REALISE_F32_BF16X3) { te.x3 = 1; return gemm_tn<float>(st, (const float*)A, lda, (const float*)B, ldb, P, I, J, te, rows_dev); }
   return RL_ERR_ARG;
 }
 int realise_conv_tn_ex(void* stream, int dtype, const void* A, int64_t lda, const realise_conv_geom* b, int P, int Co, int Ci,
@@ -554,6 +562,7 @@ int realise_debug_nt_path(int dtype, int M, int N, int K, int mode, int accumula
   e.ldaux = ldaux; e.alpha = 1.0f; e.drop_scale = 1.0f;
   if (dtype == REALISE_BF16) return gemm_nt_path<bf16_t>(M, N, K, to_epi<bf16_t>(&e), lda, ldb, rows_dev_given != 0);
   if (dtype == REALISE_F32) return gemm_nt_path<float>(M, N, K, to_epi<float>(&e), lda, ldb, rows_dev_given != 0);
+  if (dtype == REALISE_F32_BF16X3) return gemm_nt_path<float>(M, N, K, to_epi_x3(&e), lda, ldb, rows_dev_given != 0);
   return NT_PATH_REFUSED;
 }
 int64_t realise_engine_plan_installs(const realise_engine* e) { return e ? e->impl->plan_install_count() : -1; }

@@ -102,9 +102,38 @@ struct MmaF32 {                                // exact fp32: bitwise a k-ordere
     return __builtin_amdgcn_mfma_f32_16x16x4f32(x, y, c, 0, 0, 0);
   }
 };
+// bf16x3: fp32 operands in memory, each value x split in registers into hi = bf16_rne(x) and lo = bf16_rne(x - hi) (the
+// subtraction is exact in fp32); a product is hi.hi + hi.lo + lo.hi on the bf16 atom - three MFMAs per 16x16x32 step, fp32
+// accumulation.  The lo.lo term is NOT formed: that is the definition of the mode (unit error ~3 * 2^-16).
+struct MmaBF16x3 {
+  typedef float T;
+  static constexpr int K = 32;
+  struct Frag { bf16x8_t hi, lo; };
+  static __device__ __forceinline__ floatx4 mma(const Frag& x, const Frag& y, floatx4 c) {
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x.lo, y.hi, c, 0, 0, 0);
+    c = __builtin_amdgcn_mfma_f32_16x16x32_bf16(x.hi, y.lo, c, 0, 0, 0);
+    return __builtin_amdgcn_mfma_f32_16x16x32_bf16(x.hi, y.hi, c, 0, 0, 0);
+  }
+  // eight fp32 values (the K-slots 8g .. 8g+7 of one row) -> their hi / lo fragments
+  static __device__ __forceinline__ Frag split(const float (&x)[8]) {
+    uint32_t h[4], l[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      h[e] = pack2bf(x[2 * e], x[2 * e + 1]);
+      l[e] = pack2bf(x[2 * e] - __uint_as_float(h[e] << 16), x[2 * e + 1] - __uint_as_float(h[e] & 0xffff0000u));
+    }
+    Frag f;
+    f.hi = __builtin_bit_cast(bf16x8_t, uint4{h[0], h[1], h[2], h[3]});
+    f.lo = __builtin_bit_cast(bf16x8_t, uint4{l[0], l[1], l[2], l[3]});
+    return f;
+  }
+};
 template <typename T> struct MmaOf;
 template <> struct MmaOf<bf16_t> { typedef MmaBF16 type; };
 template <> struct MmaOf<float> { typedef MmaF32 type; };
+// the policy a kernel instantiation multiplies with: MmaOf<T>, or the split-bf16 one for fp32 operands (X3)
+template <typename T, bool X3> struct MmaSel { typedef typename MmaOf<T>::type type; };
+template <> struct MmaSel<float, true> { typedef MmaBF16x3 type; };
 
 // ---- LDS tile with K contiguous rows of KELEMS elements, 16-byte chunks XOR-swizzled by row --
 // chunk c of row r lives at chunk (c ^ (r & 7)): conflict-free ds_read_b128 for MFMA operand
@@ -128,6 +157,17 @@ template <> __device__ __forceinline__ float ktile_frag<float, 32>(const char* t
 }
 template <> __device__ __forceinline__ float ktile_frag<float, 64>(const char* tile, int row, int ks, int g) {
   return *(const float*)(tile + KTile<float, 64>::off(row, ks) + 4 * g);
+}
+// bf16x3 fragment of an fp32 K-tile (32 floats per row = one 16x16x32 step): two ds_read_b128 per lane, split in registers.
+// Which eight k a lane group owns is free (both operands use the same map; the sum over k has no order): group g takes the logical
+// chunks g and g + 4 (k = 4g .. 4g+3 and 16+4g .. 16+4g+3).  Chunk g is the read pattern of the bf16 atom (ks * 4 + g) and g + 4 is
+// its image under XOR 4: both are conflict-free under the KTile swizzle.  Chunks 2g and 2g + 1 (k = 8g .. 8g+7) would be 2-way
+// conflicts: in one ds_read_b128 lane group (lanes 0-3, 12-15, 20-27) groups 0 and 1 would both cover the even chunks.
+__device__ __forceinline__ MmaBF16x3::Frag ktile_frag_x3(const char* tile, int row, int g) {
+  const floatx4 u = *(const floatx4*)(tile + KTile<float, 32>::off(row, g));
+  const floatx4 v = *(const floatx4*)(tile + KTile<float, 32>::off(row, g + 4));
+  const float x[8] = {u[0], u[1], u[2], u[3], v[0], v[1], v[2], v[3]};
+  return MmaBF16x3::split(x);
 }
 
 // ---- counter-based dropout RNG (K17): mask is recomputed in backward, never stored ----------

@@ -272,6 +272,26 @@ template <typename T> struct Engine : EngineBase {
     }
     return gemm_nt<T>(st, A, lda, B, ldb, M, N, K, ep);
   }
+  // bf16x3 (realise_config.dtype == REALISE_F32_BF16X3: this engine is the float one with the flag set).  Every dense-loader GEMM the
+  // engine issues is written gemm_nt<U>(...) / gemm_tn<U>(...) / gemm_tn_group<U>(...): inside the class those names are THESE members,
+  // which hand the call to the launcher of gemm.h with the flag filled in - the one place it is set.  The gathered (ConvLoader) GEMMs,
+  // attention and the 8-wave kernels are other functions and stay as they are.
+  int x3() const { return cfg.dtype == REALISE_F32_BF16X3 ? 1 : 0; }
+  template <typename U>
+  int gemm_nt(hipStream_t st, const U* A, int64_t lda, const U* B, int64_t ldb, int M, int N, int K, EpiParams<U> ep, const int* rows_dev = nullptr) {
+    if constexpr (sizeof(U) == 4) ep.x3 = x3();
+    return rl::gemm_nt<U>(st, A, lda, B, ldb, M, N, K, ep, rows_dev);
+  }
+  template <typename U>
+  int gemm_tn(hipStream_t st, const U* A, int64_t lda, const U* B, int64_t ldb, int P_, int I_, int J_, TnEpi ep, const int* rows_dev = nullptr) {
+    if constexpr (sizeof(U) == 4) ep.x3 = x3();
+    return rl::gemm_tn<U>(st, A, lda, B, ldb, P_, I_, J_, ep, rows_dev);
+  }
+  template <typename U>
+  int gemm_tn_group(hipStream_t st, int n, const TnGroupProblem<U>* probs, int P_, float alpha, int overwrite, const int* tile_list,
+                    const int* n_tiles, int list_rows) {
+    return rl::gemm_tn_group<U>(st, n, probs, P_, alpha, overwrite, tile_list, n_tiles, list_rows, sizeof(U) == 4 ? x3() : 0);
+  }
   const int* live_rlen() const { return dead_ok ? wp<int>(pl.live_rlen) : nullptr; }
   bool cls_compact = false;                // the last forward wrote compacted classifier-gradient rows (stage_head must match)
 
@@ -1741,7 +1761,7 @@ EngineBase* make_engine(const realise_config& c, float* p, float* g, float* pu, 
     if (c.hidden != tower_of(c).features()) return nullptr;
   }
   if (c.dtype == REALISE_BF16) return new Engine<bf16_t>(c, p, g, pu, fz, bf, bi);
-  if (c.dtype == REALISE_F32) return new Engine<float>(c, p, g, pu, fz, bf, bi);
+  if (c.dtype == REALISE_F32 || c.dtype == REALISE_F32_BF16X3) return new Engine<float>(c, p, g, pu, fz, bf, bi);      // (x3(): the flag)
   return nullptr;
 }
 

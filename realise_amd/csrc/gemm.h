@@ -86,6 +86,9 @@ template <typename T> struct EpiParams {
   T* gru_gh = nullptr;                  // [M][3H]: only the n third is written
   T* gru_out = nullptr;                 // [N tokens][H], original order
   int gru_Tp = 0, gru_t = 0;
+  // bf16x3 (T = float, dense operands, the 4-wave kernels of gemm.hip): multiply with MmaBF16x3 instead of the exact fp32 atom.  The
+  // tile choice (nt_path) and the epilogues are those of fp32; gathered (ConvLoader) launches ignore it and stay exact fp32.
+  int x3 = 0;
 };
 
 // ---- operand loaders ---------------------------------------------------------------------------
@@ -359,6 +362,9 @@ struct TnEpi {
   // rows per list entry: BP (whole reduction tiles), or 16 (bf16, grouped 128 x 128 kernel): entries name live 16-row blocks and a
   // reduction tile is any four of them (wave w of the workgroup fetches the w-th) - the last tile is padded with zero blocks
   int list_rows = 0;
+  // bf16x3 (fp32 operands, dense B): the reduction runs on MmaBF16x3, the column sums on hi + lo (two ones-vector MFMAs); plan, slabs,
+  // fold and atomics are those of fp32.  Gathered (ConvLoader) launches ignore it.
+  int x3 = 0;
 };
 
 // Grouped TN (weight-gradient) launch: problems sharing the reduction length P, one 128x128 tile per workgroup, no reduction split.
@@ -378,10 +384,11 @@ template <typename T> struct TnGroup {
   const int* tile_list = nullptr;      // live reduction tiles (see TnEpi)
   const int* n_tiles = nullptr;
   int list_rows = 0;
+  int x3 = 0;                          // bf16x3 (T = float), see TnEpi
 };
 template <typename T>
 int gemm_tn_group(hipStream_t st, int n, const TnGroupProblem<T>* probs, int P, float alpha = 1.0f, int overwrite = 0,
-                  const int* tile_list = nullptr, const int* n_tiles = nullptr, int list_rows = 0);
+                  const int* tile_list = nullptr, const int* n_tiles = nullptr, int list_rows = 0, int x3 = 0);
 
 // K6: one GRU time step = recurrent GEMM + gate math in one launch (EpiParams::gru_*); H = N / 3 must be a multiple of 64
 int gemm_nt8_gru(hipStream_t st, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, int M, int N, int K, const EpiParams<bf16_t>& ep);

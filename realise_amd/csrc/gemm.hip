@@ -50,11 +50,12 @@ template <typename T, int NA> struct ConvRows<ConvLoader<T>, NA> {
   }
 };
 
-template <typename T, typename ALoader, int WM, int WN, int NSTAGE, int NF, bool SPREAD>
+template <typename T, typename ALoader, int WM, int WN, int NSTAGE, int NF, bool SPREAD, bool X3 = false>
 __global__ void __launch_bounds__(64 * WM * WN, (WM * WN == 4 && NSTAGE == 2) ? 2 : 1)
 gemm_nt_kernel(ALoader la, DenseLoader<T> lb, int M, int N, int K, int tiles_n, int ntiles, EpiParams<T> ep) {
-  typedef typename MmaOf<T>::type Mma;
+  typedef typename MmaSel<T, X3>::type Mma;      // X3 (T = float): the K-tile of 32 floats is ONE split-bf16 16x16x32 step
   typedef Geo<T> G;
+  constexpr int KST = G::BK / Mma::K;
   constexpr int BM_ = 64 * WM, BN_ = 16 * NF * WN;       // each wave: 64 rows x (16*NF) columns
   constexpr int A_BYTES = BM_ * 128, B_BYTES = BN_ * 128, STAGE = A_BYTES + B_BYTES;
   constexpr int NW = WM * WN;
@@ -184,12 +185,18 @@ gemm_nt_kernel(ALoader la, DenseLoader<T> lb, int M, int N, int K, int tiles_n, 
     const char* As = smem + (kt % NSTAGE) * STAGE;
     const char* Bs = As + A_BYTES;
 #pragma unroll
-    for (int ks = 0; ks < G::KSTEPS; ++ks) {
+    for (int ks = 0; ks < KST; ++ks) {
       typename Mma::Frag a[4], b[NF];
 #pragma unroll
-      for (int i = 0; i < 4; ++i) a[i] = ktile_frag<T, G::BK>(As, wm * 64 + i * 16 + l15, ks, g);
+      for (int i = 0; i < 4; ++i) {
+        if constexpr (X3) a[i] = ktile_frag_x3(As, wm * 64 + i * 16 + l15, g);
+        else a[i] = ktile_frag<T, G::BK>(As, wm * 64 + i * 16 + l15, ks, g);
+      }
 #pragma unroll
-      for (int j = 0; j < NF; ++j) b[j] = ktile_frag<T, G::BK>(Bs, wn * 16 * NF + j * 16 + l15, ks, g);
+      for (int j = 0; j < NF; ++j) {
+        if constexpr (X3) b[j] = ktile_frag_x3(Bs, wn * 16 * NF + j * 16 + l15, g);
+        else b[j] = ktile_frag<T, G::BK>(Bs, wn * 16 * NF + j * 16 + l15, ks, g);
+      }
 #pragma unroll
       for (int i = 0; i < 4; ++i) {
 #pragma unroll
@@ -240,7 +247,7 @@ void set_nt_variant(int v) { g_nt_variant = (v == 9 || v == 12 || v == 14 || v =
 static int g_tn_split = 0;
 void set_tn_split(int n) { g_tn_split = n; }
 
-template <typename T, typename ALoader, int WM, int WN, int NSTAGE = 2, int NF = 4, bool SPREAD = false>
+template <typename T, typename ALoader, int WM, int WN, int NSTAGE = 2, int NF = 4, bool SPREAD = false, bool X3 = false>
 static int launch_nt_tile(hipStream_t st, const ALoader& la, const DenseLoader<T>& lb, int M, int N, int K, const EpiParams<T>& ep) {
   constexpr int BM_ = 64 * WM, BN_ = 16 * NF * WN;
   const int tiles_m = (M + BM_ - 1) / BM_, tiles_n = (N + BN_ - 1) / BN_;
@@ -249,7 +256,7 @@ static int launch_nt_tile(hipStream_t st, const ALoader& la, const DenseLoader<T
   const size_t lds = ring > etile ? ring : etile;        // the epilogue re-uses the ring as per-wave transpose tiles
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_nt_kernel<T, ALoader, WM, WN, NSTAGE, NF, SPREAD>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute((const void*)gemm_nt_kernel<T, ALoader, WM, WN, NSTAGE, NF, SPREAD, X3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr_set = true;
   }
   ProfScope ps(st, sizeof(typename ALoader::KPos) == sizeof(typename DenseLoader<T>::KPos) ? PK_GEMM_NT : PK_CONV_NT, 2.0 * M * N * K);
@@ -257,7 +264,7 @@ static int launch_nt_tile(hipStream_t st, const ALoader& la, const DenseLoader<T
     if (la.rows_dev != nullptr) prof_set_exec(la.rows_dev, 2.0 * N * K, BM_, M);   // device-side row bound: surplus tiles exit at once
   EpiParams<T> epp = ep;
   epp.wide = (N % 8 == 0) && (ep.ldo % 8 == 0) && (ep.aux == nullptr || ep.ldaux % 8 == 0);
-  RL_LAUNCH((gemm_nt_kernel<T, ALoader, WM, WN, NSTAGE, NF, SPREAD>), dim3(ntiles), dim3(64 * WM * WN), lds, st, la, lb, M, N, K, tiles_n, ntiles, epp);
+  RL_LAUNCH((gemm_nt_kernel<T, ALoader, WM, WN, NSTAGE, NF, SPREAD, X3>), dim3(ntiles), dim3(64 * WM * WN), lds, st, la, lb, M, N, K, tiles_n, ntiles, epp);
   return hipGetLastError() == hipSuccess ? RL_OK : RL_ERR_LAUNCH;
 }
 
@@ -343,6 +350,16 @@ static int launch_nt(hipStream_t st, const ALoader& la, const T* B, int64_t ldb,
       default: break;
     }
   }
+  if constexpr (kDense && sizeof(T) == 4) {      // bf16x3: the same three tiles, multiplied by MmaBF16x3
+    if (ep.x3) {
+      switch (path) {
+        case NT_PATH_4W_256x64: return launch_nt_tile<T, ALoader, 4, 1, 2, 4, false, true>(st, la, lb, M, N, K, ep);
+        case NT_PATH_4W_128x96: return launch_nt_tile<T, ALoader, 2, 2, 2, 3, false, true>(st, la, lb, M, N, K, ep);
+        case NT_PATH_4W_128x128: return launch_nt_tile<T, ALoader, 2, 2, 2, 4, false, true>(st, la, lb, M, N, K, ep);
+        default: return RL_ERR_ARG;
+      }
+    }
+  }
   switch (path) {
     case NT_PATH_4W_256x64: return launch_nt_tile<T, ALoader, 4, 1>(st, la, lb, M, N, K, ep);
     case NT_PATH_4W_128x96: return launch_nt_tile<T, ALoader, 2, 2, 2, 3>(st, la, lb, M, N, K, ep);
@@ -356,6 +373,7 @@ template <typename T>
 static bool gemm_nt_args_ok(int64_t lda, const EpiParams<T>& ep) {
   if (lda % Geo<T>::VEC) return false;
   if (ep.out_f32 != nullptr && sizeof(T) != 2) return false;
+  if (ep.x3 && sizeof(T) != 4) return false;
   if (ep.col_scale != nullptr && ep.mode != EPI_AFFINE) return false;
   return true;
 }
@@ -398,7 +416,7 @@ int gemm_nt_conv(hipStream_t st, const ConvLoader<T>& la_, const T* B, int64_t l
 // hipcc (ROCm 7.2) drops the implicit instantiation of the default-tile conv kernel once the kernel body holds the ConvRows
 // helper (the host object keeps an undefined reference): instantiate the gathered-operand kernels explicitly.
 #define RL_INST_NT_CONV(T, WM, WN, NS, NF) \
-  template __global__ void gemm_nt_kernel<T, ConvLoader<T>, WM, WN, NS, NF, false>(ConvLoader<T>, DenseLoader<T>, int, int, int, int, int, EpiParams<T>);
+  template __global__ void gemm_nt_kernel<T, ConvLoader<T>, WM, WN, NS, NF, false, false>(ConvLoader<T>, DenseLoader<T>, int, int, int, int, int, EpiParams<T>);
 RL_INST_NT_CONV(bf16_t, 2, 2, 2, 4) RL_INST_NT_CONV(bf16_t, 2, 2, 2, 3) RL_INST_NT_CONV(bf16_t, 4, 1, 2, 4)
 RL_INST_NT_CONV(float, 2, 2, 2, 4) RL_INST_NT_CONV(float, 2, 2, 2, 3) RL_INST_NT_CONV(float, 4, 1, 2, 4)
 #undef RL_INST_NT_CONV
@@ -444,12 +462,12 @@ template <typename T, int NB> struct ConvTaps<ConvLoader<T>, NB> : ConvTapsImpl<
 template <typename T, int NB> struct ConvTaps<ConvLoaderDirect<T>, NB> : ConvTapsImpl<ConvLoaderDirect<T>, T, NB> {};
 
 // One (split, tile) of a TN problem; `logical` = split * ntiles + tile.  Two LDS stages of BP reduction rows.
-template <typename T, typename BLoader, bool TR, int WI, int WJ>
+template <typename T, typename BLoader, bool TR, int WI, int WJ, bool X3>
 __device__ __forceinline__ void tn_tile_body(const T* __restrict__ A, int64_t lda, BLoader lb, int P, int I, int J, int tiles_j, int ntiles,
                                              int nsplit, int pchunk, int how, TnEpi ep, int logical) {
-  typedef typename MmaOf<T>::type Mma;
+  typedef typename MmaSel<T, X3>::type Mma;      // X3 (T = float): the 32 reduction rows of a tile are ONE split-bf16 16x16x32 step
   typedef TnGeo<T> G;
-  constexpr int BP = G::BP, KST = G::KSTEPS, NST = 2;
+  constexpr int BP = G::BP, KST = G::BP / Mma::K, NST = 2;
   constexpr int BI = 64 * WI, BJ = 64 * WJ;
   constexpr int RPA = BI * (int)sizeof(T), RPB = BJ * (int)sizeof(T);         // row pitches (bytes)
   constexpr int A_BYTES = BP * RPA, B_BYTES = BP * RPB, STAGE = A_BYTES + B_BYTES;
@@ -509,14 +527,14 @@ __device__ __forceinline__ void tn_tile_body(const T* __restrict__ A, int64_t ld
   floatx4 csum[4];
 #pragma unroll
   for (int f = 0; f < 4; ++f) csum[f] = floatx4{0.f, 0.f, 0.f, 0.f};
-  typename Mma::Frag ones;
-  if constexpr (sizeof(T) == 2) {
+  typename MmaSel<T, false>::type::Frag ones;
+  bf16x8_t ones16;                                   // (X3: the column sums multiply hi and lo by bf16 ones)
+  {
     typedef __attribute__((ext_vector_type(8))) short short8_t;
     const short8_t o = {0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80, 0x3F80};
-    ones = __builtin_bit_cast(bf16x8_t, o);
-  } else {
-    ones = 1.0f;
+    ones16 = __builtin_bit_cast(bf16x8_t, o);
   }
+  if constexpr (sizeof(T) == 2) ones = ones16; else ones = 1.0f;
 
   // Fast addressing for full reduction tiles: one 64-bit source pointer per wave-instruction, advanced by a
   // constant (0 for lanes parked on the zero page); the checked path handles a ragged last tile.
@@ -649,6 +667,18 @@ __device__ __forceinline__ void tn_tile_body(const T* __restrict__ A, int64_t ld
         if constexpr (sizeof(T) == 2) {
           a[f] = tn_frag_bf16<TR, RPA>(At, ks, ca, l15, g);
           b[f] = tn_frag_bf16<TR, RPB>(Bt, ks, cb, l15, g);
+        } else if constexpr (X3) {
+          // K-slot e of group g = reduction row 4e + g (any bijection serves, the same for both operands): the eight ds_read_b32
+          // of the fp32 atom's eight steps, gathered into one fragment and split in registers
+          float xa[8], xb[8];
+#pragma unroll
+          for (int e = 0; e < 8; ++e) {
+            const int p = e * 4 + g;
+            xa[e] = *(const float*)(At + p * RPA + (((ca + l15) * 4) ^ tn_swz<float, RPA>(p)));
+            xb[e] = *(const float*)(Bt + p * RPB + (((cb + l15) * 4) ^ tn_swz<float, RPB>(p)));
+          }
+          a[f] = MmaBF16x3::split(xa);
+          b[f] = MmaBF16x3::split(xb);
         } else {
           const int p = ks * 4 + g;
           a[f] = *(const float*)(At + p * RPA + (((ca + l15) * 4) ^ tn_swz<float, RPA>(p)));
@@ -661,7 +691,14 @@ __device__ __forceinline__ void tn_tile_body(const T* __restrict__ A, int64_t ld
         for (int j = 0; j < 4; ++j) acc[i][j] = Mma::mma(b[j], a[i], acc[i][j]);
       if (do_colsum) {
 #pragma unroll
-        for (int f = 0; f < 4; ++f) csum[f] = Mma::mma(ones, a[f], csum[f]);   // every row of the result = sum_p A[p, i]
+        for (int f = 0; f < 4; ++f) {                                          // every row of the result = sum_p A[p, i]
+          if constexpr (X3) {
+            csum[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones16, a[f].lo, csum[f], 0, 0, 0);
+            csum[f] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(ones16, a[f].hi, csum[f], 0, 0, 0);
+          } else {
+            csum[f] = Mma::mma(ones, a[f], csum[f]);
+          }
+        }
       }
     }
   }
@@ -679,20 +716,20 @@ __device__ __forceinline__ void tn_tile_body(const T* __restrict__ A, int64_t ld
   }
 }
 
-template <typename T, typename BLoader, bool TR, int WI, int WJ>
+template <typename T, typename BLoader, bool TR, int WI, int WJ, bool X3 = false>
 __global__ void __launch_bounds__(256, 2)
 gemm_tn_kernel(const T* __restrict__ A, int64_t lda, BLoader lb, int P, int I, int J, int tiles_j, int ntiles,
                int nsplit, int pchunk, int how, TnEpi ep) {
   // 1-D grid of (split, tile) pairs: the XCD remap hands each XCD a contiguous run of them, so the tiles of one
   // reduction split (which share A / B row panels) sit behind one L2.
-  tn_tile_body<T, BLoader, TR, WI, WJ>(A, lda, lb, P, I, J, tiles_j, ntiles, nsplit, pchunk, how, ep, xcd_remap(blockIdx.x, ntiles * nsplit));
+  tn_tile_body<T, BLoader, TR, WI, WJ, X3>(A, lda, lb, P, I, J, tiles_j, ntiles, nsplit, pchunk, how, ep, xcd_remap(blockIdx.x, ntiles * nsplit));
 }
 
 // Grouped form: up to TN_GROUP_MAX dense problems that share the reduction length P in ONE launch, each workgroup owning one
 // 128x128 tile of one problem over the whole reduction (no split: nothing to fold).  The four weight gradients of a transformer
 // layer are 432 such tiles - one round of the chip's 512 workgroup slots - where launched one by one each needs a 3-4 way
 // reduction split (slab write + fold pass) to fill the chip: 8 launches and ~75 MB of slab traffic per layer become 1 launch.
-template <typename T, bool TR>
+template <typename T, bool TR, bool X3 = false>
 __global__ void __launch_bounds__(256, 2)
 gemm_tn_group_kernel(TnGroup<T> grp, int P, int pchunk) {
   const int logical = xcd_remap(blockIdx.x, grp.total_tiles);
@@ -704,7 +741,7 @@ gemm_tn_group_kernel(TnGroup<T> grp, int P, int pchunk) {
   TnEpi ep;
   ep.out = pr.out; ep.ldo = pr.ldo; ep.colsum = pr.colsum; ep.alpha = grp.alpha; ep.overwrite = grp.overwrite;
   ep.tile_list = grp.tile_list; ep.n_tiles = grp.n_tiles; ep.list_rows = grp.list_rows;
-  tn_tile_body<T, DenseLoader<T>, TR, 2, 2>(pr.A, pr.lda, lb, P, pr.I, pr.J, pr.tiles_j, pr.ntiles, 1, pchunk, TN_OUT_DIRECT, ep,
+  tn_tile_body<T, DenseLoader<T>, TR, 2, 2, X3>(pr.A, pr.lda, lb, P, pr.I, pr.J, pr.tiles_j, pr.ntiles, 1, pchunk, TN_OUT_DIRECT, ep,
                                             logical - pr.tile_begin);
 }
 
@@ -886,7 +923,18 @@ static int launch_tn_tile(hipStream_t st, const T* A, int64_t lda, const BLoader
     ProfScope ps(st, sizeof(typename BLoader::KPos) == sizeof(typename DenseLoader<T>::KPos) ? PK_GEMM_TN : PK_CONV_TN, 2.0 * P * I * J);
     if constexpr (sizeof(typename BLoader::KPos) == sizeof(typename DenseLoader<T>::KPos))
       if (lb.rows_dev != nullptr) prof_set_exec(lb.rows_dev, 2.0 * I * J, G::BP, P);       // the reduction stops at the device-side row bound
-    if (sizeof(T) == 2 && g_tn_tr) {
+    constexpr bool kDenseB = sizeof(typename BLoader::KPos) == sizeof(typename DenseLoader<T>::KPos);
+    bool x3_done = false;
+    if constexpr (kDenseB && sizeof(T) == 4) {
+      if (ep.x3) {
+        static bool a3 = false;
+        if (!a3) { (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<T, BLoader, false, WI, WJ, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr); a3 = true; }
+        RL_LAUNCH((gemm_tn_kernel<T, BLoader, false, WI, WJ, true>), grid, dim3(256), lds, st, A, lda, lb, P, I, J, tiles_j, ntiles, nsplit, pchunk, how, ep);
+        x3_done = true;
+      }
+    }
+    if (x3_done) {
+    } else if (sizeof(T) == 2 && g_tn_tr) {
       static bool a1 = false;
       if (!a1) { (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<T, BLoader, true, WI, WJ>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr); a1 = true; }
       RL_LAUNCH((gemm_tn_kernel<T, BLoader, true, WI, WJ>), grid, dim3(256), lds, st, A, lda, lb, P, I, J, tiles_j, ntiles, nsplit, pchunk, how, ep);
@@ -905,6 +953,7 @@ static int launch_tn(hipStream_t st, const T* A, int64_t lda, const BLoader& lb,
   if (P <= 0 || I <= 0 || J <= 0) return RL_OK;
   typedef TnGeo<T> G;
   if (lda % G::VEC) return RL_ERR_ARG;
+  if (ep.x3 && sizeof(T) != 4) return RL_ERR_ARG;
   TnPlan pl;
   const int rc = tn_plan((int)sizeof(T), false, P, I, J, ep.mode != TN_PLAIN, ep.Cin, ep.slab != nullptr, ep.slab_elems, pl);
   if (rc != RL_OK) return rc;
@@ -914,11 +963,12 @@ static int launch_tn(hipStream_t st, const T* A, int64_t lda, const BLoader& lb,
 
 template <typename T>
 int gemm_tn_group(hipStream_t st, int n, const TnGroupProblem<T>* probs, int P, float alpha, int overwrite, const int* tile_list,
-                  const int* n_tiles, int list_rows) {
+                  const int* n_tiles, int list_rows, int x3) {
   typedef TnGeo<T> G;
   if (n < 1 || n > TN_GROUP_MAX || P <= 0) return RL_ERR_ARG;
+  if (x3 && sizeof(T) != 4) return RL_ERR_ARG;
   TnGroup<T> grp;
-  grp.n = n; grp.alpha = alpha; grp.overwrite = overwrite;
+  grp.n = n; grp.alpha = alpha; grp.overwrite = overwrite; grp.x3 = x3;
   if (list_rows != 0 && list_rows != G::BP && !(list_rows == 16 && sizeof(T) == 2)) return RL_ERR_ARG;
   // A caller that hands over a live-block list may rely on it (a live-row step leaves stale values in the rows of unlisted blocks):
   // the list is honoured or the call fails - it is never silently dropped.
@@ -946,16 +996,18 @@ int gemm_tn_group(hipStream_t st, int n, const TnGroupProblem<T>* probs, int P, 
   const int lds_attr = (int)(2 * (size_t)G::BP * 256 * sizeof(T)) + TN_LIST_LDS_MAX;
   ProfScope ps(st, PK_GEMM_TN, flops);
   if (grp.tile_list != nullptr) prof_set_exec(grp.n_tiles, flops / P * grp.list_rows, sizeof(T) == 2 && grp.list_rows == 16 ? 4 : 1, P / grp.list_rows);   // live blocks only
-#define RL_TN_GROUP(TRV) do { \
+#define RL_TN_GROUP(TRV, X3V) do { \
     static bool attr = false; \
-    if (!attr) { (void)hipFuncSetAttribute((const void*)gemm_tn_group_kernel<T, TRV>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr); attr = true; } \
-    RL_LAUNCH((gemm_tn_group_kernel<T, TRV>), dim3(total), dim3(256), lds, st, grp, P, pchunk); } while (0)
-  if (sizeof(T) == 2 && g_tn_tr) RL_TN_GROUP(true); else RL_TN_GROUP(false);
+    if (!attr) { (void)hipFuncSetAttribute((const void*)gemm_tn_group_kernel<T, TRV, X3V>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr); attr = true; } \
+    RL_LAUNCH((gemm_tn_group_kernel<T, TRV, X3V>), dim3(total), dim3(256), lds, st, grp, P, pchunk); } while (0)
+  if (sizeof(T) == 2 && g_tn_tr) RL_TN_GROUP(true, false);
+  else if (sizeof(T) == 4 && grp.x3) RL_TN_GROUP(false, (sizeof(T) == 4));
+  else RL_TN_GROUP(false, false);
 #undef RL_TN_GROUP
   return hipGetLastError() == hipSuccess ? RL_OK : RL_ERR_LAUNCH;
 }
-template int gemm_tn_group<bf16_t>(hipStream_t, int, const TnGroupProblem<bf16_t>*, int, float, int, const int*, const int*, int);
-template int gemm_tn_group<float>(hipStream_t, int, const TnGroupProblem<float>*, int, float, int, const int*, const int*, int);
+template int gemm_tn_group<bf16_t>(hipStream_t, int, const TnGroupProblem<bf16_t>*, int, float, int, const int*, const int*, int, int);
+template int gemm_tn_group<float>(hipStream_t, int, const TnGroupProblem<float>*, int, float, int, const int*, const int*, int, int);
 
 template <typename T>
 int gemm_tn(hipStream_t st, const T* A, int64_t lda, const T* B, int64_t ldb, int P, int I, int J, const TnEpi& ep,

@@ -25,7 +25,9 @@ from . import _capi
 from .config import RealiseConfig, variant_of
 from .init import tensor_init, tensor_specs, synth_glyph_table
 
-_DTYPES = {"bf16": (_capi.BF16, torch.bfloat16), "fp32": (_capi.F32, torch.float32)}
+# compute_dtype -> (C ABI dtype, tensor dtype).  "bf16x3": fp32 tensors everywhere; the Linear GEMMs multiply split-bf16 (three bf16
+# MFMAs per product, fp32 accumulation), convolutions and attention stay exact fp32.
+_DTYPES = {"bf16": (_capi.BF16, torch.bfloat16), "fp32": (_capi.F32, torch.float32), "bf16x3": (_capi.F32_BF16X3, torch.float32)}
 _AR_TRAIN, _AR_UNUSED, _AR_FROZEN, _AR_BUF_F32, _AR_BUF_I64 = range(5)
 
 
@@ -70,7 +72,8 @@ class RealiseModule(nn.Module):
         self.vocab_size = config.vocab_size
         self.compute_dtype = compute_dtype or os.environ.get("REALISE_DTYPE", "bf16")
         if self.compute_dtype not in _DTYPES:
-            raise ValueError("compute_dtype must be 'bf16' or 'fp32'")
+            raise ValueError("compute_dtype must be 'bf16', 'fp32' or 'bf16x3'")
+        self._storage = "bf16" if self.compute_dtype == "bf16" else "fp32"      # the dtype of activations, logits and taps
         self._tie = bool(tie)
         # dtype of the returned logits.  "auto" (default): fp32 in eval mode - the reference contract, `logits.cpu().numpy()` in
         # run.py:262 / test.py:140 needs it - and the compute dtype in training mode, where the trainer only reads the loss
@@ -80,7 +83,7 @@ class RealiseModule(nn.Module):
         self.train_logits = True
         if self.logits_dtype not in ("auto", "bf16", "fp32"):
             raise ValueError("logits_dtype must be 'auto', 'bf16' or 'fp32'")
-        if self.compute_dtype == "fp32" and self.logits_dtype == "bf16":
+        if self._storage == "fp32" and self.logits_dtype == "bf16":
             raise ValueError("bf16 logits need compute_dtype='bf16'")
         self.static_weights = False         # serving: promise that parameters only change through tracked paths (see _ensure_engine)
         self._fwd_gen = 0
@@ -161,7 +164,7 @@ class RealiseModule(nn.Module):
     def _apply(self, fn, recurse=True):
         probe = fn(torch.zeros(1, dtype=torch.float32))
         if probe.dtype != torch.float32:
-            raise RuntimeError("master parameters stay fp32; choose the compute dtype with compute_dtype='bf16'|'fp32'")
+            raise RuntimeError("master parameters stay fp32; choose the compute dtype with compute_dtype='bf16'|'fp32'|'bf16x3'")
         self._arenas = [fn(a) if a.is_floating_point() else a.to(probe.device) for a in self._arenas]
         self._grads = fn(self._grads)
         self._anchor = torch.zeros((), requires_grad=True, device=probe.device)
@@ -477,7 +480,7 @@ class RealiseModule(nn.Module):
         lib = _capi.load()
         ptr, n = C.c_void_p(), C.c_int64()
         _capi.check(lib.realise_engine_tap(self._engine, name.encode(), C.byref(ptr), C.byref(n)), "tap " + name)
-        esz = 2 if self.compute_dtype == "bf16" else 4
+        esz = 2 if self._storage == "bf16" else 4
         off = ptr.value - self._ws.data_ptr()
         return self._ws[off:off + n.value * esz].view(_DTYPES[self.compute_dtype][1])
 
@@ -576,9 +579,9 @@ class RealiseModule(nn.Module):
         cb.loss_out = loss.data_ptr() if loss is not None else None
         # reference contract: fp32 logits (models.py:859) from the bf16 engine - written by the classifier kernel's own epilogue next to
         # the bf16 ones the loss reads (realise_batch.logits_f32_out, round 6: no cast pass over [B, S, V])
-        want = self.logits_dtype if self.logits_dtype != "auto" else ("fp32" if not training else self.compute_dtype)
+        want = self.logits_dtype if self.logits_dtype != "auto" else ("fp32" if not training else self._storage)
         wide = None
-        if not no_logits and want != self.compute_dtype:
+        if not no_logits and want != self._storage:
             wide = torch.empty((B, S, self.vocab_size), dtype=torch.float32, device=self.device)
             cb.logits_f32_out = wide.data_ptr()
         _capi.check(_capi.load().realise_engine_forward(self._engine, self._stream(), C.byref(cb)), "realise_engine_forward")
