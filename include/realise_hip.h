@@ -210,7 +210,11 @@ int realise_sum_fuse_bwd(void* stream, int dtype, const void* dfused, void* dber
 /* nn.BatchNorm2d over an NHWC activation viewed as [P = N*H*W][C] (src/char_cnn.py:17-28), optional fused ReLU.  training:
  * batch statistics (two passes: mean, then centred squares), running statistics updated with the unbiased variance and
  * `momentum`, num_batches_tracked += 1 (nullable), save_mean / save_rstd [C] for the backward.  scratch: 4*C floats.
- * Backward: relu_src = the forward's y when ReLU was fused (NULL otherwise); dgamma / dbeta are ACCUMULATED; scratch 2*C floats. */
+ * Backward: relu_src = the forward's y when ReLU was fused (NULL otherwise); dgamma / dbeta are ACCUMULATED; scratch 2*C floats.
+ * The forms the engine runs (device-side row bound, glyph multiplicities, record scratch, two inputs / two branches, eval finalize) are
+ * realise_batchnorm_stats_rows / _apply_rows / _bwd_rows in realise_hip_debug.h; pinned element by element by
+ * tests/test_tower_edges_gpu.py: the ReLU mask is relu_src > 0 (-0.0 and +0.0 mask, the smallest normal passes); rows at or behind the
+ * bound are neither read nor written; eval leaves the running buffers and num_batches_tracked bit-unchanged. */
 int realise_batchnorm_fwd(void* stream, int dtype, const void* x, int P, int C, const float* gamma, const float* beta, float eps, float momentum,
                           float* running_mean, float* running_var, int64_t* num_batches_tracked, int training, int relu, void* y,
                           float* save_mean, float* save_rstd, float* scratch);

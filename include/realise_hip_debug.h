@@ -99,7 +99,9 @@ void realise_set_ln(int key, int value);
  * stats: mean / rstd / scale / shift [C], running buffers updated (unbiased variance), num_batches_tracked += 1; sq_scratch: C floats.
  * bwd: dx = gamma rstd (g - w sum(g) / n - xhat w sum(g xhat) / n) with g = dy masked by relu_src > 0; dgamma / dbeta are ADDED to;
  * xb != NULL: a second normalisation sharing dy and the mask (bn2 + shortcut BN of a BasicBlock; one pass reads dy and the mask for
- * both); sums: 4C floats of scratch.  tools/bn_probe.py times them; tests/test_ops_gpu.py checks fast against generic paths. */
+ * both - taken while 4 C fits the engine's 2048-float sums scratch, realise_debug_bn_plan says which -); sums: 4C floats of scratch.
+ * tools/bn_probe.py times them; tests/test_ops_gpu.py checks fast against generic paths; the bounded forms below are pinned element by
+ * element. */
 int realise_batchnorm_stats_ex(void* stream, const void* x, int P, int C, int hw, const float* counts, int n_stat, const float* gamma, const float* beta,
                                float eps, float momentum, float* running_mean, float* running_var, int64_t* num_batches_tracked, float* mean, float* rstd,
                                float* scale, float* shift, float* sq_scratch, float* slots);
@@ -191,6 +193,66 @@ int realise_conv_tn_ex(void* stream, int dtype, const void* A, int64_t lda, cons
  * 128 x 192 two-per-CU with exact row masking under a device-side row count. */
 int realise_debug_nt_path(int dtype, int M, int N, int K, int mode, int accumulate, int has_aux, int64_t lda, int64_t ldb, int64_t ldo,
                           int64_t ldaux, int rows_dev_given);
+
+/* What the BatchNorm launches decide on the host for a [P, C] map of images of hw pixels, with the knobs as they stand
+ * (realise_set_ln keys 2 and 3): the host functions the launchers themselves act on, exported so that tests can pin the kernel a case
+ * is meant for (tests/tower_cases.py, tests/test_tower_edges_gpu.py; invariants swept in tests/test_tower_cases_cpu.py).
+ * slots_given: the record scratch is passed (the engine always does); branches: 1, or 2 = the backward of bn2 + the shortcut's BN.
+ * Per pass - stats (training statistics), apply, bwd_reduce, bwd_apply -: kernel 0 generic, 1 the 16-byte kernels, 2 the one-pass
+ * statistics (bn_stats_train16; stats only), 3 the paired backward (bn_bwd_reduce2 / bn_bwd_apply2; both backward passes or neither);
+ * reductions: g row chunks with one record of `stride` floats each, folded by fold_wgs workgroups (stride 0: no records - fp32
+ * atomics); overwrite 1: the outputs are overwritten (records + fold), 0: accumulated (atomics).  Two-pass statistics run two
+ * reductions of the reported plan.  Maps report g = stride = fold_wgs = 0, overwrite = 1.  Returns 0, or non-zero where a launch would
+ * be refused. */
+typedef struct realise_bn_pass { int32_t kernel, g, stride, fold_wgs, overwrite; } realise_bn_pass;
+typedef struct realise_bn_plan { realise_bn_pass stats, apply, bwd_reduce, bwd_apply; } realise_bn_plan;
+int realise_debug_bn_plan(int dtype, int P, int C, int hw, int slots_given, int branches, realise_bn_plan* plan);
+/* Which kernel realise_conv_nt reaches for a gathered launch with the knobs as they stand (realise_set_conv_c64,
+ * realise_set_nt_allow_n96): 12 = conv_c64_nt (bf16, the 64 -> 64 channel 3x3 / stride 1 / pad 1 convolution on 16x16 maps without
+ * img_index, N = 64, ldb = K = 576, M = rows a multiple of 256, ldo = 64, alpha 1, a plain store or mode 8 with scale and shift),
+ * else the realise_debug_nt_path id of the 4-wave kernel (1, 2, 3), 0 nothing to launch, -1 refused.  The host function
+ * gemm_nt_conv itself acts on; src / img_index are only compared with NULL.  has_scale: mode 8 carries col_scale and the shift. */
+int realise_debug_conv_nt_path(int dtype, const realise_conv_geom* a, int64_t ldb, int M, int N, int K, int mode, int accumulate, int has_aux,
+                               int has_scale, int64_t ldo, int64_t ldaux);
+/* realise_conv_nt and realise_gemm_nt exactly as the engine's glyph branch launches them, with what the operator boundary hides:
+ * rows_dev (device, nullable) bounds the output rows - whole images of a gathered launch; rows at or behind it are not read -,
+ * index_rows the number of images in the table behind img_index (the 32-bit span check; 0 = not checked), and the evaluation-mode
+ * BatchNorm folded into the epilogue: mode 8, out = [relu](acc * col_scale[col] + ep->bias[col] (+ ep->aux)), the shift riding in
+ * ep->bias.  col_scale is valid with mode 8 only.  The dense form with B = W + 4 Co, ldb = 9 Co is the centre tap of a 3x3 convolution
+ * on 1x1 maps.  tests/test_tower_edges_gpu.py: bounds 0, one image, all with NaN in the images behind the bound, in the table images
+ * img_index skips and in the padding channels' weights; the rows behind the bound keep their bits under the storing epilogues the
+ * tests run (see realise_gemm_nt_rows above for the last live tile of a dense launch). */
+int realise_conv_nt_ex(void* stream, int dtype, const realise_conv_geom* a, const void* B, int64_t ldb, int M, int N, int K,
+                       const realise_epilogue* ep, const float* col_scale, int relu, const int* rows_dev, int64_t index_rows);
+int realise_gemm_nt_ex(void* stream, int dtype, const void* A, int64_t lda, const void* B, int64_t ldb, int M, int N, int K,
+                       const realise_epilogue* ep, const float* col_scale, int relu, const int* rows_dev);
+/* realise_conv_dgrad_s2 under a device-side bound, as the engine launches the stride-2 data gradients: *rows_dev (nullable) counts INPUT
+ * pixel rows (whole images); each parity-class launch takes a quarter of it.  Input rows at or behind the bound keep their bits in
+ * every class (tests/test_tower_edges_gpu.py: bounds 0, one image, all, with NaN in the gradient rows of the images behind it). */
+int realise_conv_dgrad_s2_ex(void* stream, int dtype, const realise_conv_geom* a, const void* B_classes, int64_t ldb, int Cin,
+                             const realise_epilogue* ep, const int* rows_dev);
+/* The BatchNorm passes as the engine's glyph branch launches them, for fp32 and bf16: every kernel bounded by *rows_dev (device,
+ * nullable; glyph dedup: distinct glyphs x hw - rows at or behind it are neither read nor written and do not enter a sum), `counts`
+ * (nullable) the multiplicity of each image of hw pixels, n_stat the true sample count (0: P), `slots` the record scratch
+ * (COL_SLOT_FLOATS = 262144 floats; NULL: the reductions use fp32 atomics on zero-filled scratch, as realise_batchnorm_fwd / _bwd do).
+ * Pinned by tests/test_tower_edges_gpu.py with NaN in every row at or behind the bound, in the counts behind the last live glyph and
+ * in the record scratch, and with guarded outputs whose rows behind the bound keep their bits.
+ * stats_rows: training != 0: mean / rstd / scale / shift [C] from the batch, running buffers updated (unbiased variance, momentum),
+ *   num_batches_tracked += 1 (nullable); training == 0: scale / shift from the running buffers, nothing else is touched (x may be
+ *   NULL).  scratch: 2 C floats.
+ * apply_rows: y = [relu](x1 sc1 + sh1 [+ x2 sc2 + sh2]) (x2 nullable: relu(bn2(c2) + bns(cs)) of a BasicBlock).
+ * bwd_rows: as realise_batchnorm_bwd_ex (xb nullable: the second normalisation), any dtype, bounded; sums: 4 C floats. */
+int realise_batchnorm_stats_rows(void* stream, int dtype, const void* x, int P, int C, int hw, const float* counts, const int* rows_dev, int n_stat,
+                                 int training, const float* gamma, const float* beta, float eps, float momentum, float* running_mean,
+                                 float* running_var, int64_t* num_batches_tracked, float* mean, float* rstd, float* scale, float* shift,
+                                 float* scratch, float* slots);
+int realise_batchnorm_apply_rows(void* stream, int dtype, const void* x1, const float* scale1, const float* shift1, const void* x2,
+                                 const float* scale2, const float* shift2, void* y, int P, int C, int hw, int relu, const int* rows_dev);
+int realise_batchnorm_bwd_rows(void* stream, int dtype, const void* dy, const void* relu_src, int P, int C, int hw, const float* counts,
+                               const int* rows_dev, int n_stat,
+                               const void* xa, const float* mean_a, const float* rstd_a, const float* gamma_a, void* dxa, float* dgamma_a, float* dbeta_a,
+                               const void* xb, const float* mean_b, const float* rstd_b, const float* gamma_b, void* dxb, float* dgamma_b, float* dbeta_b,
+                               float* sums, float* slots);
 
 /* how many workspace plans the engine has installed (= whole-workspace zero fills) since it was created: a loop that alternates
  * batch shapes over per-shape workspace buffers (realise_engine_forget_workspace in realise_hip.h) must count one per shape */

@@ -57,6 +57,14 @@ class TnPlan(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("tile", "nsplit", "pchunk", "form", "fold", "fold_sb")]
 
 
+class BnPass(C.Structure):
+    _fields_ = [(n, C.c_int32) for n in ("kernel", "g", "stride", "fold_wgs", "overwrite")]
+
+
+class BnPlan(C.Structure):
+    _fields_ = [(n, BnPass) for n in ("stats", "apply", "bwd_reduce", "bwd_apply")]
+
+
 class Config(C.Structure):
     _fields_ = [(n, C.c_int32) for n in ("model_type", "dtype", "hidden", "heads", "intermediate", "vocab", "max_pos",
                                          "type_vocab", "bert_layers", "pho_layers", "out_layers", "num_fonts",
@@ -102,6 +110,14 @@ SYMBOLS = {
     "realise_layernorm_bwd_live": (_I, [_P, _P, _P, _P, _P, _P, _P, C.c_uint32, C.c_uint32, C.c_float, _P, _P, _P, _P, _I, _I]),
     "realise_batchnorm_stats_ex": (_I, [_P, _P, _I, _I, _I, _P, _I, _P, _P, C.c_float, C.c_float] + [_P] * 9),
     "realise_batchnorm_bwd_ex": (_I, [_P, _P, _P, _I, _I, _I, _P, _I] + [_P] * 7 + [_P] * 7 + [_P, _P]),
+    "realise_debug_bn_plan": (_I, [_I, _I, _I, _I, _I, _I, C.POINTER(BnPlan)]),
+    "realise_debug_conv_nt_path": (_I, [_I, C.POINTER(ConvGeom), _L, _I, _I, _I, _I, _I, _I, _I, _L, _L]),
+    "realise_conv_nt_ex": (_I, [_P, _I, C.POINTER(ConvGeom), _P, _L, _I, _I, _I, C.POINTER(Epilogue), _P, _I, _P, _L]),
+    "realise_conv_dgrad_s2_ex": (_I, [_P, _I, C.POINTER(ConvGeom), _P, _L, _I, C.POINTER(Epilogue), _P]),
+    "realise_gemm_nt_ex": (_I, [_P, _I, _P, _L, _P, _L, _I, _I, _I, C.POINTER(Epilogue), _P, _I, _P]),
+    "realise_batchnorm_stats_rows": (_I, [_P, _I, _P, _I, _I, _I, _P, _P, _I, _I, _P, _P, _F, _F] + [_P] * 9),
+    "realise_batchnorm_apply_rows": (_I, [_P, _I] + [_P] * 7 + [_I, _I, _I, _I, _P]),
+    "realise_batchnorm_bwd_rows": (_I, [_P, _I, _P, _P, _I, _I, _I, _P, _P, _I] + [_P] * 7 + [_P] * 7 + [_P, _P]),
     "realise_set_tn_split": (None, [_I]),
     "realise_set_conv_c64": (None, [_I]),
     "realise_set_branch_overlap": (None, [_I]),

@@ -36,7 +36,8 @@ template <typename T> ConvLoader<T> to_geom(const realise_conv_geom* g) {
 }  // namespace
 
 template <typename T>
-static int conv_dgrad_s2(hipStream_t st, const realise_conv_geom* a, const T* B, int64_t ldb, int Cin, const realise_epilogue* ep) {
+static int conv_dgrad_s2(hipStream_t st, const realise_conv_geom* a, const T* B, int64_t ldb, int Cin, const realise_epilogue* ep,
+                         const int* rows_dev = nullptr) {
   if (a->mode != 1 || a->stride != 2 || a->Hr != a->Wr || (a->Hr & (a->Hr - 1)) || a->Hr < 2 || a->img_index != nullptr) return RL_ERR_ARG;
   int hsh = 0; while ((1 << hsh) < a->Hr) ++hsh;
   const int nimg = a->rows / (a->Hr * a->Wr);
@@ -47,6 +48,7 @@ static int conv_dgrad_s2(hipStream_t st, const realise_conv_geom* a, const T* B,
     ConvLoader<T> g = to_geom<T>(a);
     g.rows = nimg * (a->Hr / 2) * (a->Wr / 2);
     g.par = c;
+    g.rows_dev = rows_dev;          // (in input-pixel rows: a class launch takes a quarter of it, ConvLoader::clamp_rows)
     int ntaps = nt;
     if (a->Hr == 2 && a->Hs == 1 && a->KH == 3 && a->KW == 3 && a->pad == 1) {      // one reachable tap per pixel of a 2x2 map
       g.tap_sel = ((c >> 1) + 1) * 3 + (c & 1) + 1;
@@ -564,6 +566,158 @@ int realise_debug_nt_path(int dtype, int M, int N, int K, int mode, int accumula
   if (dtype == REALISE_F32) return gemm_nt_path<float>(M, N, K, to_epi<float>(&e), lda, ldb, rows_dev_given != 0);
   if (dtype == REALISE_F32_BF16X3) return gemm_nt_path<float>(M, N, K, to_epi_x3(&e), lda, ldb, rows_dev_given != 0);
   return NT_PATH_REFUSED;
+}
+int realise_debug_bn_plan(int dtype, int P, int C, int hw, int slots_given, int branches, realise_bn_plan* plan) {
+  if (!plan || (dtype != REALISE_BF16 && dtype != REALISE_F32)) return RL_ERR_ARG;
+  BnPlan pl;
+  const int rc = bn_plan(dtype == REALISE_BF16 ? 2 : 4, P, C, hw, slots_given != 0, branches, pl);
+  const BnPass* src[4] = {&pl.stats, &pl.apply, &pl.bwd_reduce, &pl.bwd_apply};
+  realise_bn_pass* dst[4] = {&plan->stats, &plan->apply, &plan->bwd_reduce, &plan->bwd_apply};
+  for (int k = 0; k < 4; ++k) {
+    dst[k]->kernel = src[k]->kernel; dst[k]->g = src[k]->g; dst[k]->stride = src[k]->stride; dst[k]->fold_wgs = src[k]->fold_wgs;
+    dst[k]->overwrite = src[k]->overwrite;
+  }
+  return rc;
+}
+int realise_debug_conv_nt_path(int dtype, const realise_conv_geom* a, int64_t ldb, int M, int N, int K, int mode, int accumulate, int has_aux,
+                               int has_scale, int64_t ldo, int64_t ldaux) {
+  static const uint64_t some_operand[2] = {0, 0};      // (only compared with nullptr)
+  if (!a) return NT_PATH_REFUSED;
+  realise_epilogue e;
+  memset(&e, 0, sizeof(e));
+  e.mode = mode; e.accumulate = accumulate; e.out = (void*)some_operand; e.ldo = ldo; e.aux = has_aux ? (const void*)some_operand : nullptr;
+  e.ldaux = ldaux; e.alpha = 1.0f; e.drop_scale = 1.0f;
+  if (has_scale) e.bias = (const float*)some_operand;
+  if (dtype == REALISE_BF16) {
+    EpiParams<bf16_t> p = to_epi<bf16_t>(&e);
+    if (has_scale) p.col_scale = (const float*)some_operand;
+    return conv_nt_path<bf16_t>(to_geom<bf16_t>(a), ldb, M, N, K, p);
+  }
+  if (dtype == REALISE_F32) {
+    EpiParams<float> p = to_epi<float>(&e);
+    if (has_scale) p.col_scale = (const float*)some_operand;
+    return conv_nt_path<float>(to_geom<float>(a), ldb, M, N, K, p);
+  }
+  return NT_PATH_REFUSED;
+}
+// realise_conv_nt / realise_gemm_nt as the engine's glyph branch launches them: the extended epilogue and the device-side bound
+int realise_conv_nt_ex(void* stream, int dtype, const realise_conv_geom* a, const void* B, int64_t ldb, int M, int N, int K,
+                       const realise_epilogue* ep, const float* col_scale, int relu, const int* rows_dev, int64_t index_rows) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!ep || !ep->out || !a) return RL_ERR_ARG;
+  if (dtype == REALISE_BF16) {
+    ConvLoader<bf16_t> g = to_geom<bf16_t>(a); g.rows_dev = rows_dev; g.index_rows = index_rows;
+    EpiParams<bf16_t> e = to_epi<bf16_t>(ep); e.col_scale = col_scale; e.relu = relu;
+    return gemm_nt_conv<bf16_t>(st, g, (const bf16_t*)B, ldb, M, N, K, e);
+  }
+  if (dtype == REALISE_F32) {
+    ConvLoader<float> g = to_geom<float>(a); g.rows_dev = rows_dev; g.index_rows = index_rows;
+    EpiParams<float> e = to_epi<float>(ep); e.col_scale = col_scale; e.relu = relu;
+    return gemm_nt_conv<float>(st, g, (const float*)B, ldb, M, N, K, e);
+  }
+  return RL_ERR_ARG;
+}
+int realise_conv_dgrad_s2_ex(void* stream, int dtype, const realise_conv_geom* a, const void* B_classes, int64_t ldb, int Cin,
+                             const realise_epilogue* ep, const int* rows_dev) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!ep || !ep->out || !a) return RL_ERR_ARG;
+  if (dtype == REALISE_BF16) return conv_dgrad_s2<bf16_t>(st, a, (const bf16_t*)B_classes, ldb, Cin, ep, rows_dev);
+  if (dtype == REALISE_F32) return conv_dgrad_s2<float>(st, a, (const float*)B_classes, ldb, Cin, ep, rows_dev);
+  return RL_ERR_ARG;
+}
+int realise_gemm_nt_ex(void* stream, int dtype, const void* A, int64_t lda, const void* B, int64_t ldb, int M, int N, int K,
+                       const realise_epilogue* ep, const float* col_scale, int relu, const int* rows_dev) {
+  hipStream_t st = (hipStream_t)stream;
+  if (!ep || !ep->out) return RL_ERR_ARG;
+  if (dtype == REALISE_BF16) {
+    EpiParams<bf16_t> e = to_epi<bf16_t>(ep); e.col_scale = col_scale; e.relu = relu;
+    return gemm_nt<bf16_t>(st, (const bf16_t*)A, lda, (const bf16_t*)B, ldb, M, N, K, e, rows_dev);
+  }
+  if (dtype == REALISE_F32) {
+    EpiParams<float> e = to_epi<float>(ep); e.col_scale = col_scale; e.relu = relu;
+    return gemm_nt<float>(st, (const float*)A, lda, (const float*)B, ldb, M, N, K, e, rows_dev);
+  }
+  return RL_ERR_ARG;
+}
+}  // extern "C"
+namespace {
+RowBound bn_rows(const int* rows_dev, const float* counts, int hw, float* slots) {
+  RowBound rb; rb.rows_dev = rows_dev; rb.counts = counts; rb.hw = hw; rb.slots = slots;
+  return rb;
+}
+// Engine::bn_forward, with the atomics form of bn_fwd_t where no record scratch is given
+template <typename T>
+int bn_stats_rows_t(hipStream_t st, const T* x, int P, int C, int n, int training, const float* gamma, const float* beta, float eps, float momentum,
+                    float* rmean, float* rvar, int64_t* nbt, float* mean, float* rstd, float* scale, float* shift, float* scratch, const RowBound& rb) {
+  if (!training) return bn_finalize_eval(st, C, gamma, beta, eps, rmean, rvar, scale, shift);
+  if constexpr (sizeof(T) == 2) {
+    if (bn_stats_train16(st, x, P, C, n, gamma, beta, eps, momentum, rmean, rvar, mean, rstd, scale, shift, nbt, rb) == RL_OK) return RL_OK;
+  }
+  if (rb.slots != nullptr) {
+    RL_TRY(col_sum<T>(st, x, P, C, mean, rb, 1.0f / (float)n));          // the fold writes the mean directly
+  } else {
+    RL_TRY(fill_f32(st, scratch, 0.0f, 2 * C));
+    RL_TRY(col_sum<T>(st, x, P, C, scratch, rb));
+    RL_TRY(bn_finalize_mean(st, scratch, C, n, mean));
+  }
+  RL_TRY(col_sumsq_centered<T>(st, x, P, C, mean, scratch + C, rb));
+  return bn_finalize_train(st, mean, scratch + C, C, n, gamma, beta, eps, momentum, rmean, rvar, rstd, scale, shift, nbt);
+}
+// Engine::resnet_backward's BatchNorm part: paired where bn_bwd_reduce2 takes it, else the second normalisation first, then the first
+template <typename T>
+int bn_bwd_rows_t(hipStream_t st, const T* g, const T* o, int P, int C, int ns, const T* xa, const float* mean_a, const float* rstd_a,
+                  const float* gamma_a, T* dxa, float* dgamma_a, float* dbeta_a, const T* xb, const float* mean_b, const float* rstd_b,
+                  const float* gamma_b, T* dxb, float* dgamma_b, float* dbeta_b, float* sums, const RowBound& rb) {
+  if (xb != nullptr) {
+    if constexpr (sizeof(T) == 2) {
+      if (bn_bwd_reduce2(st, g, o, xa, mean_a, rstd_a, xb, mean_b, rstd_b, P, C, sums, rb) == RL_OK)
+        return bn_bwd_apply2(st, g, o, xa, mean_a, rstd_a, gamma_a, dxa, dgamma_a, dbeta_a, xb, mean_b, rstd_b, gamma_b, dxb, dgamma_b, dbeta_b, sums, P, C, rb, ns);
+    }
+    if (rb.slots == nullptr) RL_TRY(fill_f32(st, sums, 0.0f, 2 * C));
+    RL_TRY(bn_bwd_reduce<T>(st, g, o, xb, mean_b, rstd_b, P, C, sums, rb));
+    RL_TRY(bn_bwd_apply<T>(st, g, o, xb, mean_b, rstd_b, gamma_b, sums, P, C, dxb, dgamma_b, dbeta_b, rb, ns));
+  }
+  if (rb.slots == nullptr) RL_TRY(fill_f32(st, sums, 0.0f, 2 * C));
+  RL_TRY(bn_bwd_reduce<T>(st, g, o, xa, mean_a, rstd_a, P, C, sums, rb));
+  return bn_bwd_apply<T>(st, g, o, xa, mean_a, rstd_a, gamma_a, sums, P, C, dxa, dgamma_a, dbeta_a, rb, ns);
+}
+}  // namespace
+extern "C" {
+int realise_batchnorm_stats_rows(void* stream, int dtype, const void* x, int P, int C, int hw, const float* counts, const int* rows_dev, int n_stat,
+                                 int training, const float* gamma, const float* beta, float eps, float momentum, float* running_mean,
+                                 float* running_var, int64_t* num_batches_tracked, float* mean, float* rstd, float* scale, float* shift,
+                                 float* scratch, float* slots) {
+  if (!gamma || !beta || !scale || !shift || !running_mean || !running_var || P < 1 || C < 4 || (C & 3) || hw < 1) return RL_ERR_ARG;
+  if (training && (!x || !mean || !rstd || !scratch)) return RL_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const RowBound rb = bn_rows(rows_dev, counts, hw, slots);
+  const int n = n_stat > 0 ? n_stat : P;
+  RL_BY_DTYPE(bn_stats_rows_t<bf16_t>(st, (const bf16_t*)x, P, C, n, training, gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked,
+                                      mean, rstd, scale, shift, scratch, rb),
+              bn_stats_rows_t<float>(st, (const float*)x, P, C, n, training, gamma, beta, eps, momentum, running_mean, running_var, num_batches_tracked,
+                                     mean, rstd, scale, shift, scratch, rb));
+}
+int realise_batchnorm_apply_rows(void* stream, int dtype, const void* x1, const float* scale1, const float* shift1, const void* x2,
+                                 const float* scale2, const float* shift2, void* y, int P, int C, int hw, int relu, const int* rows_dev) {
+  if (!x1 || !scale1 || !shift1 || !y || (x2 && (!scale2 || !shift2)) || P < 1 || C < 4 || (C & 3) || hw < 1) return RL_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const RowBound rb = bn_rows(rows_dev, nullptr, hw, nullptr);
+  RL_BY_DTYPE(bn_apply<bf16_t>(st, (const bf16_t*)x1, scale1, shift1, (const bf16_t*)x2, scale2, shift2, (bf16_t*)y, P, C, relu, rb),
+              bn_apply<float>(st, (const float*)x1, scale1, shift1, (const float*)x2, scale2, shift2, (float*)y, P, C, relu, rb));
+}
+int realise_batchnorm_bwd_rows(void* stream, int dtype, const void* dy, const void* relu_src, int P, int C, int hw, const float* counts,
+                               const int* rows_dev, int n_stat,
+                               const void* xa, const float* mean_a, const float* rstd_a, const float* gamma_a, void* dxa, float* dgamma_a, float* dbeta_a,
+                               const void* xb, const float* mean_b, const float* rstd_b, const float* gamma_b, void* dxb, float* dgamma_b, float* dbeta_b,
+                               float* sums, float* slots) {
+  if (!dy || !xa || !dxa || !sums || P < 1 || C < 4 || (C & 3) || hw < 1 || (xb && !dxb)) return RL_ERR_ARG;
+  hipStream_t st = (hipStream_t)stream;
+  const RowBound rb = bn_rows(rows_dev, counts, hw, slots);
+  const int ns = n_stat > 0 ? n_stat : P;
+  RL_BY_DTYPE(bn_bwd_rows_t<bf16_t>(st, (const bf16_t*)dy, (const bf16_t*)relu_src, P, C, ns, (const bf16_t*)xa, mean_a, rstd_a, gamma_a, (bf16_t*)dxa, dgamma_a,
+                                    dbeta_a, (const bf16_t*)xb, mean_b, rstd_b, gamma_b, (bf16_t*)dxb, dgamma_b, dbeta_b, sums, rb),
+              bn_bwd_rows_t<float>(st, (const float*)dy, (const float*)relu_src, P, C, ns, (const float*)xa, mean_a, rstd_a, gamma_a, (float*)dxa, dgamma_a,
+                                   dbeta_a, (const float*)xb, mean_b, rstd_b, gamma_b, (float*)dxb, dgamma_b, dbeta_b, sums, rb));
 }
 int64_t realise_engine_plan_installs(const realise_engine* e) { return e ? e->impl->plan_install_count() : -1; }
 void realise_engine_forget_workspace(realise_engine* e, void* workspace) { if (e) e->impl->forget_workspace(workspace); }

@@ -1109,8 +1109,8 @@ template <typename T> struct Engine : EngineBase {
       // tensors instead of four passes over three)
       bool paired = false;
       if constexpr (sizeof(T) == 2) {
-        if (4 * Co <= 2048 &&
-            bn_bwd_reduce2(st, d_out, wp<T>(a.out), wp<T>(a.c2), wp<float>(a.bn2.mean), wp<float>(a.bn2.rstd), wp<T>(a.cs), wp<float>(a.bns.mean),
+        // (paired while bn_pair_ok says so: the 16-byte kernels apply and 4 Co floats fit the sums scratch)
+        if (bn_bwd_reduce2(st, d_out, wp<T>(a.out), wp<T>(a.c2), wp<float>(a.bn2.mean), wp<float>(a.bn2.rstd), wp<T>(a.cs), wp<float>(a.bns.mean),
                            wp<float>(a.bns.rstd), Pn, Co, sums, rb) == RL_OK) {
           RL_TRY(bn_bwd_apply2(st, d_out, wp<T>(a.out), wp<T>(a.c2), wp<float>(a.bn2.mean), wp<float>(a.bn2.rstd), pp(o.bn2.g), dc2, gp(o.bn2.g),
                                gp(o.bn2.b), wp<T>(a.cs), wp<float>(a.bns.mean), wp<float>(a.bns.rstd), pp(o.bns.g), dcs, gp(o.bns.g), gp(o.bns.b),

@@ -433,9 +433,13 @@ enum NtPath {
   NT_PATH_8W_256x192 = 5, NT_PATH_8W_128x192 = 6, NT_PATH_8W_128x192Q = 7, NT_PATH_8W_KTAIL = 8,      // gemm_nt8.hip
   NT_PATH_8P = 9, NT_PATH_8P_MDEV = 10,                                                               // gemm_nt8p.hip
   NT_PATH_8W_MEXACT = 11,    // gemm_nt8.hip, 128x192 two-per-CU bounded by a device-side row count with exact row masking
+  NT_PATH_C64 = 12,          // conv_c64_nt.hip (gathered launches only: conv_nt_path)
 };
 template <typename T>
 int gemm_nt_path(int M, int N, int K, const EpiParams<T>& ep, int64_t lda, int64_t ldb, bool rows_dev);
+// the same for a gathered launch (realise_debug_conv_nt_path): what gemm_nt_conv acts on; `la` finalized
+template <typename T>
+int conv_nt_path(const ConvLoader<T>& la, int64_t ldb, int M, int N, int K, const EpiParams<T>& ep);
 void set_nt8_group_m(int g);       // tile order of the 8-wave NT kernels: 0/1 row-major, g > 1: g tile rows per column step (L2 blocking)
 
 void tn_fold_launch(hipStream_t st, const TnEpi& ep, int nsplit, int I, int J);     // out += alpha * sum of the split slabs, fixed order

@@ -69,6 +69,9 @@ gemm_nt_kernel(ALoader la, DenseLoader<T> lb, int M, int N, int K, int tiles_n, 
   la.clamp_rows();
   const int live = ((la.rows + BM_ - 1) / BM_) * tiles_n;
   if ((int)blockIdx.x >= live) return;
+  // A parity-class launch scatters its rows over the input map: the rows at or behind the device-side bound are not written (a storing
+  // class launch left zeros in the pixels of dead images that fell into its last live tile; the accumulating one already left them alone).
+  if (ep.rm_hw_shift >= 0) M = min(M, la.rows);
   const int tile = xcd_remap(blockIdx.x, live < ntiles ? live : ntiles);
   const int tm = tile / tiles_n, tn = tile - tm * tiles_n;
   const int m0 = tm * BM_, n0 = tn * BN_;
@@ -393,22 +396,36 @@ int gemm_nt(hipStream_t st, const T* A, int64_t lda, const T* B, int64_t ldb, in
   la.rows_dev = rows_dev;
   return launch_nt<T, DenseLoader<T>>(st, la, B, ldb, M, N, K, ep);
 }
+// Which kernel a gathered launch reaches (realise_debug_conv_nt_path): the argument checks of gemm_nt_conv, the geometry test of the
+// LDS-resident 64-channel kernel, else the choice of launch_nt.  `la` is finalized.
 template <typename T>
-int gemm_nt_conv(hipStream_t st, const ConvLoader<T>& la_, const T* B, int64_t ldb, int M, int N, int K, const EpiParams<T>& ep) {
-  if (la_.C % Geo<T>::VEC || ep.out_f32 != nullptr || (ep.col_scale != nullptr && ep.mode != EPI_AFFINE)) return RL_ERR_ARG;
-  ConvLoader<T> la = la_;
-  la.finalize();
-  if (la.K != K || !la.span_ok()) return RL_ERR_ARG;
-  if (la.par >= 0 && (la.par > 3 || la.mode != 1 || la.stride != 2 || la.hw_shift < 2 || la.w_shift < 1 || la.img_index != nullptr)) return RL_ERR_ARG;
+int conv_nt_path(const ConvLoader<T>& la, int64_t ldb, int M, int N, int K, const EpiParams<T>& ep) {
+  if (la.C % Geo<T>::VEC || ep.out_f32 != nullptr || (ep.col_scale != nullptr && ep.mode != EPI_AFFINE)) return NT_PATH_REFUSED;
+  if (la.K != K || !la.span_ok()) return NT_PATH_REFUSED;
+  if (la.par >= 0 && (la.par > 3 || la.mode != 1 || la.stride != 2 || la.hw_shift < 2 || la.w_shift < 1 || la.img_index != nullptr)) return NT_PATH_REFUSED;
   if constexpr (sizeof(T) == 2) {
     // 64 -> 64 channels, 3x3 / stride 1 / pad 1 on 16x16 maps (glyph ResNet block 1), plain store: the LDS-resident image + weights kernel
     if (g_conv_c64 && la.par < 0 && la.C == 64 && la.KH == 3 && la.KW == 3 && la.stride == 1 && la.pad == 1 && la.mode <= 1 &&
         la.Hr == 16 && la.Wr == 16 && la.Hs == 16 && la.Ws == 16 && la.img_index == nullptr && N == 64 && K == 576 && ldb == 576 &&
         M == la.rows && (M % 256) == 0 && (int64_t)M * 128 < 0xFFFFFE00ll && ep.out2 == nullptr && ep.alpha == 1.0f && ep.ldo == 64 && ep.rm_hw_shift < 0) {
-      if (ep.mode == EPI_STORE && ep.accumulate == 0 && ep.bias == nullptr && ep.col_scale == nullptr)
-        return conv_c64_nt(st, la.src, B, ep.out, M, la.rows_dev, la.mode);
-      if (ep.mode == EPI_AFFINE && ep.col_scale != nullptr && ep.bias != nullptr && (ep.aux == nullptr || ep.ldaux == 64))
-        return conv_c64_nt(st, la.src, B, ep.out, M, la.rows_dev, la.mode, ep.col_scale, ep.bias, ep.aux, ep.relu);
+      if (ep.mode == EPI_STORE && ep.accumulate == 0 && ep.bias == nullptr && ep.col_scale == nullptr) return NT_PATH_C64;
+      if (ep.mode == EPI_AFFINE && ep.col_scale != nullptr && ep.bias != nullptr && (ep.aux == nullptr || ep.ldaux == 64)) return NT_PATH_C64;
+    }
+  }
+  return nt_path<T>(false, la.rows_dev != nullptr, M, N, K, ep, 0, ldb);
+}
+template int conv_nt_path<bf16_t>(const ConvLoader<bf16_t>&, int64_t, int, int, int, const EpiParams<bf16_t>&);
+template int conv_nt_path<float>(const ConvLoader<float>&, int64_t, int, int, int, const EpiParams<float>&);
+template <typename T>
+int gemm_nt_conv(hipStream_t st, const ConvLoader<T>& la_, const T* B, int64_t ldb, int M, int N, int K, const EpiParams<T>& ep) {
+  ConvLoader<T> la = la_;
+  la.finalize();
+  const int path = conv_nt_path<T>(la, ldb, M, N, K, ep);
+  if (path == NT_PATH_REFUSED) return RL_ERR_ARG;
+  if constexpr (sizeof(T) == 2) {
+    if (path == NT_PATH_C64) {
+      if (ep.mode == EPI_STORE) return conv_c64_nt(st, la.src, B, ep.out, M, la.rows_dev, la.mode);
+      return conv_c64_nt(st, la.src, B, ep.out, M, la.rows_dev, la.mode, ep.col_scale, ep.bias, ep.aux, ep.relu);
     }
   }
   return launch_nt<T, ConvLoader<T>>(st, la, B, ldb, M, N, K, ep);

@@ -216,7 +216,26 @@ void set_bn_fast(int on);
 void set_bn_chunks(int n);
 void set_adamw_reg(int on);         // realise_set_ln key 6: AdamW + operand-copy tiles with the in-register transpose (1) or through LDS (0, default)
 void set_ce_fast(int on);           // bf16 masked cross-entropy with the logits row held in registers (default 1)
-int bn_fast();
+// What the BatchNorm launches decide on the host (realise_debug_bn_plan): the choices col_sum / col_sumsq_centered / bn_bwd_reduce(2) /
+// bn_stats_train16 / bn_apply / bn_bwd_apply(2) themselves act on, as pure host functions under the knobs as they stand.
+enum BnKernel { BN_GENERIC = 0, BN_16B = 1, BN_ONEPASS = 2, BN_PAIRED = 3 };
+struct BnPass {
+  int kernel = BN_GENERIC;
+  int g = 0;             // reductions: row chunks (workgroups along the rows, one record each); 0: refused / a map
+  int stride = 0;        // floats of a chunk's record (0: no records)
+  int fold_wgs = 0;      // workgroups of the ordered fold behind the records (0: no fold)
+  int overwrite = 0;     // reductions: 1 the outputs are overwritten (records + fold), 0 accumulated (atomics); maps: 1
+  int gx = 1, tpr_shift = 5;      // generic reduction kernel only: workgroups along the columns, log2 threads per row
+};
+struct BnPlan { BnPass stats, apply, bwd_reduce, bwd_apply; };
+// one column reduction: nout folded outputs of C floats each (1, 2; 4 = the paired backward sums); fast: the 16-byte kernel may be taken
+BnPass col_reduce_plan(int elem_bytes, int rows, int C, int hw, bool slots_given, int nout, bool fast);
+BnPass bn_stats_plan(int elem_bytes, int P, int C, int hw, bool slots_given);       // BN_ONEPASS, or the plan of each of the two passes
+BnPass bn_map_plan(int elem_bytes, int P, int C, int hw);                           // bn_apply / bn_bwd_apply: BN_16B or BN_GENERIC
+bool bn_pair_ok(int elem_bytes, int P, int C, int hw, bool slots_given);            // bn2 + shortcut BN backward in one reduction and one map
+constexpr int BN_PAIR_SUMS = 2048;       // floats of the engine's sums scratch: a paired backward needs 4 C of them
+// elem_bytes 2 (bf16) / 4 (fp32); branches 1 / 2 (the backward of bn2 + the shortcut's BN); RL_ERR_ARG: a launch would be refused
+int bn_plan(int elem_bytes, int P, int C, int hw, bool slots_given, int branches, BnPlan& pl);
 // one-pass training statistics of a bf16 [P, C] map + everything bn_finalize_train does (2 launches instead of 5, x read once);
 // RL_ERR_ARG when the fast path does not apply
 int bn_stats_train16(hipStream_t st, const bf16_t* x, int P, int C, int n_stat, const float* gamma, const float* beta, float eps, float momentum,

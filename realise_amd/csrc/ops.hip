@@ -177,7 +177,76 @@ static int g_bn_fast = 1, g_bn_chunks = 1024;       // bf16 16-byte BatchNorm / 
 static int g_bn_onepass = 1;                        // bf16 training statistics in one pass about the running mean (bn_stats_train16)
 void set_bn_fast(int on) { g_bn_fast = on & 1; g_bn_onepass = (on & 1) && !(on & 2); }
 void set_bn_chunks(int n) { if (n >= 1 && n <= 4096) g_bn_chunks = n; }
-int bn_fast() { return g_bn_fast; }
+// ---- the host plan of the BatchNorm launches (ops.h; realise_debug_bn_plan): every kernel choice below is made here and nowhere else ----
+static inline int pow2_shift(int C) { int s = 0; while (s < 31 && (1 << s) < C) ++s; return (1 << s) == C ? s : -1; }
+// the 16-byte kernels apply: bf16, C a power of two in [8, 2048], hw a power of two
+static inline bool bn_fast_shape(int elem_bytes, int C, int hw) {
+  const int cs = pow2_shift(C);
+  return elem_bytes == 2 && g_bn_fast && cs >= 3 && cs <= 11 && pow2_shift(hw) >= 0;
+}
+// row chunks of a 16-byte reduction: the knob, at least four row passes per workgroup, the records inside the scratch
+static inline int reduce16_chunks(int rows, int C, int stride) {
+  const int rpp = 2048 / C;
+  int g = g_bn_chunks;
+  const int max_g = (rows + 4 * rpp - 1) / (4 * rpp);
+  if (g > max_g) g = max_g;
+  if ((int64_t)g * stride > COL_SLOT_FLOATS) g = COL_SLOT_FLOATS / stride;
+  return g < 1 ? 1 : g;
+}
+BnPass col_reduce_plan(int elem_bytes, int rows, int C, int hw, bool slots_given, int nout, bool fast) {
+  BnPass p;
+  if (fast && slots_given && bn_fast_shape(elem_bytes, C, hw)) {       // (the 16-byte kernels write records only: they need the scratch)
+    p.kernel = BN_16B; p.stride = nout * C; p.g = reduce16_chunks(rows, C, p.stride); p.fold_wgs = (p.stride + 31) / 32; p.overwrite = 1;
+    return p;
+  }
+  p.tpr_shift = 5;
+  while (p.tpr_shift > 2 && (1 << p.tpr_shift) * 4 > C) --p.tpr_shift;      // 32 threads x 4 columns unless the row is narrower
+  const int tpr = 1 << p.tpr_shift;
+  p.gx = (C + tpr * 4 - 1) / (tpr * 4);
+  int gy = 1024 / p.gx;
+  if (gy < 1) gy = 1;
+  const int rpp = 256 / tpr;
+  const int max_gy = (rows + 4 * rpp - 1) / (4 * rpp);                      // at least 4 passes per workgroup
+  if (gy > max_gy) gy = max_gy;
+  if (gy < 1) gy = 1;
+  if (slots_given) {           // per-chunk partial records [C | C] + ordered fold: bitwise reproducible (gy * 2C <= COL_SLOT_FLOATS)
+    p.stride = 2 * C;
+    if ((int64_t)gy * p.stride > COL_SLOT_FLOATS) gy = COL_SLOT_FLOATS / p.stride;      // (0: refused)
+    p.fold_wgs = ((nout > 1 ? 2 * C : C) + 31) / 32;
+    p.overwrite = 1;
+  }
+  p.g = gy;
+  return p;
+}
+BnPass bn_stats_plan(int elem_bytes, int P, int C, int hw, bool slots_given) {
+  if (slots_given && g_bn_onepass && P > 0 && bn_fast_shape(elem_bytes, C, hw)) {
+    BnPass p;
+    p.kernel = BN_ONEPASS; p.stride = 2 * C; p.g = reduce16_chunks(P, C, p.stride); p.fold_wgs = (C + 31) / 32; p.overwrite = 1;
+    return p;
+  }
+  return col_reduce_plan(elem_bytes, P, C, hw, slots_given, 1, true);
+}
+BnPass bn_map_plan(int elem_bytes, int P, int C, int hw) {
+  BnPass p;
+  p.overwrite = 1;
+  if (bn_fast_shape(elem_bytes, C, hw) && (((int64_t)P * C) & 7) == 0) p.kernel = BN_16B;
+  return p;
+}
+bool bn_pair_ok(int elem_bytes, int P, int C, int hw, bool slots_given) {
+  return col_reduce_plan(elem_bytes, P, C, hw, slots_given, 4, true).kernel == BN_16B && bn_map_plan(elem_bytes, P, C, hw).kernel == BN_16B &&
+         4 * C <= BN_PAIR_SUMS;
+}
+int bn_plan(int elem_bytes, int P, int C, int hw, bool slots_given, int branches, BnPlan& pl) {
+  pl = BnPlan();
+  if ((elem_bytes != 2 && elem_bytes != 4) || P < 1 || C < 4 || (C & 3) || hw < 1 || branches < 1 || branches > 2) return RL_ERR_ARG;
+  pl.stats = bn_stats_plan(elem_bytes, P, C, hw, slots_given);
+  pl.apply = bn_map_plan(elem_bytes, P, C, hw);
+  const bool pair = branches == 2 && bn_pair_ok(elem_bytes, P, C, hw, slots_given);
+  pl.bwd_reduce = col_reduce_plan(elem_bytes, P, C, hw, slots_given, pair ? 4 : 2, true);
+  pl.bwd_apply = bn_map_plan(elem_bytes, P, C, hw);
+  if (pair) pl.bwd_reduce.kernel = pl.bwd_apply.kernel = BN_PAIRED;
+  return (pl.stats.g < 1 || pl.bwd_reduce.g < 1) ? RL_ERR_ARG : RL_OK;
+}
 void set_ln_fast(int on) { g_ln_fast = on; }
 void set_ln_bwd_blocks(int n) { if (g_ln_v2) g_ln_bwd_blocks_v2 = n > 0 ? n : 256; else g_ln_bwd_blocks = n > 0 ? n : 512; }      // (of the active variant)
 
@@ -1118,30 +1187,18 @@ __global__ void __launch_bounds__(256) col_fold_kernel(float* __restrict__ slots
   }
 }
 template <typename F>
-static int launch_col_reduce(hipStream_t st, const F& f, int rows, int C, float* out0, float* out1, RowBound rb = RowBound(),
+static int launch_col_reduce(hipStream_t st, const F& f, int rows, int C, float* out0, float* out1, const BnPass& pl, RowBound rb = RowBound(),
                              float* slots = nullptr, float alpha = 1.0f) {
   if (rows <= 0 || C <= 0) return RL_OK;
   if (C & 3) return RL_ERR_ARG;
-  int tpr_shift = 5;
-  while (tpr_shift > 2 && (1 << tpr_shift) * 4 > C) --tpr_shift;        // 32 threads x 4 columns unless the row is narrower
-  const int tpr = 1 << tpr_shift;
-  const int gx = (C + tpr * 4 - 1) / (tpr * 4);
-  int gy = 1024 / gx;
-  if (gy < 1) gy = 1;
-  const int rpp = 256 / tpr;
-  const int max_gy = (rows + 4 * rpp - 1) / (4 * rpp);                  // at least 4 passes per workgroup
-  if (gy > max_gy) gy = max_gy;
-  if (gy < 1) gy = 1;
-  if (slots != nullptr) {      // per-chunk partial records + ordered fold: bitwise reproducible (gy * 2C <= COL_SLOT_FLOATS)
-    const int stride = 2 * C;
-    if ((int64_t)gy * stride > COL_SLOT_FLOATS) gy = COL_SLOT_FLOATS / stride;
-    if (gy < 1) return RL_ERR_ARG;
-    hipLaunchKernelGGL((col_reduce_kernel<F>), dim3(gx, gy), dim3(256), 0, st, f, rows, C, tpr_shift, out0, out1, rb, slots, stride);
+  if (pl.g < 1) return RL_ERR_ARG;
+  if (slots != nullptr) {      // per-chunk partial records + ordered fold: bitwise reproducible (col_reduce_plan keeps g * 2C <= COL_SLOT_FLOATS)
+    hipLaunchKernelGGL((col_reduce_kernel<F>), dim3(pl.gx, pl.g), dim3(256), 0, st, f, rows, C, pl.tpr_shift, out0, out1, rb, slots, pl.stride);
     const int n = out1 ? 2 * C : C;
-    hipLaunchKernelGGL(col_fold_kernel, dim3((n + 31) / 32), dim3(256), 0, st, slots, stride, gy, n, out0, out1, C, 1, 0, alpha);     // OVERWRITES out0 / out1
+    hipLaunchKernelGGL(col_fold_kernel, dim3(pl.fold_wgs), dim3(256), 0, st, slots, pl.stride, pl.g, n, out0, out1, C, 1, 0, alpha);     // OVERWRITES out0 / out1
   } else {
     if (alpha != 1.0f) return RL_ERR_ARG;        // the scaled form exists on the record + fold path only
-    hipLaunchKernelGGL((col_reduce_kernel<F>), dim3(gx, gy), dim3(256), 0, st, f, rows, C, tpr_shift, out0, out1, rb, (float*)nullptr, 0);
+    hipLaunchKernelGGL((col_reduce_kernel<F>), dim3(pl.gx, pl.g), dim3(256), 0, st, f, rows, C, pl.tpr_shift, out0, out1, rb, (float*)nullptr, 0);
   }
   return RL_LAUNCH_CHECK();
 }
@@ -1164,7 +1221,7 @@ struct WSum16F {                      // sum_r w_r x[r][c]
   const bf16_t* x; RowW16 w;
   struct Item { uint4 x; };
   struct Ctx {};
-  __device__ __forceinline__ Ctx prep(int) const { return Ctx{}; }
+  __device__ __forceinline__ Ctx prep(int, int) const { return Ctx{}; }
   __device__ __forceinline__ Item load(int64_t e) const { return Item{*(const uint4*)(x + e)}; }
   __device__ __forceinline__ void add(Acc16<1>& a, const Item& it, const Ctx&, int r) const {
     floatx4 lo, hi; unpack8(it.x, lo, hi);
@@ -1177,7 +1234,7 @@ struct SumSqC16F {                    // sum_r w_r (x[r][c] - mean[c])^2
   const bf16_t* x; const float* mean; RowW16 w;
   struct Item { uint4 x; };
   struct Ctx { floatx4 mlo, mhi; };
-  __device__ __forceinline__ Ctx prep(int col) const { return Ctx{*(const floatx4*)(mean + col), *(const floatx4*)(mean + col + 4)}; }
+  __device__ __forceinline__ Ctx prep(int col, int) const { return Ctx{*(const floatx4*)(mean + col), *(const floatx4*)(mean + col + 4)}; }
   __device__ __forceinline__ Item load(int64_t e) const { return Item{*(const uint4*)(x + e)}; }
   __device__ __forceinline__ void add(Acc16<1>& a, const Item& it, const Ctx& c, int r) const {
     floatx4 lo, hi; unpack8(it.x, lo, hi);
@@ -1193,7 +1250,7 @@ template <int NB> struct BnBwd16F {
   const bf16_t* dy; const bf16_t* relu_src; const bf16_t* x[NB]; const float* mean[NB]; const float* rstd[NB];
   struct Item { uint4 g, o, x[NB]; };
   struct Ctx { floatx4 mlo[NB], mhi[NB], rlo[NB], rhi[NB]; };
-  __device__ __forceinline__ Ctx prep(int col) const {
+  __device__ __forceinline__ Ctx prep(int col, int) const {
     Ctx c;
 #pragma unroll
     for (int b = 0; b < NB; ++b) {
@@ -1236,7 +1293,13 @@ struct Moments16F {
   struct Ctx { floatx4 klo, khi; };
   // pivot K = the batch's own first row (a sample of the distribution being measured: |mean - K| is of the order of the standard
   // deviation whatever the running statistics hold - fresh buffers, buffers loaded from another domain)
-  __device__ __forceinline__ Ctx prep(int col) const { Ctx c; unpack8(*(const uint4*)(x + col), c.klo, c.khi); return c; }
+  // (no live row under a device-side bound of 0: row 0 is not read, the pivot is 0 - bn_fold_train_kernel adds the same back)
+  __device__ __forceinline__ Ctx prep(int col, int rows) const {
+    Ctx c;
+    if (rows > 0) unpack8(*(const uint4*)(x + col), c.klo, c.khi);
+    else c.klo = c.khi = floatx4{0.f, 0.f, 0.f, 0.f};
+    return c;
+  }
   __device__ __forceinline__ Item load(int64_t e) const { return Item{*(const uint4*)(x + e)}; }
   __device__ __forceinline__ void add(Acc16<2>& a, const Item& it, const Ctx& c, int r) const {
     floatx4 lo, hi; unpack8(it.x, lo, hi);
@@ -1252,7 +1315,7 @@ struct Moments16F {
 __global__ void __launch_bounds__(256) bn_fold_train_kernel(const float* __restrict__ slots, int slot_stride, int nrec, int C, float inv_n, float unbias,
                                                              const float* __restrict__ gamma, const float* __restrict__ beta, float eps, float momentum,
                                                              float* rmean, float* rvar, float* mean, float* rstd, float* scale, float* shift, int64_t* nbt,
-                                                             const bf16_t* __restrict__ x0) {
+                                                             const bf16_t* __restrict__ x0, const int* __restrict__ rows_dev) {
   __shared__ floatx4 red[2][32][8];
   const int cq = threadIdx.x & 7, kl = threadIdx.x >> 3;
   const int c = (blockIdx.x * 8 + cq) * 4;
@@ -1272,10 +1335,11 @@ __global__ void __launch_bounds__(256) bn_fold_train_kernel(const float* __restr
   }
   if (blockIdx.x == 0 && threadIdx.x == 0 && nbt != nullptr) *nbt += 1;
   if (kl == 0 && c < C) {
+    const bool pivot = rows_dev == nullptr || *rows_dev > 0;
     s1 = red[0][0][cq]; s2 = red[1][0][cq];
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      const float d = s1[j] * inv_n, m = to_f<bf16_t>(x0[c + j]) + d;   // the pivot was the batch's first row (Moments16F::prep)
+      const float d = s1[j] * inv_n, m = (pivot ? to_f<bf16_t>(x0[c + j]) : 0.f) + d;   // the pivot was the batch's first row (Moments16F::prep)
       const float var = fmaxf(s2[j] * inv_n - d * d, 0.f);
       const float rs = 1.0f / sqrtf(var + eps), g = gamma[c + j];
       mean[c + j] = m; rstd[c + j] = rs; scale[c + j] = g * rs; shift[c + j] = beta[c + j] - m * g * rs;
@@ -1296,7 +1360,7 @@ __global__ void __launch_bounds__(256) col_reduce16_kernel(F f, int rows_max, in
   Acc16<F::NACC> acc;
 #pragma unroll
   for (int k = 0; k < F::NACC; ++k) acc.lo[k] = acc.hi[k] = floatx4{0.f, 0.f, 0.f, 0.f};
-  const typename F::Ctx ctx = f.prep(col);
+  const typename F::Ctx ctx = f.prep(col, rows);
   int r = r0 + ry;
   const int64_t step = (int64_t)rpp << c_shift;
   int64_t e = ((int64_t)r << c_shift) + col;
@@ -1324,25 +1388,12 @@ __global__ void __launch_bounds__(256) col_reduce16_kernel(F f, int rows_max, in
     __syncthreads();
   }
 }
-static inline int pow2_shift(int C) { int s = 0; while ((1 << s) < C) ++s; return (1 << s) == C ? s : -1; }
-// fast path applies: bf16, C a power of two in [8, 2048], hw a power of two, ordered-fold scratch present
-static inline bool col16_ok(int C, const RowBound& rb) {
-  const int cs = pow2_shift(C);
-  return g_bn_fast && cs >= 3 && cs <= 11 && pow2_shift(rb.hw) >= 0 && rb.slots != nullptr;
-}
-// nout = folded outputs of C floats each, written contiguously to `out` (overwritten); alpha scales them
+// nout = folded outputs of C floats each, written contiguously to `out` (overwritten); alpha scales them; pl: a BN_16B plan of col_reduce_plan
 template <typename F>
-static int launch_col_reduce16(hipStream_t st, const F& f, int rows, int C, float* out, int nout, int dup0_at, const RowBound& rb, float alpha) {
+static int launch_col_reduce16(hipStream_t st, const F& f, int rows, int C, float* out, int dup0_at, const RowBound& rb, float alpha, const BnPass& pl) {
   if (rows <= 0) return RL_OK;
-  const int cs = pow2_shift(C), rpp = 2048 >> cs;
-  const int stride = nout * C;
-  int g = g_bn_chunks;
-  const int max_g = (rows + 4 * rpp - 1) / (4 * rpp);
-  if (g > max_g) g = max_g;
-  if ((int64_t)g * stride > COL_SLOT_FLOATS) g = COL_SLOT_FLOATS / stride;
-  if (g < 1) g = 1;
-  hipLaunchKernelGGL((col_reduce16_kernel<F>), dim3(g), dim3(256), 0, st, f, rows, cs, rb, rb.slots, stride, dup0_at);
-  hipLaunchKernelGGL(col_fold_kernel, dim3((stride + 31) / 32), dim3(256), 0, st, rb.slots, stride, g, stride, out, out + C, C, 1, 0, alpha);
+  hipLaunchKernelGGL((col_reduce16_kernel<F>), dim3(pl.g), dim3(256), 0, st, f, rows, pow2_shift(C), rb, rb.slots, pl.stride, dup0_at);
+  hipLaunchKernelGGL(col_fold_kernel, dim3(pl.fold_wgs), dim3(256), 0, st, rb.slots, pl.stride, pl.g, pl.stride, out, out + C, C, 1, 0, alpha);
   return RL_LAUNCH_CHECK();
 }
 
@@ -1355,7 +1406,7 @@ template <typename T> int bias_grad(hipStream_t st, const T* dy, int64_t ld, int
   SumF<T> f{dy, ld};
   RowBound rb;
   rb.rows_dev = rows_dev;
-  return launch_col_reduce(st, f, rows, N, out, nullptr, rb);
+  return launch_col_reduce(st, f, rows, N, out, nullptr, col_reduce_plan((int)sizeof(T), rows, N, 1, false, 1, false), rb);
 }
 template int bias_grad<bf16_t>(hipStream_t, const bf16_t*, int64_t, int, int, float*, const int*);
 template int bias_grad<float>(hipStream_t, const float*, int64_t, int, int, float*, const int*);
@@ -1367,11 +1418,12 @@ template <typename T> struct WSumF {
   }
 };
 template <typename T> int col_sum(hipStream_t st, const T* x, int P, int C, float* out, RowBound rb, float scale) {
+  const BnPass pl = col_reduce_plan((int)sizeof(T), P, C, rb.hw, rb.slots != nullptr, 1, true);
   if constexpr (sizeof(T) == 2) {
-    if (col16_ok(C, rb)) { WSum16F f{x, RowW16{rb.counts, pow2_shift(rb.hw)}}; return launch_col_reduce16(st, f, P, C, out, 1, 0, rb, scale); }
+    if (pl.kernel == BN_16B) { WSum16F f{x, RowW16{rb.counts, pow2_shift(rb.hw)}}; return launch_col_reduce16(st, f, P, C, out, 0, rb, scale, pl); }
   }
   WSumF<T> f{x, (int64_t)C, rb};
-  return launch_col_reduce(st, f, P, C, out, nullptr, rb, rb.slots, scale);
+  return launch_col_reduce(st, f, P, C, out, nullptr, pl, rb, rb.slots, scale);
 }
 template int col_sum<bf16_t>(hipStream_t, const bf16_t*, int, int, float*, RowBound, float);
 template int col_sum<float>(hipStream_t, const float*, int, int, float*, RowBound, float);
@@ -1384,11 +1436,12 @@ template <typename T> struct SumSqCF {
   }
 };
 template <typename T> int col_sumsq_centered(hipStream_t st, const T* x, int P, int C, const float* mean, float* out, RowBound rb) {
+  const BnPass pl = col_reduce_plan((int)sizeof(T), P, C, rb.hw, rb.slots != nullptr, 1, true);
   if constexpr (sizeof(T) == 2) {
-    if (col16_ok(C, rb)) { SumSqC16F f{x, mean, RowW16{rb.counts, pow2_shift(rb.hw)}}; return launch_col_reduce16(st, f, P, C, out, 1, 0, rb, 1.0f); }
+    if (pl.kernel == BN_16B) { SumSqC16F f{x, mean, RowW16{rb.counts, pow2_shift(rb.hw)}}; return launch_col_reduce16(st, f, P, C, out, 0, rb, 1.0f, pl); }
   }
   SumSqCF<T> f{x, (int64_t)C, mean, rb};
-  return launch_col_reduce(st, f, P, C, out, nullptr, rb, rb.slots);
+  return launch_col_reduce(st, f, P, C, out, nullptr, pl, rb, rb.slots);
 }
 template int col_sumsq_centered<bf16_t>(hipStream_t, const bf16_t*, int, int, const float*, float*, RowBound);
 template int col_sumsq_centered<float>(hipStream_t, const float*, int, int, const float*, float*, RowBound);
@@ -1410,35 +1463,31 @@ template <typename T> struct BnBwdF {
 template <typename T>
 int bn_bwd_reduce(hipStream_t st, const T* dy, const T* relu_src, const T* x, const float* mean, const float* rstd, int P, int C,
                   float* sums, RowBound rb) {
+  const BnPass pl = col_reduce_plan((int)sizeof(T), P, C, rb.hw, rb.slots != nullptr, 2, true);
   if constexpr (sizeof(T) == 2) {
-    if (col16_ok(C, rb)) { BnBwd16F<1> f{dy, relu_src, {x}, {mean}, {rstd}}; return launch_col_reduce16(st, f, P, C, sums, 2, 0, rb, 1.0f); }
+    if (pl.kernel == BN_16B) { BnBwd16F<1> f{dy, relu_src, {x}, {mean}, {rstd}}; return launch_col_reduce16(st, f, P, C, sums, 0, rb, 1.0f, pl); }
   }
   BnBwdF<T> f{dy, relu_src, x, mean, rstd, (int64_t)C};
-  return launch_col_reduce(st, f, P, C, sums, sums + C, rb, rb.slots);
+  return launch_col_reduce(st, f, P, C, sums, sums + C, pl, rb, rb.slots);
 }
 int bn_stats_train16(hipStream_t st, const bf16_t* x, int P, int C, int n_stat, const float* gamma, const float* beta, float eps, float momentum,
                      float* rmean, float* rvar, float* mean, float* rstd, float* scale, float* shift, int64_t* nbt, RowBound rb) {
-  if (!col16_ok(C, rb) || !g_bn_onepass || P <= 0) return RL_ERR_ARG;
-  const int cs = pow2_shift(C), rpp = 2048 >> cs, stride = 2 * C;
-  int g = g_bn_chunks;
-  const int max_g = (P + 4 * rpp - 1) / (4 * rpp);
-  if (g > max_g) g = max_g;
-  if ((int64_t)g * stride > COL_SLOT_FLOATS) g = COL_SLOT_FLOATS / stride;
-  if (g < 1) g = 1;
+  const BnPass pl = bn_stats_plan(2, P, C, rb.hw, rb.slots != nullptr);
+  if (pl.kernel != BN_ONEPASS) return RL_ERR_ARG;
   Moments16F f{x, RowW16{rb.counts, pow2_shift(rb.hw)}};
-  hipLaunchKernelGGL((col_reduce16_kernel<Moments16F>), dim3(g), dim3(256), 0, st, f, P, cs, rb, rb.slots, stride, 0);
+  hipLaunchKernelGGL((col_reduce16_kernel<Moments16F>), dim3(pl.g), dim3(256), 0, st, f, P, pow2_shift(C), rb, rb.slots, pl.stride, 0);
   const int n = n_stat > 0 ? n_stat : P;
-  hipLaunchKernelGGL(bn_fold_train_kernel, dim3((C + 31) / 32), dim3(256), 0, st, rb.slots, stride, g, C, 1.0f / (float)n,
-                     (float)n / (float)(n > 1 ? n - 1 : 1), gamma, beta, eps, momentum, rmean, rvar, mean, rstd, scale, shift, nbt, x);
+  hipLaunchKernelGGL(bn_fold_train_kernel, dim3(pl.fold_wgs), dim3(256), 0, st, rb.slots, pl.stride, pl.g, C, 1.0f / (float)n,
+                     (float)n / (float)(n > 1 ? n - 1 : 1), gamma, beta, eps, momentum, rmean, rvar, mean, rstd, scale, shift, nbt, x, rb.rows_dev);
   return RL_LAUNCH_CHECK();
 }
 // Two normalisations sharing dy and the ReLU mask: sums = [sum g | sum g xhat_a | sum g | sum g xhat_b] (4C floats).  Returns
 // RL_ERR_ARG when the fast path does not apply (the caller then runs the two single reductions).
 int bn_bwd_reduce2(hipStream_t st, const bf16_t* dy, const bf16_t* relu_src, const bf16_t* xa, const float* mean_a, const float* rstd_a,
                    const bf16_t* xb, const float* mean_b, const float* rstd_b, int P, int C, float* sums, RowBound rb) {
-  if (!col16_ok(C, rb)) return RL_ERR_ARG;
+  if (!bn_pair_ok(2, P, C, rb.hw, rb.slots != nullptr)) return RL_ERR_ARG;
   BnBwd16F<2> f{dy, relu_src, {xa, xb}, {mean_a, mean_b}, {rstd_a, rstd_b}};
-  return launch_col_reduce16(st, f, P, C, sums, 4, 2, rb, 1.0f);
+  return launch_col_reduce16(st, f, P, C, sums, 2, rb, 1.0f, col_reduce_plan(2, P, C, rb.hw, true, 4, true));
 }
 template int bn_bwd_reduce<bf16_t>(hipStream_t, const bf16_t*, const bf16_t*, const bf16_t*, const float*, const float*, int, int, float*, RowBound);
 template int bn_bwd_reduce<float>(hipStream_t, const float*, const float*, const float*, const float*, const float*, int, int, float*, RowBound);

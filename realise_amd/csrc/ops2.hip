@@ -463,15 +463,11 @@ __global__ void __launch_bounds__(256) bn_bwd_apply16_kernel(const bf16_t* __res
   }
 }
 static inline int ew16_blocks(int64_t n8) { int64_t b = (n8 + 255) / 256; b = (b + 3) / 4; return (int)(b > 2048 ? 2048 : (b < 1 ? 1 : b)); }
-static inline bool bn16_ok(int P, int C, const RowBound& rb) {
-  const int cs = pow2_shift2(C);
-  return bn_fast() && cs >= 3 && cs <= 11 && pow2_shift2(rb.hw) >= 0 && (((int64_t)P * C) & 7) == 0;
-}
 // the two-branch backward map (bn2 + shortcut BN of a BasicBlock): RL_ERR_ARG when the fast path does not apply
 int bn_bwd_apply2(hipStream_t st, const bf16_t* dy, const bf16_t* relu_src, const bf16_t* xa, const float* mean_a, const float* rstd_a,
                   const float* gamma_a, bf16_t* dxa, float* dgamma_a, float* dbeta_a, const bf16_t* xb, const float* mean_b, const float* rstd_b,
                   const float* gamma_b, bf16_t* dxb, float* dgamma_b, float* dbeta_b, const float* sums4, int P, int C, RowBound rb, int n_stat) {
-  if (!bn16_ok(P, C, rb)) return RL_ERR_ARG;
+  if (!bn_pair_ok(2, P, C, rb.hw, true)) return RL_ERR_ARG;
   const BnBwdBranch b0{xa, mean_a, rstd_a, gamma_a, sums4, dxa, dgamma_a, dbeta_a}, b1{xb, mean_b, rstd_b, gamma_b, sums4 + 2 * C, dxb, dgamma_b, dbeta_b};
   const int64_t n8 = (int64_t)P * C / 8;
   hipLaunchKernelGGL((bn_bwd_apply16_kernel<2>), dim3(ew16_blocks(n8)), dim3(256), 0, st, dy, relu_src, b0, b1, P, pow2_shift2(C), pow2_shift2(rb.hw),
@@ -486,7 +482,7 @@ int bn_apply(hipStream_t st, const T* x1, const float* sc1, const float* sh1, co
   if (C & 3) return RL_ERR_ARG;
   const int64_t n = (int64_t)P * C;
   if constexpr (sizeof(T) == 2) {
-    if (bn16_ok(P, C, rb)) {
+    if (bn_map_plan(2, P, C, rb.hw).kernel == BN_16B) {
       if (x2 != nullptr) hipLaunchKernelGGL((bn_apply16_kernel<2>), dim3(ew16_blocks(n / 8)), dim3(256), 0, st, x1, sc1, sh1, x2, sc2, sh2, y, P, pow2_shift2(C), relu, rb);
       else hipLaunchKernelGGL((bn_apply16_kernel<1>), dim3(ew16_blocks(n / 8)), dim3(256), 0, st, x1, sc1, sh1, x2, sc2, sh2, y, P, pow2_shift2(C), relu, rb);
       return RL_LAUNCH_CHECK();
@@ -531,7 +527,7 @@ int bn_bwd_apply(hipStream_t st, const T* dy, const T* relu_src, const T* x, con
   if (C & 3) return RL_ERR_ARG;
   const int64_t n = (int64_t)P * C;
   if constexpr (sizeof(T) == 2) {
-    if (bn16_ok(P, C, rb)) {
+    if (bn_map_plan(2, P, C, rb.hw).kernel == BN_16B) {
       const BnBwdBranch b0{x, mean, rstd, gamma, sums, dx, dgamma, dbeta};
       hipLaunchKernelGGL((bn_bwd_apply16_kernel<1>), dim3(ew16_blocks(n / 8)), dim3(256), 0, st, dy, relu_src, b0, b0, P, pow2_shift2(C), pow2_shift2(rb.hw),
                          1.0f / (float)(n_stat > 0 ? n_stat : P), rb);

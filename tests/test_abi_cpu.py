@@ -53,6 +53,28 @@ def test_debug_tn_plan_answers_without_a_gpu():
     assert lib.realise_debug_tn_plan(7, 0, 64, 64, 64, 0, 0, 0, C.byref(pl)) != 0                    # no such dtype
 
 
+def test_debug_bn_plan_and_conv_nt_path_answer_without_a_gpu():
+    """realise_debug_bn_plan and realise_debug_conv_nt_path (include/realise_hip_debug.h) are pure host functions: the host choices of the
+    BatchNorm launchers and of gemm_nt_conv; their invariants and the shapes are pinned in tests/test_tower_cases_cpu.py"""
+    lib = _capi.load()
+    pl = _capi.BnPlan()
+    assert lib.realise_debug_bn_plan(_capi.BF16, 8192 * 256, 64, 256, 1, 2, C.byref(pl)) == 0
+    assert (pl.stats.kernel, pl.apply.kernel, pl.bwd_reduce.kernel, pl.bwd_apply.kernel) == (2, 1, 3, 3)        # one-pass, 16-byte, paired
+    assert (pl.stats.g, pl.stats.stride, pl.stats.overwrite, pl.bwd_reduce.stride) == (1024, 128, 1, 256)
+    assert lib.realise_debug_bn_plan(_capi.BF16, 8192, 768, 1, 1, 2, C.byref(pl)) == 0
+    assert (pl.stats.kernel, pl.apply.kernel, pl.bwd_reduce.kernel, pl.bwd_apply.kernel) == (0, 0, 0, 0)        # C = 768: generic
+    assert lib.realise_debug_bn_plan(_capi.F32, 448, 64, 64, 0, 1, C.byref(pl)) == 0 and pl.stats.overwrite == 0 and pl.stats.stride == 0
+    assert lib.realise_debug_bn_plan(_capi.BF16, 448, 66, 64, 1, 1, C.byref(pl)) != 0                           # C % 4
+    assert lib.realise_debug_bn_plan(7, 448, 64, 64, 1, 1, C.byref(pl)) != 0                                    # no such dtype
+    g = _capi.ConvGeom()
+    g.src = 64
+    g.rows, g.Hr, g.Wr, g.Hs, g.Ws, g.C, g.KH, g.KW, g.stride, g.pad, g.mode = 768, 16, 16, 16, 16, 64, 3, 3, 1, 1, 0
+    assert lib.realise_debug_conv_nt_path(_capi.BF16, C.byref(g), 576, 768, 64, 576, 0, 0, 0, 0, 64, 64) == 12  # conv_c64_nt
+    assert lib.realise_debug_conv_nt_path(_capi.F32, C.byref(g), 576, 768, 64, 576, 0, 0, 0, 0, 64, 64) == 1
+    assert lib.realise_debug_conv_nt_path(_capi.BF16, C.byref(g), 576, 768, 64, 512, 0, 0, 0, 0, 64, 64) == -1  # K is not KH KW C
+    assert lib.realise_debug_conv_nt_path(_capi.BF16, None, 576, 768, 64, 576, 0, 0, 0, 0, 64, 64) == -1
+
+
 @pytest.mark.parametrize("model_type,count", [("arch3", 427), ("bert", 201)])
 def test_layout_matches_reference_state_dict(model_type, count):
     cfg = RealiseConfig()
