@@ -93,13 +93,14 @@ int realise_layernorm_bwd_live(void* stream, const void* dy, const void* xhat, c
  * backward with four rows of a wave in flight, no barrier before the first row, one-barrier epilogue, 256 workgroups; 0: the round-4
  * kernels) - key 1 sets the workgroups of whichever backward is active */
 void realise_set_ln(int key, int value);
-/* BatchNorm training statistics and backward exactly as the engine's glyph branch runs them (bf16, NHWC viewed as [P, C];
- * char_cnn.py:15-32): per-row-chunk partial records in `slots` (1 MiB scratch) folded in a fixed order; `counts` (nullable) =
+/* BatchNorm training statistics and backward through the two host functions the engine's glyph branch calls (bn_stats / bn_backward
+ * of csrc/ops.h; bf16, NHWC viewed as [P, C]; char_cnn.py:15-32): per-row-chunk partial records in `slots` (1 MiB scratch) folded in a fixed order; `counts` (nullable) =
  * multiplicity of each image of `hw` pixels (glyph dedup), n_stat = the true sample count of the statistics (0: P).
  * stats: mean / rstd / scale / shift [C], running buffers updated (unbiased variance), num_batches_tracked += 1; sq_scratch: C floats.
  * bwd: dx = gamma rstd (g - w sum(g) / n - xhat w sum(g xhat) / n) with g = dy masked by relu_src > 0; dgamma / dbeta are ADDED to;
  * xb != NULL: a second normalisation sharing dy and the mask (bn2 + shortcut BN of a BasicBlock; one pass reads dy and the mask for
- * both - taken while 4 C fits the engine's 2048-float sums scratch, realise_debug_bn_plan says which -); sums: 4C floats of scratch.
+ * both - taken while 4 C fits the engine's 2048-float sums scratch, realise_debug_bn_plan says which; otherwise a's reduction and map
+ * run first, then b's -); sums: 4C floats of scratch.
  * tools/bn_probe.py times them; tests/test_ops_gpu.py checks fast against generic paths; the bounded forms below are pinned element by
  * element. */
 int realise_batchnorm_stats_ex(void* stream, const void* x, int P, int C, int hw, const float* counts, int n_stat, const float* gamma, const float* beta,
@@ -226,12 +227,13 @@ int realise_conv_nt_ex(void* stream, int dtype, const realise_conv_geom* a, cons
                        const realise_epilogue* ep, const float* col_scale, int relu, const int* rows_dev, int64_t index_rows);
 int realise_gemm_nt_ex(void* stream, int dtype, const void* A, int64_t lda, const void* B, int64_t ldb, int M, int N, int K,
                        const realise_epilogue* ep, const float* col_scale, int relu, const int* rows_dev);
-/* realise_conv_dgrad_s2 under a device-side bound, as the engine launches the stride-2 data gradients: *rows_dev (nullable) counts INPUT
- * pixel rows (whole images); each parity-class launch takes a quarter of it.  Input rows at or behind the bound keep their bits in
+/* realise_conv_dgrad_s2 under a device-side bound: conv_dgrad_s2 of csrc/gemm.h, the host function the engine's stride-2 data gradients
+ * go through (class loop, tap-less classes, the one-tap 2x2 case).  *rows_dev (nullable) counts INPUT pixel rows (whole images); each parity-class launch takes a quarter of it.  Input rows at or behind the bound keep their bits in
  * every class (tests/test_tower_edges_gpu.py: bounds 0, one image, all, with NaN in the gradient rows of the images behind it). */
 int realise_conv_dgrad_s2_ex(void* stream, int dtype, const realise_conv_geom* a, const void* B_classes, int64_t ldb, int Cin,
                              const realise_epilogue* ep, const int* rows_dev);
-/* The BatchNorm passes as the engine's glyph branch launches them, for fp32 and bf16: every kernel bounded by *rows_dev (device,
+/* The BatchNorm passes of the engine's glyph branch, for fp32 and bf16: stats_rows and bwd_rows are bn_stats / bn_backward of
+ * csrc/ops.h, the host functions the engine itself calls, apply_rows is bn_apply.  Every kernel is bounded by *rows_dev (device,
  * nullable; glyph dedup: distinct glyphs x hw - rows at or behind it are neither read nor written and do not enter a sum), `counts`
  * (nullable) the multiplicity of each image of hw pixels, n_stat the true sample count (0: P), `slots` the record scratch
  * (COL_SLOT_FLOATS = 262144 floats; NULL: the reductions use fp32 atomics on zero-filled scratch, as realise_batchnorm_fwd / _bwd do).

@@ -990,21 +990,14 @@ template <typename T> struct Engine : EngineBase {
   // Pn = B*S*Hout^2 is the TRUE sample count of the statistics (every token counts, PADs included, as in the
   // reference); the kernels visit only the distinct glyphs and weight them by their multiplicity.
   int bn_forward(hipStream_t st, const T* x, int Pn, int C, const BnOff& o, const BnAct& a, const RowBound& rb) {
-    if (last.training) {
-      float* sums = wp<float>(pl.bn_sums);
-      if constexpr (sizeof(T) == 2) {
-        if (bn_stats_train16(st, x, Pn, C, Pn, pp(o.g), pp(o.b), 1e-5f, 0.1f, BF + o.rmean, BF + o.rvar, wp<float>(a.mean), wp<float>(a.rstd),
-                             wp<float>(a.scale), wp<float>(a.shift), BI + o.nbt, rb) == RL_OK)
-          return RL_OK;
-      }
-      RL_TRY(col_sum<T>(st, x, Pn, C, wp<float>(a.mean), rb, 1.0f / (float)Pn));          // the fold writes the mean directly
-      RL_TRY(col_sumsq_centered<T>(st, x, Pn, C, wp<float>(a.mean), sums + C, rb));
-      RL_TRY(bn_finalize_train(st, wp<float>(a.mean), sums + C, C, Pn, pp(o.g), pp(o.b), 1e-5f, 0.1f, BF + o.rmean, BF + o.rvar,
-                               wp<float>(a.rstd), wp<float>(a.scale), wp<float>(a.shift), BI + o.nbt));
-    } else {
-      RL_TRY(bn_finalize_eval(st, C, pp(o.g), pp(o.b), 1e-5f, BF + o.rmean, BF + o.rvar, wp<float>(a.scale), wp<float>(a.shift)));
-    }
-    return RL_OK;
+    return bn_stats<T>(st, x, Pn, C, Pn, last.training, pp(o.g), pp(o.b), 1e-5f, 0.1f, BF + o.rmean, BF + o.rvar, BI + o.nbt, wp<float>(a.mean),
+                       wp<float>(a.rstd), wp<float>(a.scale), wp<float>(a.shift), wp<float>(pl.bn_sums), rb);
+  }
+  // one normalisation of a block's backward (ops.h bn_backward): its saved input and statistics, where d(input) goes, its parameter gradients
+  BnBranch<T> bn_branch(int64_t x, const BnOff& o, const BnAct& a, T* dx) {
+    BnBranch<T> b;
+    b.x = wp<T>(x); b.mean = wp<float>(a.mean); b.rstd = wp<float>(a.rstd); b.gamma = pp(o.g); b.dx = dx; b.dgamma = gp(o.g); b.dbeta = gp(o.b);
+    return b;
   }
   bool glyph_gathered = false;             // gu_dense holds the distinct glyph images of the last resnet_forward
   int gather_glyphs(hipStream_t st) {
@@ -1107,25 +1100,7 @@ template <typename T> struct Engine : EngineBase {
       // out = relu(bn2(c2) + bns(cs))
       // bn2 and the shortcut's BN see the same incoming gradient and ReLU mask: bf16 reads them once for both (two passes over four
       // tensors instead of four passes over three)
-      bool paired = false;
-      if constexpr (sizeof(T) == 2) {
-        // (paired while bn_pair_ok says so: the 16-byte kernels apply and 4 Co floats fit the sums scratch)
-        if (bn_bwd_reduce2(st, d_out, wp<T>(a.out), wp<T>(a.c2), wp<float>(a.bn2.mean), wp<float>(a.bn2.rstd), wp<T>(a.cs), wp<float>(a.bns.mean),
-                           wp<float>(a.bns.rstd), Pn, Co, sums, rb) == RL_OK) {
-          RL_TRY(bn_bwd_apply2(st, d_out, wp<T>(a.out), wp<T>(a.c2), wp<float>(a.bn2.mean), wp<float>(a.bn2.rstd), pp(o.bn2.g), dc2, gp(o.bn2.g),
-                               gp(o.bn2.b), wp<T>(a.cs), wp<float>(a.bns.mean), wp<float>(a.bns.rstd), pp(o.bns.g), dcs, gp(o.bns.g), gp(o.bns.b),
-                               sums, Pn, Co, rb, Pn));
-          paired = true;
-        }
-      }
-      if (!paired) {
-        RL_TRY(bn_bwd_reduce<T>(st, d_out, wp<T>(a.out), wp<T>(a.c2), wp<float>(a.bn2.mean), wp<float>(a.bn2.rstd), Pn, Co, sums, rb));
-        RL_TRY(bn_bwd_apply<T>(st, d_out, wp<T>(a.out), wp<T>(a.c2), wp<float>(a.bn2.mean), wp<float>(a.bn2.rstd), pp(o.bn2.g), sums,
-                               Pn, Co, dc2, gp(o.bn2.g), gp(o.bn2.b), rb, Pn));
-        RL_TRY(bn_bwd_reduce<T>(st, d_out, wp<T>(a.out), wp<T>(a.cs), wp<float>(a.bns.mean), wp<float>(a.bns.rstd), Pn, Co, sums, rb));
-        RL_TRY(bn_bwd_apply<T>(st, d_out, wp<T>(a.out), wp<T>(a.cs), wp<float>(a.bns.mean), wp<float>(a.bns.rstd), pp(o.bns.g), sums,
-                               Pn, Co, dcs, gp(o.bns.g), gp(o.bns.b), rb, Pn));
-      }
+      RL_TRY(bn_backward<T>(st, d_out, wp<T>(a.out), Pn, Co, Pn, bn_branch(a.c2, o.bn2, a.bn2, dc2), bn_branch(a.cs, o.bns, a.bns, dcs), sums, rb));
       // conv2 (3x3 s1): weight grad and data grad
       { TnEpi te; te.slab = wp<float>(la.sc->tn_slab); te.slab_elems = TN_SLAB_ELEMS; te.mode = TN_CONVW; te.out = gp(o.w2); te.Cin = Co; te.Cpad = Co; te.KHW = 9;
         if (a.Hout == 1) { te.tap0 = 4; RL_TRY(gemm_tn<T>(st, dc2, Co, wp<T>(a.h1), Co, Pn, Co, Co, te, rb.rows_dev)); }       // centre tap only
@@ -1134,9 +1109,7 @@ template <typename T> struct Engine : EngineBase {
         if (a.Hout == 1) RL_TRY(gemm_nt<T>(st, dc2, Co, sp<T>(s.w2d) + 4 * Co, 9 * Co, Pn, Co, Co, ep, rb.rows_dev));          // centre tap only
         else RL_TRY(gemm_nt_conv<T>(st, geom(dc2, nullptr, Pn, a.Hout, a.Hout, Co, 3, 1, 1, 1, rb.rows_dev), sp<T>(s.w2d), 9 * Co, Pn, Co, 9 * Co, ep)); }
       // h1 = relu(bn1(c1))
-      RL_TRY(bn_bwd_reduce<T>(st, dh1, wp<T>(a.h1), wp<T>(a.c1), wp<float>(a.bn1.mean), wp<float>(a.bn1.rstd), Pn, Co, sums, rb));
-      RL_TRY(bn_bwd_apply<T>(st, dh1, wp<T>(a.h1), wp<T>(a.c1), wp<float>(a.bn1.mean), wp<float>(a.bn1.rstd), pp(o.bn1.g), sums,
-                             Pn, Co, dc1, gp(o.bn1.g), gp(o.bn1.b), rb, Pn));
+      RL_TRY(bn_backward<T>(st, dh1, wp<T>(a.h1), Pn, Co, Pn, bn_branch(a.c1, o.bn1, a.bn1, dc1), BnBranch<T>(), sums, rb));
       // conv1 (3x3 s2) and shortcut (1x1 s2) weight grads
       { TnEpi te; te.slab = wp<float>(la.sc->tn_slab); te.slab_elems = TN_SLAB_ELEMS; te.mode = TN_CONVW; te.out = gp(o.w1); te.Cin = o.cin; te.Cpad = Cin; te.KHW = 9;
         RL_TRY(gemm_tn_conv<T>(st, dc1, Co, geom(x_in, index, Pn, a.Hout, a.Hin, Cin, 3, 2, 1, 0, rb.rows_dev), Pn, Co, 9 * Cin, te)); }
@@ -1147,25 +1120,12 @@ template <typename T> struct Engine : EngineBase {
         const int* in_bound = rbound(k - 1).rows_dev;
         T* dx = (d_out == wp<T>(pl.r_dx)) ? wp<T>(pl.r_dout) : wp<T>(pl.r_dx);
         EpiParams<T> ep; ep.mode = EPI_STORE; ep.out = dx; ep.ldo = Cin;
-        int hsh = 0; while ((1 << hsh) < a.Hin) ++hsh;
-        if (g_dgrad_parity && (1 << hsh) == a.Hin && hsh >= 1) {
+        if (g_dgrad_parity && a.Hin >= 2 && (a.Hin & (a.Hin - 1)) == 0) {
           // by parity class of the input pixel: only the taps that reach it, a quarter of the rows per launch; the 1x1 stride-2
           // shortcut reaches the (even, even) pixels only
-          ep.rm_hw_shift = 2 * hsh; ep.rm_w_shift = hsh;
-          for (int c = 0; c < 4; ++c) {
-            int first = 0;
-            int nt = conv_s2_class(3, 3, 1, c, &first, nullptr);
-            ConvLoader<T> g = geom(dc1, nullptr, Pin / 4, a.Hin, a.Hout, Co, 3, 2, 1, 1, in_bound);
-            g.par = c; ep.rm_par = c; ep.accumulate = 0;
-            if (a.Hout == 1) {      // 2x2 map under a 1x1 output: pixel (py, px) is reached by tap (py + 1, px + 1) alone
-              g.tap_sel = ((c >> 1) + 1) * 3 + (c & 1) + 1;
-              first = conv_s2_slot(3, 3, 1, (c >> 1) + 1, (c & 1) + 1); nt = 1;
-            }
-            RL_TRY(gemm_nt_conv<T>(st, g, sp<T>(s.w1p) + (int64_t)first * Co, 9 * Co, Pin / 4, Cin, nt * Co, ep));
-          }
-          ConvLoader<T> g = geom(dcs, nullptr, Pin / 4, a.Hin, a.Hout, Co, 1, 2, 0, 1, in_bound);
-          g.par = 0; ep.rm_par = 0; ep.accumulate = 1;
-          RL_TRY(gemm_nt_conv<T>(st, g, sp<T>(s.wsd), Co, Pin / 4, Cin, Co, ep));
+          RL_TRY(conv_dgrad_s2<T>(st, geom(dc1, nullptr, Pin, a.Hin, a.Hout, Co, 3, 2, 1, 1, in_bound), sp<T>(s.w1p), 9 * Co, Cin, ep));
+          ep.accumulate = 1;
+          RL_TRY(conv_dgrad_s2<T>(st, geom(dcs, nullptr, Pin, a.Hin, a.Hout, Co, 1, 2, 0, 1, in_bound), sp<T>(s.wsd), Co, Cin, ep));
         } else {
           RL_TRY(gemm_nt_conv<T>(st, geom(dc1, nullptr, Pin, a.Hin, a.Hout, Co, 3, 2, 1, 1, in_bound), sp<T>(s.w1d), 9 * Co, Pin, Cin, 9 * Co, ep));
           ep.accumulate = 1;

@@ -406,6 +406,13 @@ int gemm_nt(hipStream_t st, const T* A, int64_t lda, const T* B, int64_t ldb, in
 template <typename T>
 int gemm_nt_conv(hipStream_t st, const ConvLoader<T>& la, const T* B, int64_t ldb, int M, int N, int K,
                  const EpiParams<T>& ep);
+// Stride-2 data gradient by input-pixel parity classes (ConvLoader::par): `full` is the mode-1 geometry over ALL input pixels (Hr = Wr
+// a power of two >= 2, no img_index; rows_dev counts input-pixel rows), B the class-ordered weight copy (conv_s2_class()), ep.out the
+// [rows, Cin] input gradient.  One gemm_nt_conv per class over a quarter of the rows, K = the class's taps; a class no tap reaches
+// (1x1: all but class 0) is skipped when accumulating and refused otherwise; a 2x2 map under a 1x1 output of a 3x3 / pad 1 convolution
+// has one reachable tap per pixel (ConvLoader::tap_sel).  The engine and realise_conv_dgrad_s2(_ex) call this.
+template <typename T>
+int conv_dgrad_s2(hipStream_t st, const ConvLoader<T>& full, const T* B_classes, int64_t ldb, int Cin, const EpiParams<T>& ep);
 // C[I,J] += sum_p A[p,i] * B[p,j]   (A: [P, >=I] row-major; B dense or gathered)
 template <typename T>
 int gemm_tn(hipStream_t st, const T* A, int64_t lda, const T* B, int64_t ldb, int P, int I, int J, const TnEpi& ep,

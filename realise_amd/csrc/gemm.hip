@@ -441,6 +441,32 @@ template int gemm_nt<bf16_t>(hipStream_t, const bf16_t*, int64_t, const bf16_t*,
 template int gemm_nt<float>(hipStream_t, const float*, int64_t, const float*, int64_t, int, int, int, const EpiParams<float>&, const int*);
 template int gemm_nt_conv<bf16_t>(hipStream_t, const ConvLoader<bf16_t>&, const bf16_t*, int64_t, int, int, int, const EpiParams<bf16_t>&);
 template int gemm_nt_conv<float>(hipStream_t, const ConvLoader<float>&, const float*, int64_t, int, int, int, const EpiParams<float>&);
+template <typename T>
+int conv_dgrad_s2(hipStream_t st, const ConvLoader<T>& full, const T* B, int64_t ldb, int Cin, const EpiParams<T>& ep) {
+  if (full.mode != 1 || full.stride != 2 || full.Hr != full.Wr || (full.Hr & (full.Hr - 1)) || full.Hr < 2 || full.img_index != nullptr) return RL_ERR_ARG;
+  int hsh = 0; while ((1 << hsh) < full.Hr) ++hsh;
+  // one reachable tap per pixel of a 2x2 map under a 1x1 output: pixel (py, px) is reached by tap (py + 1, px + 1) alone
+  const bool one_tap = full.Hr == 2 && full.Hs == 1 && full.KH == 3 && full.KW == 3 && full.pad == 1;
+  ConvLoader<T> g = full;
+  g.rows = full.rows / (full.Hr * full.Wr) * (full.Hr / 2) * (full.Wr / 2);      // (rows_dev stays in input-pixel rows: ConvLoader::clamp_rows)
+  EpiParams<T> e = ep;
+  e.rm_hw_shift = 2 * hsh; e.rm_w_shift = hsh;
+  for (int c = 0; c < 4; ++c) {
+    int first = 0;
+    int nt = conv_s2_class(full.KH, full.KW, full.pad, c, &first, nullptr);
+    if (nt == 0) { if (!ep.accumulate) return RL_ERR_ARG; continue; }      // pixels no tap reaches: only meaningful when accumulating
+    g.par = c; e.rm_par = c;
+    if (one_tap) {
+      g.tap_sel = ((c >> 1) + 1) * 3 + (c & 1) + 1;
+      first = conv_s2_slot(3, 3, 1, (c >> 1) + 1, (c & 1) + 1); nt = 1;
+    }
+    const int rc = gemm_nt_conv<T>(st, g, B + (int64_t)first * full.C, ldb, g.rows, Cin, nt * full.C, e);
+    if (rc != RL_OK) return rc;
+  }
+  return RL_OK;
+}
+template int conv_dgrad_s2<bf16_t>(hipStream_t, const ConvLoader<bf16_t>&, const bf16_t*, int64_t, int, const EpiParams<bf16_t>&);
+template int conv_dgrad_s2<float>(hipStream_t, const ConvLoader<float>&, const float*, int64_t, int, const EpiParams<float>&);
 
 // =================================================================================================
 // TN: C[I,J] += sum_p A[p,i] * B[p,j].  Operand tiles are staged in their natural layout

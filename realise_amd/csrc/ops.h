@@ -267,6 +267,25 @@ template <typename T>
 int bn_bwd_apply(hipStream_t st, const T* dy, const T* relu_src, const T* x, const float* mean, const float* rstd,
                  const float* gamma, const float* sums, int P, int C, T* dx, float* dgamma, float* dbeta,
                  RowBound rb = RowBound(), int n_stat = 0);
+// The two launch sequences over the passes above.  The engine's glyph tower and every BatchNorm entry point of the C surface call
+// these, so what the element-wise tests pin is what a training step runs.
+// bn_stats: (scale, shift) of one normalisation for bn_apply.  Evaluation: from the running buffers, nothing else is touched.
+// Training: mean / rstd from the batch and the running-buffer update - bf16 in one pass where bn_stats_train16 takes it, else two
+// reductions: with rb.slots the first one's fold writes the mean, without it both use atomics on the zero-filled scratch.
+// n_stat: the true sample count (0: P); scratch: 2 C floats (with rb.slots only scratch[C, 2C) is touched).
+template <typename T>
+int bn_stats(hipStream_t st, const T* x, int P, int C, int n_stat, int training, const float* gamma, const float* beta, float eps, float momentum,
+             float* rmean, float* rvar, int64_t* nbt, float* mean, float* rstd, float* scale, float* shift, float* scratch, RowBound rb = RowBound());
+// bn_backward: the normalisations behind one incoming gradient dy and ReLU mask relu_src: a alone (b.x == nullptr), or a BasicBlock's
+// bn2 (a) + shortcut BN (b) - in one reduction and one map where bn_bwd_reduce2 takes them, else reduce + apply for a, then for b
+// (without rb.slots each after a zero fill of sums[0, 2C)).  sums: 4 C floats.
+template <typename T> struct BnBranch {
+  const T* x = nullptr; const float* mean = nullptr; const float* rstd = nullptr; const float* gamma = nullptr;
+  T* dx = nullptr; float* dgamma = nullptr; float* dbeta = nullptr;
+};
+template <typename T>
+int bn_backward(hipStream_t st, const T* dy, const T* relu_src, int P, int C, int n_stat, const BnBranch<T>& a, const BnBranch<T>& b, float* sums,
+                RowBound rb = RowBound());
 // g = dy * (relu_src > 0)
 template <typename T> int relu_bwd(hipStream_t st, const T* dy, const T* relu_src, T* g, int64_t n);
 

@@ -8,6 +8,7 @@ namespace rl {
 __global__ void col_fold_kernel(float* __restrict__ slots, int slot_stride, int nrec, int n, float* out0, float* out1, int C, int overwrite, int clean, float alpha);
 
 #define RL_LAUNCH_CHECK() (hipGetLastError() == hipSuccess ? RL_OK : RL_ERR_LAUNCH)
+#define RL_TRY(expr) do { const int _rc = (expr); if (_rc != RL_OK) return _rc; } while (0)
 static constexpr int LN_MAXV = 4;   // up to 4 x (64 lanes x 4 elems) = 1024 columns per row
 
 __global__ void mask_to_additive_kernel(const int64_t* __restrict__ m, float* __restrict__ out, int n) {
@@ -1491,6 +1492,49 @@ int bn_bwd_reduce2(hipStream_t st, const bf16_t* dy, const bf16_t* relu_src, con
 }
 template int bn_bwd_reduce<bf16_t>(hipStream_t, const bf16_t*, const bf16_t*, const bf16_t*, const float*, const float*, int, int, float*, RowBound);
 template int bn_bwd_reduce<float>(hipStream_t, const float*, const float*, const float*, const float*, const float*, int, int, float*, RowBound);
+
+// ---- the two BatchNorm launch sequences (ops.h): what the plan above decides, issued here and nowhere else ----
+template <typename T>
+int bn_stats(hipStream_t st, const T* x, int P, int C, int n_stat, int training, const float* gamma, const float* beta, float eps, float momentum,
+             float* rmean, float* rvar, int64_t* nbt, float* mean, float* rstd, float* scale, float* shift, float* scratch, RowBound rb) {
+  if (!training) return bn_finalize_eval(st, C, gamma, beta, eps, rmean, rvar, scale, shift);
+  const int n = n_stat > 0 ? n_stat : P;
+  if constexpr (sizeof(T) == 2) {
+    if (bn_stats_train16(st, x, P, C, n, gamma, beta, eps, momentum, rmean, rvar, mean, rstd, scale, shift, nbt, rb) == RL_OK) return RL_OK;
+  }
+  if (rb.slots != nullptr) {
+    RL_TRY(col_sum<T>(st, x, P, C, mean, rb, 1.0f / (float)n));          // the fold writes the mean directly
+  } else {
+    RL_TRY(fill_f32(st, scratch, 0.0f, 2 * C));
+    RL_TRY(col_sum<T>(st, x, P, C, scratch, rb));
+    RL_TRY(bn_finalize_mean(st, scratch, C, n, mean));
+  }
+  RL_TRY(col_sumsq_centered<T>(st, x, P, C, mean, scratch + C, rb));
+  return bn_finalize_train(st, mean, scratch + C, C, n, gamma, beta, eps, momentum, rmean, rvar, rstd, scale, shift, nbt);
+}
+template int bn_stats<bf16_t>(hipStream_t, const bf16_t*, int, int, int, int, const float*, const float*, float, float, float*, float*, int64_t*, float*,
+                              float*, float*, float*, float*, RowBound);
+template int bn_stats<float>(hipStream_t, const float*, int, int, int, int, const float*, const float*, float, float, float*, float*, int64_t*, float*,
+                             float*, float*, float*, float*, RowBound);
+template <typename T>
+int bn_backward(hipStream_t st, const T* dy, const T* relu_src, int P, int C, int n_stat, const BnBranch<T>& a, const BnBranch<T>& b, float* sums,
+                RowBound rb) {
+  if constexpr (sizeof(T) == 2) {
+    // (paired while bn_pair_ok says so: the 16-byte kernels apply and 4 C floats fit the sums scratch)
+    if (b.x != nullptr && bn_bwd_reduce2(st, dy, relu_src, a.x, a.mean, a.rstd, b.x, b.mean, b.rstd, P, C, sums, rb) == RL_OK)
+      return bn_bwd_apply2(st, dy, relu_src, a.x, a.mean, a.rstd, a.gamma, a.dx, a.dgamma, a.dbeta, b.x, b.mean, b.rstd, b.gamma, b.dx, b.dgamma,
+                           b.dbeta, sums, P, C, rb, n_stat);
+  }
+  for (const BnBranch<T>* br : {&a, &b}) {
+    if (br->x == nullptr) continue;
+    if (rb.slots == nullptr) RL_TRY(fill_f32(st, sums, 0.0f, 2 * C));      // (atomics; with records the reduction overwrites)
+    RL_TRY(bn_bwd_reduce<T>(st, dy, relu_src, br->x, br->mean, br->rstd, P, C, sums, rb));
+    RL_TRY(bn_bwd_apply<T>(st, dy, relu_src, br->x, br->mean, br->rstd, br->gamma, sums, P, C, br->dx, br->dgamma, br->dbeta, rb, n_stat));
+  }
+  return RL_OK;
+}
+template int bn_backward<bf16_t>(hipStream_t, const bf16_t*, const bf16_t*, int, int, int, const BnBranch<bf16_t>&, const BnBranch<bf16_t>&, float*, RowBound);
+template int bn_backward<float>(hipStream_t, const float*, const float*, int, int, int, const BnBranch<float>&, const BnBranch<float>&, float*, RowBound);
 
 // ---------------------------------------------------------------------------------------------
 // Dropout as a stand-alone map (the one before the classifier, models.py:858)

@@ -1,4 +1,6 @@
-"""The glyph tower's BatchNorm family as the engine launches it, element by element against the float64 references of tests/tower_cases.py.
+"""The glyph tower's BatchNorm family and convolutions, element by element against the float64 references of tests/tower_cases.py, through
+the host functions the engine itself calls: bn_stats / bn_backward (realise_batchnorm_stats_rows / _bwd_rows), bn_apply, conv_dgrad_s2
+(realise_conv_dgrad_s2_ex) and gemm_nt_conv / gemm_nt - a slip in a launch sequence fails here, not only in the whole-model goldens.
 
 Conventions of every case: the kernels a launch is meant for are asserted first through realise_debug_bn_plan; every kernel runs under a
 device-side row bound; x, dy, the ReLU source and the second input hold NaN in every row at or behind the bound (and in a whole image

@@ -3,7 +3,8 @@ every pass on the call's own inputs with the bar of every element, the host plan
 realise_debug_conv_nt_path), the same launch as plain float32 code ("statement", with the mutants), and the tables of shapes.
 
 tests/test_tower_edges_gpu.py runs the kernels through them; tests/test_tower_cases_cpu.py runs the statements and subtly wrong answers
-through them without a GPU.  The bars: DESIGN section 3, "Element-wise bars of the glyph tower's BatchNorm".
+through them without a GPU.  The entry points it launches call bn_stats / bn_backward / bn_apply, the host functions the engine calls.
+The bars: DESIGN section 3, "Element-wise bars of the glyph tower's BatchNorm".
 """
 import ctypes as C
 import functools
