@@ -22,7 +22,7 @@ extern "C" {
 #define REALISE_BF16 1
 /* fp32 buffers; the dense (Linear) GEMMs split every operand value x in registers into hi = bf16(x), lo = bf16(x - hi) and form
  * hi.hi + hi.lo + lo.hi on the bf16 MFMA with fp32 accumulation (the lo.lo term is not computed).  Accepted by realise_gemm_nt,
- * realise_gemm_nt_rows, realise_gemm_tn, realise_gemm_tn_grouped (+ _live) and the realise_debug_* calls that describe them, and as
+ * realise_gemm_nt_decode (a form of it), realise_gemm_nt_rows, realise_gemm_tn, realise_gemm_tn_grouped (+ _live) and the realise_debug_* calls that describe them, and as
  * realise_config.dtype (every other kernel of that engine - convolutions, attention, row kernels - is the REALISE_F32 one); every
  * other operator refuses it. */
 #define REALISE_F32_BF16X3 2
@@ -249,6 +249,35 @@ int realise_segment_sum_chw4(void* stream, int dtype, const void* x, const int32
  * `logits.detach().cpu().numpy()` + `np.argmax(preds, axis=-1)` (src/run.py:262-263): only the ids cross PCIe. */
 int realise_argmax(void* stream, int dtype, const void* logits, int64_t ld, int rows, int V, int64_t* ids);
 
+/* Top-k decoding fused into the classifier GEMM: C = A . B^T + bias is never stored.  Replaces the [B, S, V] logits of
+ * models.py:859-869 plus `np.argmax(preds, -1)` (src/run.py:262-263, src/test.py:143) where only the corrections - and how sure the
+ * model is of them - are wanted.  Per row: the best k columns (ids), their logits (values), exp(value - lse) (probs), the row's
+ * log-sum-exp over all N columns (lse) and, with `labels`, the logit at labels[row] (label_logit; a label outside [0, N) leaves its
+ * entry unwritten).  Ranking is on the value the default forward would have stored - bf16(acc + bias) widened to fp32 for
+ * REALISE_BF16 (what realise_batch.logits_f32_out holds), the fp32 value otherwise; a beats b when a > b or a is NaN and b is not,
+ * the lower column on equal values (realise_argmax's rule and numpy's); -0.0 ranks, and is reported, as +0.0.  Columns >= N enter
+ * nothing.  With k = 1 the launch takes the persistent 256 x 192 kernel exactly where realise_gemm_nt with a plain store to pitch N
+ * would; otherwise, and for k > 1, the 4-wave 128 x 128 / 128 x 96 tile of the cost rule (realise_debug_nt_path, mode 16).  Where the
+ * decode launch and the plain store run the same kernel, `values` are the stored logits bit for bit; where the plain store would take
+ * another kernel (an 8-wave kernel of small N at M >= 1024, the 256 x 128 tile, the persistent kernel for k > 1), equality with the
+ * stored logits holds up to accumulation order only.  Each (row, column slab of one wave) leaves one record in `scratch`
+ * (16-byte aligned, realise_gemm_nt_decode_scratch_bytes of the same arguments, which is 0 for a refused shape); a merge kernel folds
+ * them in ascending column order, so two launches agree bit for bit.  Refused (argument error, before any pointer is read): N <= 64,
+ * N < k, N % 4 != 0, a K or pitch realise_gemm_nt refuses, k outside 1..4, a scratch that is too small. */
+typedef struct {
+  int32_t k;                 /* 1..4 */
+  int64_t* ids;              /* [rows, k] */
+  float* values;             /* [rows, k] logits as the default forward would have stored them */
+  float* probs;              /* [rows, k] exp(value - lse) */
+  float* lse;                /* [rows] */
+  float* label_logit;        /* nullable, [rows]: the value at labels[row] */
+  void* scratch; int64_t scratch_bytes;
+} realise_decode;
+int64_t realise_gemm_nt_decode_scratch_bytes(int dtype, int M, int N, int K, int k);
+int realise_gemm_nt_decode(void* stream, int dtype, const void* A, int64_t lda, const void* B, int64_t ldb,
+                           int M, int N, int K, const float* bias, const int64_t* labels /* nullable */,
+                           const realise_decode* d);
+
 /* ------------------------------------------------------------------------------------------
  * Whole-model engine: SpellBert.forward (models.py:50-73) / SpellBertPho2ResArch3.forward
  * (models.py:806-870) and their autograd (`loss.backward()`, run.py:200), one C call each.
@@ -328,6 +357,12 @@ void realise_engine_set_id_flag(realise_engine* e, int32_t* flag);
  * leave the classifier head inside the kernels that store them; the host never reads it and the cross-entropy gradient rows are
  * not touched.  The pointer must stay valid until the backward's kernels have run; it stays installed until changed. */
 void realise_engine_set_loss_grad(realise_engine* e, const float* grad_dev);
+/* Inference without logits (replaces models.py:859-869 + src/run.py:262-263 / src/test.py:143 `np.argmax(preds, -1)`): with a decode
+ * request installed, realise_engine_forward with training == 0 and logits_out == NULL runs the MLM transform over every row (where
+ * the variant has one) and realise_gemm_nt_decode on the classifier input - rows = B * S, the outputs in `d` - and, with tgt_idx /
+ * loss_masks, writes the masked mean of lse - label_logit to loss_out (d->label_logit is then required).  The struct is copied; NULL
+ * clears the request.  Without a request a NULL logits_out behaves as before. */
+void realise_engine_set_decode(realise_engine* e, const realise_decode* d);
 
 typedef struct {
   int32_t B, S, Tp;

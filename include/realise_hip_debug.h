@@ -191,7 +191,9 @@ int realise_conv_tn_ex(void* stream, int dtype, const void* A, int64_t lda, cons
  * that tests can pin the kernel a case is meant for.  -1 refused (argument error), 0 nothing to launch; 4-wave kernels: 1 256 x 64,
  * 2 128 x 128, 3 128 x 96, 4 256 x 128 with spread fetches; 8-wave kernels: 5 256 x 192, 6 128 x 192 three-stage, 7 128 x 192
  * two-per-CU, 8 the ragged-K instantiation; 9 persistent 256 x 192, 10 the same bounded by the device-side row count; 11 8-wave
- * 128 x 192 two-per-CU with exact row masking under a device-side row count. */
+ * 128 x 192 two-per-CU with exact row masking under a device-side row count.
+ * mode 16: the route of realise_gemm_nt_decode for (dtype, M, N, K, lda, ldb) and k = `accumulate` (0 counts as 1) - 9, 2 or 3, or
+ * -1 where it is refused; has_aux, ldo, ldaux and rows_dev_given are ignored. */
 int realise_debug_nt_path(int dtype, int M, int N, int K, int mode, int accumulate, int has_aux, int64_t lda, int64_t ldb, int64_t ldo,
                           int64_t ldaux, int rows_dev_given);
 

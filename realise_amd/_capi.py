@@ -83,6 +83,11 @@ class Batch(C.Structure):
                 ("n_alive_dev", C.c_void_p), ("eval_live_rows", C.c_int32), ("logits_f32_out", C.c_void_p)]
 
 
+class Decode(C.Structure):
+    _fields_ = [("k", C.c_int32), ("ids", C.c_void_p), ("values", C.c_void_p), ("probs", C.c_void_p), ("lse", C.c_void_p),
+                ("label_logit", C.c_void_p), ("scratch", C.c_void_p), ("scratch_bytes", C.c_int64)]
+
+
 # every symbol include/realise_hip.h declares: name -> (restype, argtypes)
 _P, _I, _L, _F, _U = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint32
 SYMBOLS = {
@@ -149,6 +154,9 @@ SYMBOLS = {
     "realise_gather_rows_chw4": (_I, [_P, _I, _P, _P, _I, _I, _P]),
     "realise_segment_sum_chw4": (_I, [_P, _I, _P, _P, _I, _I, _P, _P, _P]),
     "realise_argmax": (_I, [_P, _I, _P, _L, _I, _I, _P]),
+    "realise_gemm_nt_decode_scratch_bytes": (_L, [_I, _I, _I, _I, _I]),
+    "realise_gemm_nt_decode": (_I, [_P, _I, _P, _L, _P, _L, _I, _I, _I, _P, _P, C.POINTER(Decode)]),
+    "realise_engine_set_decode": (None, [_P, C.POINTER(Decode)]),
     "realise_build_pho": (_I, [_P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P]),
     "realise_layout_count": (_I, [C.POINTER(Config)]),
     "realise_layout_entry": (_I, [C.POINTER(Config), _I, C.c_char_p, _I, C.POINTER(C.c_int32), C.POINTER(_L),

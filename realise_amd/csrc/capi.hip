@@ -250,6 +250,17 @@ int realise_build_pho(void* stream, const int64_t* src_idx, int T, const int64_t
 int realise_argmax(void* stream, int dtype, const void* logits, int64_t ld, int rows, int V, int64_t* ids) {
   RL_BY_DTYPE(0, argmax_rows<E>((hipStream_t)stream, (const E*)logits, ld, rows, V, ids));
 }
+// models.py:859-869 + np.argmax(preds, -1) (src/run.py:262-263, src/test.py:143) without the logits: see include/realise_hip.h
+int64_t realise_gemm_nt_decode_scratch_bytes(int dtype, int M, int N, int K, int k) {
+  RL_BY_DTYPE_OR(0, 1, nt_decode_scratch_bytes(gemm_nt_decode_path<E>(M, N, K, K, K, k, x3), M, N, k));
+}
+int realise_gemm_nt_decode(void* stream, int dtype, const void* A, int64_t lda, const void* B, int64_t ldb, int M, int N, int K,
+                           const float* bias, const int64_t* labels, const realise_decode* d) {
+  if (!d) return RL_ERR_ARG;
+  DecodeOut o; o.k = d->k; o.ids = d->ids; o.values = d->values; o.probs = d->probs; o.lse = d->lse; o.label_logit = d->label_logit;
+  o.scratch = d->scratch; o.scratch_bytes = d->scratch_bytes;
+  RL_BY_DTYPE(1, gemm_nt_decode<E>((hipStream_t)stream, (const E*)A, lda, (const E*)B, ldb, M, N, K, bias, labels, o, x3));
+}
 int realise_masked_ce(void* stream, int dtype, const void* logits, int64_t ld, const int64_t* labels, const int64_t* loss_mask,
                       int rows, int V, float* loss_out, float* count_scratch, void* dlogits) {
   RL_BY_DTYPE(0, ce_loss<E>((hipStream_t)stream, (const E*)logits, ld, labels, loss_mask, rows, V, loss_out, count_scratch, (E*)dlogits));
@@ -417,6 +428,7 @@ int realise_conv_tn_ex(void* stream, int dtype, const void* A, int64_t lda, cons
 }
 int realise_debug_nt_path(int dtype, int M, int N, int K, int mode, int accumulate, int has_aux, int64_t lda, int64_t ldb, int64_t ldo,
                           int64_t ldaux, int rows_dev_given) {
+  if (mode == 16) RL_BY_DTYPE_OR(NT_PATH_REFUSED, 1, gemm_nt_decode_path<E>(M, N, K, lda, ldb, accumulate > 0 ? accumulate : 1, x3));
   RL_BY_DTYPE_OR(NT_PATH_REFUSED, 1, gemm_nt_path<E>(M, N, K, path_epi<E>(x3, mode, accumulate, has_aux, 0, ldo, ldaux), lda, ldb, rows_dev_given != 0));
 }
 int realise_debug_bn_plan(int dtype, int P, int C, int hw, int slots_given, int branches, realise_bn_plan* plan) {
@@ -487,6 +499,7 @@ void realise_engine_invalidate_frozen(realise_engine* e) { if (e) e->impl->inval
 void realise_engine_set_grads_fresh(realise_engine* e, int fresh) { if (e) e->impl->set_grads_fresh(fresh); }
 void realise_engine_set_id_flag(realise_engine* e, int32_t* flag) { if (e) e->impl->set_id_flag((int*)flag); }
 void realise_engine_set_loss_grad(realise_engine* e, const float* grad_dev) { if (e) e->impl->set_loss_grad(grad_dev); }
+void realise_engine_set_decode(realise_engine* e, const realise_decode* d) { if (e) e->impl->set_decode(d); }
 int realise_engine_forward(realise_engine* e, void* stream, const realise_batch* batch) {
   return (e && batch) ? e->impl->forward((hipStream_t)stream, *batch) : RL_ERR_ARG;
 }

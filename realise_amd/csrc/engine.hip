@@ -1366,6 +1366,22 @@ template <typename T> struct Engine : EngineBase {
     const DropParams dfin = site(5000, cfg.hidden_dropout);
     const T* cls_in = top;
     if (dfin.thresh) { RL_TRY(dropout_apply<T>(st, top, wp<T>(pl.out_d), Tk, H, dfin)); cls_in = wp<T>(pl.out_d); }
+    if (b.logits_out == nullptr && !b.training && dec_req.k != 0) {
+      // Inference (models.py:859-869 + np.argmax(preds, -1) of src/run.py:262-263 / src/test.py:143) without a [B*S, V] tensor: the
+      // classifier GEMM's epilogue reduces its tiles to per-row candidates and softmax partials (gemm_nt_decode), every row, every dtype.
+      const bool want_loss = b.tgt_idx != nullptr;
+      if (want_loss && (!b.loss_masks || !b.loss_out || !dec_req.label_logit)) return RL_ERR_ARG;
+      if (vr.mlm_head) {
+        RL_TRY(head_forward(st, cls_in, Tk, nullptr));
+        cls_in = wp<T>(pl.head_y);
+      }
+      DecodeOut o; o.k = dec_req.k; o.ids = dec_req.ids; o.values = dec_req.values; o.probs = dec_req.probs; o.lse = dec_req.lse;
+      o.label_logit = dec_req.label_logit; o.scratch = dec_req.scratch; o.scratch_bytes = dec_req.scratch_bytes;
+      RL_TRY(gemm_nt_decode<T>(st, cls_in, H, sp<T>(sh_cls_w), H, Tk, V, H, pp(L.cls_b), want_loss ? b.tgt_idx : nullptr, o, sizeof(T) == 4 ? x3() : 0));
+      if (want_loss) RL_TRY(decode_loss(st, dec_req.lse, dec_req.label_logit, b.tgt_idx, b.loss_masks, Tk, b.loss_out));
+      have_fwd = false;
+      return RL_OK;
+    }
     if (b.logits_out == nullptr) {
       // K13 (round 6; models.py:859-869 as the training loop consumes it, run.py:191 takes the loss alone): no [B*S, V] logits.  The
       // classifier runs over the rows that enter the loss only - listed first, the classifier input gathered to match - and writes
@@ -1521,6 +1537,8 @@ template <typename T> struct Engine : EngineBase {
   // hidden) - instead of a read-modify-write pass over the ~200 MB of cross-entropy gradient rows
   const float* loss_grad = nullptr;
   void set_loss_grad(const float* g) override { loss_grad = g; }
+  realise_decode dec_req = realise_decode();      // k == 0: no decode request installed
+  void set_decode(const realise_decode* d) override { if (d) dec_req = *d; else dec_req = realise_decode(); }
   int stage_head(const Lane& la) {      // classifier + final dropout ; leaves d(top hidden) in gA
     const hipStream_t st = la.st;
     const int Tk = pl.B * pl.S;

@@ -13,8 +13,20 @@ enum EpiMode {
   EPI_AFFINE = 8,      // out = [relu](acc * col_scale[col] + bias[col] (+ aux))  (K9, evaluation: BatchNorm folded into the convolution)
 };
 
+// Decode form of the NT GEMM (gemm_nt_decode): nothing of C is stored.  Every (row, column slab of one wave) leaves one record in
+// caller-owned scratch - the slab's best KC (value, column) pairs under DecCand's order (gemm_dev.h) and its online-softmax pair -
+// laid out [plane][slab][row] in 16-byte words (a wave's 16 rows are 256 contiguous bytes; the merge kernel reads coalesced).
+struct DecodeParams {
+  int kc = 0;                           // 0: not a decode launch; 1 / 4: candidates kept per record
+  int nslab = 0;                        // column slabs per row = tile columns x waves along N
+  float* rec = nullptr;
+  const int64_t* labels = nullptr;      // nullable [M]: the column whose value goes to label_logit[row] (outside [0, N): not written)
+  float* label_logit = nullptr;
+};
+
 template <typename T> struct EpiParams {
   int mode = EPI_STORE;
+  DecodeParams dec;
   T* out = nullptr;
   int64_t ldo = 0;
   T* out2 = nullptr;
@@ -447,6 +459,17 @@ int gemm_nt_path(int M, int N, int K, const EpiParams<T>& ep, int64_t lda, int64
 // the same for a gathered launch (realise_debug_conv_nt_path): what gemm_nt_conv acts on; `la` finalized
 template <typename T>
 int conv_nt_path(const ConvLoader<T>& la, int64_t ldb, int M, int N, int K, const EpiParams<T>& ep);
+// Decode launch (realise_gemm_nt_decode): the route - NT_PATH_8P exactly where the plain store of the same shape takes it, else the
+// 4-wave 128 x 128 / 128 x 96 tile of the cost rule -, the slab count of that route, the scratch it needs, and the launch + merge.
+template <typename T> int gemm_nt_decode_path(int M, int N, int K, int64_t lda, int64_t ldb, int k, int x3);
+int nt_decode_slabs(int path, int N);
+int64_t nt_decode_scratch_bytes(int path, int M, int N, int k);
+struct DecodeOut { int k = 0; int64_t* ids = nullptr; float* values = nullptr; float* probs = nullptr; float* lse = nullptr;
+                   float* label_logit = nullptr; void* scratch = nullptr; int64_t scratch_bytes = 0; };
+template <typename T>
+int gemm_nt_decode(hipStream_t st, const T* A, int64_t lda, const T* B, int64_t ldb, int M, int N, int K, const float* bias,
+                   const int64_t* labels, const DecodeOut& d, int x3);
+int gemm_nt8p_decode(hipStream_t st, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, int M, int N, int K, const EpiParams<bf16_t>& ep);
 void set_nt8_group_m(int g);       // tile order of the 8-wave NT kernels: 0/1 row-major, g > 1: g tile rows per column step (L2 blocking)
 
 void tn_fold_launch(hipStream_t st, const TnEpi& ep, int nsplit, int I, int J);     // out += alpha * sum of the split slabs, fixed order

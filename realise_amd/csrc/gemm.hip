@@ -17,6 +17,7 @@
 // Operands are passed to the MFMA swapped (B-fragment first) so each lane ends up with 4 CONSECUTIVE
 // OUTPUT COLUMNS of one row: epilogue loads/stores are 8-16 B per lane.
 #include "gemm_dev.h"
+#include "ops.h"
 #include "prof.h"
 
 namespace rl {
@@ -50,7 +51,8 @@ template <typename T, int NA> struct ConvRows<ConvLoader<T>, NA> {
   }
 };
 
-template <typename T, typename ALoader, int WM, int WN, int NSTAGE, int NF, bool SPREAD, bool X3 = false>
+// DEC = 1 / 4: the decode form (DecodeParams, gemm.h) - same main loop, same accumulators, nothing of C stored
+template <typename T, typename ALoader, int WM, int WN, int NSTAGE, int NF, bool SPREAD, bool X3 = false, int DEC = 0>
 __global__ void __launch_bounds__(64 * WM * WN, (WM * WN == 4 && NSTAGE == 2) ? 2 : 1)
 gemm_nt_kernel(ALoader la, DenseLoader<T> lb, int M, int N, int K, int tiles_n, int ntiles, EpiParams<T> ep) {
   typedef typename MmaSel<T, X3>::type Mma;      // X3 (T = float): the K-tile of 32 floats is ONE split-bf16 16x16x32 step
@@ -215,6 +217,37 @@ gemm_nt_kernel(ALoader la, DenseLoader<T> lb, int M, int N, int K, int tiles_n, 
       }
     }
   }
+  if constexpr (DEC > 0) {
+    // Decode epilogue: per row of the wave's 64 x 16NF slab the best DEC (value, column) pairs and the softmax pair, on the values a
+    // plain store would have left (acc + bias, rounded to T); one record per (row, slab) from the g == 0 lane, 256 contiguous bytes
+    // per 16 rows.  Columns at or beyond N enter nothing.
+    const int cf = n0 + wn * 16 * NF + 4 * g, slab = tn * WN + wn;
+    floatx4 b4[NF];
+#pragma unroll
+    for (int j = 0; j < NF; ++j)
+      b4[j] = (ep.bias != nullptr && cf + 16 * j < N) ? *(const floatx4*)(ep.bias + cf + 16 * j) : floatx4{0.f, 0.f, 0.f, 0.f};
+    uint4* rec = (uint4*)ep.dec.rec;
+#pragma unroll
+    for (int i = 0; i < 4; ++i) {
+      const int row = m0 + wm * 64 + i * 16 + l15;
+      auto val = [&](int j) { return dec_round<T>(acc[i][j] + b4[j]); };
+      int label = -1;
+      if (ep.dec.labels != nullptr && row < M) {
+        const int64_t lb = ep.dec.labels[row];
+        label = (lb >= 0 && lb < N) ? (int)lb : -1;
+      }
+      float lv; bool own;
+      const DecCand<DEC> c = dec_row<T, DEC, NF>(val, cf, N, ep.dec.labels != nullptr, label, lv, own);
+      if (row < M) {
+        if (g == 0) {
+#pragma unroll
+          for (int p = 0; p < (DEC == 1 ? 1 : 3); ++p) rec[((int64_t)p * ep.dec.nslab + slab) * M + row] = dec_plane<DEC>(c, p);
+        }
+        if (own && ep.dec.label_logit != nullptr) ep.dec.label_logit[row] = lv;
+      }
+    }
+    return;
+  }
   if (ep.wide) {
     // Each wave transposes its 64 x 16NF result through a private, padded fp32 LDS tile (row stride 16NF + 4 floats:
     // the 8-lane groups of ds_write_b128 land on 8 distinct 4-bank sets) and leaves with 8 consecutive columns per lane.
@@ -250,7 +283,7 @@ void set_nt_variant(int v) { g_nt_variant = (v == 9 || v == 12 || v == 14 || v =
 static int g_tn_split = 0;
 void set_tn_split(int n) { g_tn_split = n; }
 
-template <typename T, typename ALoader, int WM, int WN, int NSTAGE = 2, int NF = 4, bool SPREAD = false, bool X3 = false>
+template <typename T, typename ALoader, int WM, int WN, int NSTAGE = 2, int NF = 4, bool SPREAD = false, bool X3 = false, int DEC = 0>
 static int launch_nt_tile(hipStream_t st, const ALoader& la, const DenseLoader<T>& lb, int M, int N, int K, const EpiParams<T>& ep) {
   constexpr int BM_ = 64 * WM, BN_ = 16 * NF * WN;
   const int tiles_m = (M + BM_ - 1) / BM_, tiles_n = (N + BN_ - 1) / BN_;
@@ -259,7 +292,7 @@ static int launch_nt_tile(hipStream_t st, const ALoader& la, const DenseLoader<T
   const size_t lds = ring > etile ? ring : etile;        // the epilogue re-uses the ring as per-wave transpose tiles
   static bool attr_set = false;
   if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_nt_kernel<T, ALoader, WM, WN, NSTAGE, NF, SPREAD, X3>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+    (void)hipFuncSetAttribute((const void*)gemm_nt_kernel<T, ALoader, WM, WN, NSTAGE, NF, SPREAD, X3, DEC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
     attr_set = true;
   }
   ProfScope ps(st, sizeof(typename ALoader::KPos) == sizeof(typename DenseLoader<T>::KPos) ? PK_GEMM_NT : PK_CONV_NT, 2.0 * M * N * K);
@@ -267,10 +300,15 @@ static int launch_nt_tile(hipStream_t st, const ALoader& la, const DenseLoader<T
     if (la.rows_dev != nullptr) prof_set_exec(la.rows_dev, 2.0 * N * K, BM_, M);   // device-side row bound: surplus tiles exit at once
   EpiParams<T> epp = ep;
   epp.wide = (N % 8 == 0) && (ep.ldo % 8 == 0) && (ep.aux == nullptr || ep.ldaux % 8 == 0);
-  RL_LAUNCH((gemm_nt_kernel<T, ALoader, WM, WN, NSTAGE, NF, SPREAD, X3>), dim3(ntiles), dim3(64 * WM * WN), lds, st, la, lb, M, N, K, tiles_n, ntiles, epp);
+  RL_LAUNCH((gemm_nt_kernel<T, ALoader, WM, WN, NSTAGE, NF, SPREAD, X3, DEC>), dim3(ntiles), dim3(64 * WM * WN), lds, st, la, lb, M, N, K, tiles_n, ntiles, epp);
   return hipGetLastError() == hipSuccess ? RL_OK : RL_ERR_LAUNCH;
 }
 
+static double nt_tile_cost(int M, int N, int bn) {       // the tile-width rule of nt_path (below)
+  const long tiles = (long)((M + 127) / 128) * ((N + bn - 1) / bn);
+  const long tpc = (tiles + 255) / 256;
+  return bn * (tpc == 1 ? 1.0 : 0.75 * (double)tpc);
+}
 // Which kernel a launch reaches: ONE pure host function of the shape, the epilogue and the knobs (g_nt_variant, g_nt_n96), called by
 // launch_nt itself and exported as realise_debug_nt_path (NtPath, gemm.h) so that a test can pin the choice it relies on.
 template <typename T>
@@ -282,11 +320,7 @@ static int nt_path(bool dense, bool rows_dev, int M, int N, int K, const EpiPara
   // minimise  width x f(tiles per CU)  with f(1) = 1 and f(n) = 0.75 n (two co-resident tiles overlap each other's
   // stalls): e.g. M = 8192, N = 768 -> 8 x 96 columns = 512 tiles, two per CU on every CU, instead of 384 tiles of
   // 128 columns (half the CUs run two, half run one): +25 % measured (tools/nt_probe.cpp, n96 knob).
-  auto cost = [&](int bn) {
-    const long tiles = (long)((M + 127) / 128) * ((N + bn - 1) / bn);
-    const long tpc = (tiles + 255) / 256;
-    return bn * (tpc == 1 ? 1.0 : 0.75 * (double)tpc);
-  };
+  auto cost = [&](int bn) { return nt_tile_cost(M, N, bn); };
   if constexpr (sizeof(T) == 2) {
     if (dense) {
       // Production path for the big dense GEMMs: the ping-pong 8-wave kernel (gemm_nt8.hip), tile by chip fill.  Variants 12 / 14 / 16
@@ -396,6 +430,75 @@ int gemm_nt(hipStream_t st, const T* A, int64_t lda, const T* B, int64_t ldb, in
   la.rows_dev = rows_dev;
   return launch_nt<T, DenseLoader<T>>(st, la, B, ldb, M, N, K, ep);
 }
+// ---- decode launch: C = A . B^T + bias reduced per row to its best k entries and its log-sum-exp; no C anywhere ----
+// Route: NT_PATH_8P exactly where the plain store of the same shape (out pitch N) takes it - same body, same tile, same k-order, so the
+// accumulators are those of the storing launch bit for bit -; likewise on the 4-wave 128 x 128 / 128 x 96 tiles.  Where the storing
+// launch would take another kernel (the 8-wave tiles of gemm_nt8.hip, the 256 x 128 tile), and for k > 1 where it would take the
+// persistent kernel (whose decode form keeps one candidate: gemm_nt8p.hip), the decode launch runs the 4-wave tile of the cost rule:
+// equal to the stored logits up to accumulation order only.
+template <typename T>
+int gemm_nt_decode_path(int M, int N, int K, int64_t lda, int64_t ldb, int k, int x3) {
+  if (k < 1 || k > 4 || M <= 0 || K <= 0 || N <= 64 || N < k || (N & 3)) return NT_PATH_REFUSED;
+  static const uint64_t some_operand[2] = {0, 0};      // (only compared with nullptr)
+  EpiParams<T> ep; ep.mode = EPI_STORE; ep.out = (T*)some_operand; ep.ldo = N; ep.bias = (const float*)some_operand; ep.x3 = x3;
+  if (!gemm_nt_args_ok<T>(lda, ep)) return NT_PATH_REFUSED;
+  const int p = nt_path<T>(true, false, M, N, K, ep, lda, ldb);
+  if (p == NT_PATH_REFUSED || p == NT_PATH_NONE) return NT_PATH_REFUSED;
+  if ((p == NT_PATH_8P && k == 1) || p == NT_PATH_4W_128x128 || p == NT_PATH_4W_128x96) return p;
+  return (g_nt_n96 && nt_tile_cost(M, N, 96) < nt_tile_cost(M, N, 128)) ? NT_PATH_4W_128x96 : NT_PATH_4W_128x128;
+}
+template int gemm_nt_decode_path<bf16_t>(int, int, int, int64_t, int64_t, int, int);
+template int gemm_nt_decode_path<float>(int, int, int, int64_t, int64_t, int, int);
+// slabs per row: one per wave along N - 96 columns on the persistent tile (192 x 2 waves), 64 / 48 on the 4-wave tiles
+int nt_decode_slabs(int path, int N) {
+  switch (path) {
+    case NT_PATH_8P: return ((N + 191) / 192) * 2;
+    case NT_PATH_4W_128x128: return ((N + 127) / 128) * 2;
+    case NT_PATH_4W_128x96: return ((N + 95) / 96) * 2;
+    default: return 0;
+  }
+}
+int64_t nt_decode_scratch_bytes(int path, int M, int N, int k) {
+  const int ns = nt_decode_slabs(path, N);
+  if (ns <= 0 || M <= 0 || k < 1 || k > 4) return 0;
+  return (int64_t)(k == 1 ? 1 : 3) * ns * (int64_t)M * 16;
+}
+template <typename T>
+int gemm_nt_decode(hipStream_t st, const T* A, int64_t lda, const T* B, int64_t ldb, int M, int N, int K, const float* bias,
+                   const int64_t* labels, const DecodeOut& d, int x3) {
+  const int path = gemm_nt_decode_path<T>(M, N, K, lda, ldb, d.k, x3);
+  if (path == NT_PATH_REFUSED) return RL_ERR_ARG;
+  const int64_t need = nt_decode_scratch_bytes(path, M, N, d.k);
+  if (!A || !B || !d.ids || !d.values || !d.probs || !d.lse || !d.scratch || d.scratch_bytes < need || need >= 0x7FFFFF00ll ||
+      ((uintptr_t)d.scratch & 15) || (labels != nullptr && d.label_logit == nullptr)) return RL_ERR_ARG;
+  EpiParams<T> ep; ep.mode = EPI_STORE; ep.bias = bias; ep.x3 = x3; ep.ldo = N;
+  ep.dec.kc = d.k == 1 ? 1 : 4; ep.dec.nslab = nt_decode_slabs(path, N); ep.dec.rec = (float*)d.scratch;
+  ep.dec.labels = labels; ep.dec.label_logit = labels ? d.label_logit : nullptr;
+  DenseLoader<T> la{A, lda, M, K};
+  DenseLoader<T> lb{B, ldb, N, K};
+  typedef DenseLoader<T> DL;
+  int rc = RL_ERR_ARG;
+  const bool one = ep.dec.kc == 1, n96 = path == NT_PATH_4W_128x96;
+  if constexpr (sizeof(T) == 2) {
+    if (path == NT_PATH_8P) rc = gemm_nt8p_decode(st, A, lda, B, ldb, M, N, K, ep);
+  }
+  if (path != NT_PATH_8P) {
+    if constexpr (sizeof(T) == 4) {
+      if (x3) {
+        rc = n96 ? (one ? launch_nt_tile<T, DL, 2, 2, 2, 3, false, true, 1>(st, la, lb, M, N, K, ep) : launch_nt_tile<T, DL, 2, 2, 2, 3, false, true, 4>(st, la, lb, M, N, K, ep))
+                 : (one ? launch_nt_tile<T, DL, 2, 2, 2, 4, false, true, 1>(st, la, lb, M, N, K, ep) : launch_nt_tile<T, DL, 2, 2, 2, 4, false, true, 4>(st, la, lb, M, N, K, ep));
+      }
+    }
+    if (!x3) {
+      rc = n96 ? (one ? launch_nt_tile<T, DL, 2, 2, 2, 3, false, false, 1>(st, la, lb, M, N, K, ep) : launch_nt_tile<T, DL, 2, 2, 2, 3, false, false, 4>(st, la, lb, M, N, K, ep))
+               : (one ? launch_nt_tile<T, DL, 2, 2, 2, 4, false, false, 1>(st, la, lb, M, N, K, ep) : launch_nt_tile<T, DL, 2, 2, 2, 4, false, false, 4>(st, la, lb, M, N, K, ep));
+    }
+  }
+  if (rc != RL_OK) return rc;
+  return decode_merge(st, ep.dec.rec, ep.dec.kc, ep.dec.nslab, M, d.k, d.ids, d.values, d.probs, d.lse);
+}
+template int gemm_nt_decode<bf16_t>(hipStream_t, const bf16_t*, int64_t, const bf16_t*, int64_t, int, int, int, const float*, const int64_t*, const DecodeOut&, int);
+template int gemm_nt_decode<float>(hipStream_t, const float*, int64_t, const float*, int64_t, int, int, int, const float*, const int64_t*, const DecodeOut&, int);
 // Which kernel a gathered launch reaches (realise_debug_conv_nt_path): the argument checks of gemm_nt_conv, the geometry test of the
 // LDS-resident 64-channel kernel, else the choice of launch_nt.  `la` is finalized.
 template <typename T>

@@ -155,6 +155,119 @@ __device__ __forceinline__ void epilogue8_pre(const EpiParams<bf16_t>& ep, int M
   }
 }
 
+// ---- decode epilogue (DecodeParams, gemm.h): top-KC candidates + online-softmax pair of one row over a wave's column slab --------
+// A candidate is (key, column).  key = the order-preserving unsigned image of the value the default forward would have stored: larger
+// key = better, every NaN is the largest key, -0.0 counts as +0.0 (and is reported as +0.0), so "a beats b" - a > b, or a NaN and b
+// not; the lower column on equal values - is  key_a > key_b || (key_a == key_b && col_a < col_b): a total order, so the best KC of a
+// row do not depend on the order in which slabs, lanes or workgroups are folded.  key 0 / column INT_MAX = no candidate.
+constexpr int DEC_NOCOL = 0x7FFFFFFF;
+__device__ __forceinline__ uint32_t dec_key(float x) {
+  const float y = x + 0.0f;
+  const uint32_t u = __float_as_uint(y);
+  return (y != y) ? 0xFFFFFFFFu : (u ^ ((uint32_t)((int32_t)u >> 31) | 0x80000000u));
+}
+__device__ __forceinline__ float dec_val(uint32_t k) {
+  return __uint_as_float(k == 0xFFFFFFFFu ? 0x7FC00000u : ((k & 0x80000000u) ? (k ^ 0x80000000u) : ~k));
+}
+template <int KC> struct DecCand {
+  uint32_t key[KC];
+  int col[KC];
+  float m, s;      // online softmax over the columns seen: m = their maximum (-inf: none seen), s = sum exp(v - m)
+  __device__ __forceinline__ void clear() {
+#pragma unroll
+    for (int j = 0; j < KC; ++j) { key[j] = 0u; col[j] = DEC_NOCOL; }
+    m = -__builtin_huge_valf(); s = 0.f;
+  }
+  // Sorted insertion as a chain of compare-exchanges (the newcomer sinks to its place, the last one falls out), written without
+  // short-circuit operators so that it compiles to compares and selects - no divergent branches in the GEMM's epilogue.
+  // TIES = false: the caller inserts in ascending column order (an equal key never displaces).
+  template <bool TIES> __device__ __forceinline__ void insert(uint32_t k, int c) {
+#pragma unroll
+    for (int j = 0; j < KC; ++j) {
+      const uint32_t ko = key[j];
+      const int co = col[j];
+      const bool gt = TIES ? ((k > ko) | ((k == ko) & (c < co))) : (k > ko);
+      key[j] = gt ? k : ko; col[j] = gt ? c : co;
+      k = gt ? ko : k; c = gt ? co : c;
+    }
+  }
+  __device__ __forceinline__ void fold_sum(float m2, float s2) {      // (a NaN sum stays NaN whatever the maxima are)
+    const float mm = fmaxf(m, m2);
+    s = s * (m == mm ? 1.0f : expf(m - mm)) + s2 * (m2 == mm ? 1.0f : expf(m2 - mm));
+    m = mm;
+  }
+};
+// the value a plain store would have left in memory, widened back to fp32
+template <typename T> __device__ __forceinline__ floatx4 dec_round(floatx4 v) {
+  if constexpr (sizeof(T) == 2) {
+    const uint32_t p0 = pack2bf(v[0], v[1]), p1 = pack2bf(v[2], v[3]);
+    v[0] = __uint_as_float(p0 << 16); v[1] = __uint_as_float(p0 & 0xffff0000u);
+    v[2] = __uint_as_float(p1 << 16); v[3] = __uint_as_float(p1 & 0xffff0000u);
+  }
+  return v;
+}
+// One row of a wave's slab in the accumulator layout of the NT kernels: lane (g, l15) holds get(j) = columns col0 + 16 j .. + 3 of row
+// l15 (col0 = slab start + 4 g; values biased and rounded: dec_round - formed on demand, twice, instead of living in 4 NT registers).  Returns, in every lane of the row, the slab's best KC
+// and its softmax pair; `label` (a column, or negative) picks the value at that column into lv and returns own = this lane holds it.
+template <typename T, int KC, int NT, typename F>
+__device__ __forceinline__ DecCand<KC> dec_row(const F& get, int col0, int N, bool has_label, int label, float& lv, bool& own) {
+  DecCand<KC> c;
+  c.clear();
+  own = false; lv = 0.f;
+#pragma unroll
+  for (int j = 0; j < NT; ++j) {
+    const bool ok = col0 + 16 * j < N;                 // N % 4 == 0: a lane's quad is inside or outside as a whole
+    const floatx4 v = get(j);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+      c.template insert<false>(ok ? dec_key(v[e]) : 0u, ok ? col0 + 16 * j + e : DEC_NOCOL);
+      if (has_label) {                                 // (uniform over the launch; a label is below N, so a column behind N never matches)
+        const bool hit = col0 + 16 * j + e == label;
+        own = own | hit; lv = hit ? v[e] : lv;
+      }
+    }
+  }
+  // the lane's sum around its own maximum (its best candidate; a NaN there makes the sum NaN)
+  if (c.col[0] != DEC_NOCOL) {
+    c.m = dec_val(c.key[0]);
+    float s = 0.f;
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+      if (col0 + 16 * j < N) {
+        const floatx4 v = get(j);
+#pragma unroll
+        for (int e = 0; e < 4; ++e) s += exp_t<T>(v[e] - c.m);
+      }
+    }
+    c.s = s;
+  }
+  // the four lanes of a row: l15, l15 + 16, l15 + 32, l15 + 48.  Both partners of an exchange compute the same list.
+#pragma unroll
+  for (int o = 16; o <= 32; o <<= 1) {
+    uint32_t pk[KC]; int pc[KC];
+#pragma unroll
+    for (int j = 0; j < KC; ++j) { pk[j] = (uint32_t)__shfl_xor((int)c.key[j], o, 64); pc[j] = __shfl_xor(c.col[j], o, 64); }
+    const float pm = __shfl_xor(c.m, o, 64), ps = __shfl_xor(c.s, o, 64);
+#pragma unroll
+    for (int j = 0; j < KC; ++j) c.template insert<true>(pk[j], pc[j]);
+    // (the lower lane's pair first in both partners: the same rounding on either side)
+    const bool hi = (threadIdx.x & o) != 0;
+    DecCand<KC> t; t.m = hi ? pm : c.m; t.s = hi ? ps : c.s;
+    t.fold_sum(hi ? c.m : pm, hi ? c.s : ps);
+    c.m = t.m; c.s = t.s;
+  }
+  return c;
+}
+// record words of one (row, slab): plane 0 = {value, column, m, s} (KC = 1) / plane 0 = values, 1 = columns, 2 = {m, s, 0, 0} (KC = 4)
+template <int KC> __device__ __forceinline__ uint4 dec_plane(const DecCand<KC>& c, int p) {
+  if constexpr (KC == 1) return uint4{__float_as_uint(dec_val(c.key[0])), (uint32_t)c.col[0], __float_as_uint(c.m), __float_as_uint(c.s)};
+  else {
+    if (p == 0) return uint4{__float_as_uint(dec_val(c.key[0])), __float_as_uint(dec_val(c.key[1])), __float_as_uint(dec_val(c.key[2])), __float_as_uint(dec_val(c.key[3]))};
+    if (p == 1) return uint4{(uint32_t)c.col[0], (uint32_t)c.col[1], (uint32_t)c.col[2], (uint32_t)c.col[3]};
+    return uint4{__float_as_uint(c.m), __float_as_uint(c.s), 0u, 0u};
+  }
+}
+
 // ---- TN (weight-gradient) device helpers of gemm.hip ---------------------------------------------
 template <typename T> struct TnGeo;
 template <> struct TnGeo<bf16_t> { static constexpr int BP = 64, KSTEPS = 2, VEC = 8; };

@@ -24,6 +24,10 @@ namespace rl {
 typedef __attribute__((ext_vector_type(4))) uint32_t u32x4;
 constexpr int EPI_STORE_F32X = 8;      // template value only (not an EpiMode): EPI_STORE + EpiParams::out_f32
 constexpr int EPI_GELU_NOPRE = 9;      // template value only: EPI_GELU without the pre-activation store (out2 == nullptr: no backward follows)
+// template value only: the decode form (DecodeParams, gemm.h), ONE candidate per record.  The four-candidate form of this body did not
+// fit the 256 registers of two waves per SIMD (it compiled to 256 VGPRs + 412 bytes of scratch per lane, also as a rolled loop over the
+// row groups), so it is not instantiated: top-2..4 requests run on the 4-wave tile (gemm_nt_decode_path).
+constexpr int EPI_DECODE1 = 10;
 typedef __attribute__((ext_vector_type(4))) int i32x4;
 
 // (the host pass of hipcc parses kernel bodies too and silently drops a kernel stub whose body holds AMDGPU register constraints
@@ -35,6 +39,18 @@ __device__ __forceinline__ u32x4 asm_buffer_load_b128(uint32_t voff, i32x4 rsrc)
   asm volatile("s_nop 4\n\tbuffer_load_dwordx4 %0, %1, %2, 0 offen" : "=&v"(v) : "v"(voff), "s"(rsrc) : "memory");
 #endif
   return v;
+}
+__device__ __forceinline__ uint32_t asm_buffer_load_b32(uint32_t voff, i32x4 rsrc) {
+  uint32_t v = 0u;
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("s_nop 4\n\tbuffer_load_dword %0, %1, %2, 0 offen" : "=&v"(v) : "v"(voff), "s"(rsrc) : "memory");
+#endif
+  return v;
+}
+__device__ __forceinline__ void asm_after_wait(uint32_t& v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+  asm volatile("" : "+v"(v));
+#endif
 }
 __device__ __forceinline__ void asm_after_wait(u32x4& v) {      // pins the uses of an asm-loaded value behind the preceding s_waitcnt
 #if defined(__HIP_DEVICE_COMPILE__)
@@ -67,7 +83,13 @@ __device__ __forceinline__ void nt8p_body(const bf16_t* __restrict__ A, int64_t 
   static_assert(!C::HOLD_B && (NT % 2) == 0, "persistent kernel: hold-A schedule");
   // EPI_STORE_F32X (this file only): EPI_STORE + the fp32 copy of every stored value (EpiParams::out_f32), one 16-byte store per
   // accumulator tile in the accumulator layout (a lane: 4 consecutive columns of one row)
-  constexpr int NSTORE = MT * (NT / 2) * (EPI == EPI_GELU ? 2 : 1) + (EPI == EPI_STORE_F32X ? MT * NT : 0);      // 16-byte store instructions of one tile's epilogue, per wave
+  // Decode form: a wave's epilogue issues, for each of its MT row groups, the record (one 16-byte store) and one 4-byte
+  // label store - ALL of them unconditionally, every tile, by every wave (lanes with nothing to write aim beyond the descriptor's range
+  // and are dropped there), so the count the next tile's waits add is exact: 2 MT store instructions, none of C.
+  constexpr bool kDecode = EPI == EPI_DECODE1;
+  constexpr int KC = 1, DPLANES = 1;
+  constexpr int NSTORE = kDecode ? MT * (DPLANES + 1)
+                                 : MT * (NT / 2) * (EPI == EPI_GELU ? 2 : 1) + (EPI == EPI_STORE_F32X ? MT * NT : 0);      // store instructions of one tile's epilogue, per wave
   extern __shared__ __attribute__((aligned(16))) char smem[];
   const int tid = threadIdx.x, lane = tid & 63, g = lane >> 4, l15 = lane & 15;
   const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
@@ -131,6 +153,12 @@ __device__ __forceinline__ void nt8p_body(const bf16_t* __restrict__ A, int64_t 
   };
   const __amdgpu_buffer_rsrc_t rsF = __builtin_amdgcn_make_buffer_rsrc((void*)(EPI == EPI_STORE_F32X ? (void*)ep.out_f32 : (void*)ep.out), 0,
                                                                        EPI == EPI_STORE_F32X ? (int)(uint32_t)(((int64_t)(M - 1) * ep.ldo_f32 + N) * 4) : 0, 0x00020000);
+  // decode: the records, the label of every row (the low word of the int64: a column below 2^31 or no match) and the label's value
+  const bool has_lab = kDecode && ep.dec.labels != nullptr;
+  const uint32_t rec_bytes = kDecode ? (uint32_t)((int64_t)DPLANES * ep.dec.nslab * M * 16) : 0u;
+  const __amdgpu_buffer_rsrc_t rsR = __builtin_amdgcn_make_buffer_rsrc((void*)(kDecode ? (void*)ep.dec.rec : (void*)A), 0, (int)rec_bytes, 0x00020000);
+  const __amdgpu_buffer_rsrc_t rsL = __builtin_amdgcn_make_buffer_rsrc((void*)(has_lab ? (void*)ep.dec.label_logit : (void*)A), 0, has_lab ? M * 4 : 0, 0x00020000);
+  const i32x4 wLab = rsrc_words(has_lab ? (const void*)ep.dec.labels : (const void*)A, has_lab ? (uint32_t)M * 8u : 0u);
   const bool has_bias = EPI != EPI_GELU_BWD && ep.bias != nullptr;
   const i32x4 wBias = rsrc_words(has_bias ? (const void*)ep.bias : (const void*)A, has_bias ? (uint32_t)N * 4u : 0u);
   const i32x4 wX = rsrc_words(EPI == EPI_GELU_BWD ? (const void*)ep.aux : (const void*)A,
@@ -273,6 +301,15 @@ __device__ __forceinline__ void nt8p_body(const bf16_t* __restrict__ A, int64_t 
           ax[i][jp] = asm_buffer_load_b128(off, wX);
         }
     }
+    const int dslab = (n0 / C::BN) * C::WN + wn;      // decode: this wave's column slab of the tile just finished
+    uint32_t lab[kDecode ? MT : 1];
+    if constexpr (kDecode) {
+#pragma unroll
+      for (int i = 0; i < MT; ++i) {
+        const int r = row_w + 16 * i;
+        lab[i] = asm_buffer_load_b32(r < M ? (uint32_t)r * 8u : 0x7FFFFF00u, wLab);      // (no labels: a zero-size descriptor, reads 0, never used)
+      }
+    }
     int ntm, ntn;
     const bool more = tile_of(it + 1, ntm, ntn);
     if (more) {
@@ -294,6 +331,35 @@ __device__ __forceinline__ void nt8p_body(const bf16_t* __restrict__ A, int64_t 
         for (int jp = 0; jp < NT / 2; ++jp) asm_after_wait(ax[i][jp]);
     }
 
+    if constexpr (kDecode) {
+#pragma unroll
+      for (int i = 0; i < MT; ++i) asm_after_wait(lab[i]);
+      // the values EPI_STORE would have stored, bf16(acc + bias), replace the accumulators in place (the bias registers die here)
+#pragma unroll
+      for (int i = 0; i < MT; ++i)
+#pragma unroll
+        for (int j = 0; j < NT; ++j) {
+          if (has_bias) acc[i][j] += __builtin_bit_cast(floatx4, bias4[j]);
+          acc[i][j] = dec_round<bf16_t>(acc[i][j]);
+        }
+      __builtin_amdgcn_sched_barrier(0);
+      // per row group: the slab's candidate and softmax pair
+#pragma unroll
+      for (int i = 0; i < MT; ++i) {
+        const int r = row_w + 16 * i;
+        auto val = [&](int j) { return acc[i][j]; };
+        const int label = (has_lab && (int)lab[i] >= 0 && (int)lab[i] < N) ? (int)lab[i] : -1;
+        float lv; bool own;
+        const DecCand<KC> c = dec_row<bf16_t, KC, NT>(val, col_f, N, has_lab, label, lv, own);
+        const bool wr = g == 0 && r < M;
+#pragma unroll
+        for (int p = 0; p < DPLANES; ++p) {
+          const uint32_t off = wr ? (uint32_t)((((int64_t)p * ep.dec.nslab + dslab) * M + r) * 16) : 0x7FFFFF00u;
+          __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, dec_plane<KC>(c, p)), rsR, off, 0, 0);
+        }
+        __builtin_amdgcn_raw_buffer_store_b32(__float_as_uint(lv), rsL, (own && r < M) ? (uint32_t)r * 4u : 0x7FFFFF00u, 0, 0);
+      }
+    } else {
 #pragma unroll
     for (int i = 0; i < MT; ++i) {
 #pragma unroll
@@ -342,6 +408,7 @@ __device__ __forceinline__ void nt8p_body(const bf16_t* __restrict__ A, int64_t 
           __builtin_amdgcn_raw_buffer_store_b128(__builtin_bit_cast(u32x4, rnd(v1)), rsF, of1, 0, 0);
         }
       }
+    }
     }
     if (!more) break;
     ++it;
@@ -403,6 +470,15 @@ int gemm_nt8p(hipStream_t st, const bf16_t* A, int64_t lda, const bf16_t* B, int
     case EPI_GELU_BWD: return launch_nt8p<PCfg256x192, EPI_GELU_BWD>(st, A, lda, B, ldb, M, N, K, ep, g_nt8p_wgs);
     default: return RL_ERR_ARG;
   }
+}
+
+// the decode form of the persistent kernel (gemm_nt_decode, gemm.hip): the caller has checked that a plain store of this shape is supported
+int gemm_nt8p_decode(hipStream_t st, const bf16_t* A, int64_t lda, const bf16_t* B, int64_t ldb, int M, int N, int K, const EpiParams<bf16_t>& ep) {
+  if (ep.dec.rec == nullptr || ep.dec.nslab != ((N + PCfg256x192::BN - 1) / PCfg256x192::BN) * PCfg256x192::WN || ep.m_dev != nullptr ||
+      (int64_t)ep.dec.nslab * M * 16 >= 0x7FFFFF00ll || (int64_t)M * 8 >= 0x7FFFFF00ll || (K % 64) != 0 || K < 128 || (N % 8) != 0 ||
+      (lda % 8) != 0 || (ldb % 8) != 0 || (int64_t)M * lda * 2 >= 0x7FFFFF00ll || (int64_t)N * ldb * 2 >= 0x7FFFFF00ll) return RL_ERR_ARG;
+  if (ep.dec.kc != 1) return RL_ERR_ARG;
+  return launch_nt8p<PCfg256x192, EPI_DECODE1>(st, A, lda, B, ldb, M, N, K, ep, g_nt8p_wgs);
 }
 
 }  // namespace rl

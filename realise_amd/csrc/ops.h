@@ -315,6 +315,11 @@ template <typename T> int segment_sum_chw4(hipStream_t st, const T* x, const int
 // ---- weight shadows (operand copies in the compute dtype) ----------------------------------------
 template <typename T> int cast_copy(hipStream_t st, const float* src, T* dst, int64_t n);
 template <typename T> int cast_to_f32(hipStream_t st, const T* src, float* dst, int64_t n);     // 16-byte aligned pointers
+// Decode GEMM, second half (gemm_nt_decode): folds the nslab records of every row (DecodeParams, gemm.h), slabs ascending, into
+// ids / values / probs [M, k] and lse [M]; kc = candidates per record (1 or 4), k <= kc.
+int decode_merge(hipStream_t st, const float* rec, int kc, int nslab, int M, int k, int64_t* ids, float* values, float* probs, float* lse);
+// masked mean of lse - label_logit over the rows that enter the loss (models.py:862-869: loss_mask == 1, label != -100); one workgroup, fixed order
+int decode_loss(hipStream_t st, const float* lse, const float* label_logit, const int64_t* labels, const int64_t* loss_mask, int rows, float* loss_out);
 // src fp32 [R][C] -> dst [R][C] (optional) and dstT [C][R] (optional)
 template <typename T> int cast_transpose(hipStream_t st, const float* src, int R, int C, T* dst, T* dstT);
 // many matrices in ONE launch (the per-step refresh of every Linear weight's W and W^T operand copies): `descs` is a

@@ -597,6 +597,96 @@ template <typename T> int cast_to_f32(hipStream_t st, const T* src, float* dst, 
 template int cast_to_f32<bf16_t>(hipStream_t, const bf16_t*, float*, int64_t);
 template int cast_to_f32<float>(hipStream_t, const float*, float*, int64_t);
 
+// ---- decode GEMM: merge of the per-slab records (what np.argmax(preds, -1) of src/run.py:262-263 / src/test.py:143 read the [B, S, V]
+// logits for).  One lane per row; records are [plane][slab][row] 16-byte words, so a wave reads 1 KiB lines.  Slabs are folded in
+// ascending column order with the comparator of the epilogue (DecCand, gemm_dev.h): a function of the records alone.
+template <int KC>
+__global__ void __launch_bounds__(64) decode_merge_kernel(const uint4* __restrict__ rec, int nslab, int M, int k, int64_t* __restrict__ ids,
+                                                          float* __restrict__ values, float* __restrict__ probs, float* __restrict__ lse) {
+  const int row = blockIdx.x * 64 + threadIdx.x;
+  if (row >= M) return;
+  uint32_t key[KC]; int col[KC];
+#pragma unroll
+  for (int j = 0; j < KC; ++j) { key[j] = 0u; col[j] = 0x7FFFFFFF; }
+  float m = -__builtin_huge_valf(), s = 0.f;
+  auto beats = [](uint32_t ka, int ca, uint32_t kb, int cb) { return ka > kb || (ka == kb && ca < cb); };
+  auto keyof = [](float x) {
+    const float y = x + 0.0f;
+    const uint32_t u = __float_as_uint(y);
+    return (y != y) ? 0xFFFFFFFFu : (u ^ ((uint32_t)((int32_t)u >> 31) | 0x80000000u));
+  };
+  for (int sl = 0; sl < nslab; ++sl) {
+    uint32_t v[KC]; int c[KC]; float m2, s2;
+    if constexpr (KC == 1) {
+      const uint4 r = rec[(int64_t)sl * M + row];
+      v[0] = r.x; c[0] = (int)r.y; m2 = __uint_as_float(r.z); s2 = __uint_as_float(r.w);
+    } else {
+      const uint4 r0 = rec[(int64_t)sl * M + row], r1 = rec[((int64_t)nslab + sl) * M + row], r2 = rec[((int64_t)2 * nslab + sl) * M + row];
+      v[0] = r0.x; v[1] = r0.y; v[2] = r0.z; v[3] = r0.w;
+      c[0] = (int)r1.x; c[1] = (int)r1.y; c[2] = (int)r1.z; c[3] = (int)r1.w;
+      m2 = __uint_as_float(r2.x); s2 = __uint_as_float(r2.y);
+    }
+    if (c[0] == 0x7FFFFFFF) continue;                  // a slab that lies beyond N as a whole
+#pragma unroll
+    for (int e = 0; e < KC; ++e) {
+      const int ce = c[e];
+      const uint32_t ke = ce == 0x7FFFFFFF ? 0u : keyof(__uint_as_float(v[e]));
+      bool b[KC];
+#pragma unroll
+      for (int j = 0; j < KC; ++j) b[j] = beats(ke, ce, key[j], col[j]);
+#pragma unroll
+      for (int j = KC - 1; j >= 0; --j) {
+        const int jm = j > 0 ? j - 1 : 0;
+        const bool up = j > 0 && b[jm];
+        key[j] = b[j] ? (up ? key[jm] : ke) : key[j];
+        col[j] = b[j] ? (up ? col[jm] : ce) : col[j];
+      }
+    }
+    const float mm = fmaxf(m, m2);
+    s = s * (m == mm ? 1.0f : expf(m - mm)) + s2 * (m2 == mm ? 1.0f : expf(m2 - mm));
+    m = mm;
+  }
+  const float l = m + logf(s);
+  lse[row] = l;
+#pragma unroll
+  for (int j = 0; j < KC; ++j) {
+    if (j < k) {
+      const uint32_t kj = key[j];
+      const float val = __uint_as_float(kj == 0xFFFFFFFFu ? 0x7FC00000u : ((kj & 0x80000000u) ? (kj ^ 0x80000000u) : ~kj));
+      ids[(int64_t)row * k + j] = col[j];
+      values[(int64_t)row * k + j] = val;
+      probs[(int64_t)row * k + j] = expf(val - l);
+    }
+  }
+}
+int decode_merge(hipStream_t st, const float* rec, int kc, int nslab, int M, int k, int64_t* ids, float* values, float* probs, float* lse) {
+  if (!rec || !ids || !values || !probs || !lse || M < 1 || nslab < 1 || k < 1 || k > kc || (kc != 1 && kc != 4)) return RL_ERR_ARG;
+  const dim3 grid((M + 63) / 64);
+  if (kc == 1) hipLaunchKernelGGL((decode_merge_kernel<1>), grid, dim3(64), 0, st, (const uint4*)rec, nslab, M, k, ids, values, probs, lse);
+  else hipLaunchKernelGGL((decode_merge_kernel<4>), grid, dim3(64), 0, st, (const uint4*)rec, nslab, M, k, ids, values, probs, lse);
+  return RL_LAUNCH_CHECK();
+}
+
+// the loss of models.py:862-869 from the decode outputs: mean over the active rows of lse - logit[label]
+__global__ void __launch_bounds__(256) decode_loss_kernel(const float* __restrict__ lse, const float* __restrict__ label_logit,
+                                                          const int64_t* __restrict__ labels, const int64_t* __restrict__ loss_mask, int rows,
+                                                          float* __restrict__ loss_out) {
+  __shared__ float sm[8];
+  float a = 0.f, n = 0.f;
+  for (int i = threadIdx.x; i < rows; i += 256) {
+    if (loss_mask[i] == 1 && labels[i] != -100) { a += lse[i] - label_logit[i]; n += 1.f; }
+  }
+  a = wave_sum(a); n = wave_sum(n);
+  if ((threadIdx.x & 63) == 0) { sm[threadIdx.x >> 6] = a; sm[4 + (threadIdx.x >> 6)] = n; }
+  __syncthreads();
+  if (threadIdx.x == 0) *loss_out = (sm[0] + sm[1] + sm[2] + sm[3]) / (sm[4] + sm[5] + sm[6] + sm[7]);
+}
+int decode_loss(hipStream_t st, const float* lse, const float* label_logit, const int64_t* labels, const int64_t* loss_mask, int rows, float* loss_out) {
+  if (!lse || !label_logit || !labels || !loss_mask || !loss_out || rows < 1) return RL_ERR_ARG;
+  hipLaunchKernelGGL(decode_loss_kernel, dim3(1), dim3(256), 0, st, lse, label_logit, labels, loss_mask, rows, loss_out);
+  return RL_LAUNCH_CHECK();
+}
+
 template <typename T>
 __global__ void __launch_bounds__(256)
 cast_transpose_kernel(const float* __restrict__ src, int R, int C, T* __restrict__ dst, T* __restrict__ dstT) {

@@ -28,6 +28,8 @@ from .init import tensor_init, tensor_specs, synth_glyph_table
 # compute_dtype -> (C ABI dtype, tensor dtype).  "bf16x3": fp32 tensors everywhere; the Linear GEMMs multiply split-bf16 (three bf16
 # MFMAs per product, fp32 accumulation), convolutions and attention stay exact fp32.
 _DTYPES = {"bf16": (_capi.BF16, torch.bfloat16), "fp32": (_capi.F32, torch.float32), "bf16x3": (_capi.F32_BF16X3, torch.float32)}
+# what RealiseModule.predict returns: ids / probs / logits [B, S, k], lse [B, S], loss (0-d or None)
+Prediction = collections.namedtuple("Prediction", ["ids", "probs", "logits", "lse", "loss"])
 _AR_TRAIN, _AR_UNUSED, _AR_FROZEN, _AR_BUF_F32, _AR_BUF_I64 = range(5)
 
 
@@ -503,6 +505,40 @@ class RealiseModule(nn.Module):
         return t.to(device=self.device, dtype=torch.int64).contiguous()
 
     def forward(self, batch):
+        return self._forward(batch, 0)
+
+    @torch.no_grad()
+    def predict(self, batch, topk=1):
+        """Inference without logits: ``Prediction(ids [B, S, k] int64, probs [B, S, k], logits [B, S, k], lse [B, S], loss)`` - the
+        best ``topk`` (1..4) corrections of every position, best first (ties: the lower id, as ``decode``), their softmax
+        probabilities and logits, the log-sum-exp over the vocabulary, and the evaluation loss (0-d, or None without ``tgt_idx``).
+        The classifier GEMM's epilogue reduces its tiles to candidates and softmax partials (``realise_gemm_nt_decode``): no
+        [B, S, V] tensor is allocated, written or read.  ``ids[..., 0]`` equals ``decode(forward(batch)[-1])`` and
+        ``logits[..., 0]`` the row maximum of the default forward's logits, bit for bit.  Evaluation mode only."""
+        if self.training:
+            raise RuntimeError("predict() needs a module in evaluation mode: call model.eval() first")
+        k = int(topk)
+        if k < 1 or k > 4:
+            raise ValueError("topk must be 1..4")
+        return self._forward(batch, k)
+
+    def _decode_buffers(self, B, S, k):
+        """outputs + record scratch of predict(), allocated once per (B, S, k) and kept"""
+        cache = self.__dict__.setdefault("_predict_bufs", {})
+        key = (B, S, k)
+        if key not in cache:
+            lib = _capi.load()
+            H, V = self.config.hidden_size, self.vocab_size
+            need = lib.realise_gemm_nt_decode_scratch_bytes(_DTYPES[self.compute_dtype][0], B * S, V, H, k)
+            if need <= 0:
+                raise RuntimeError("predict(): the decode GEMM refuses B * S = %d, V = %d, H = %d, topk = %d" % (B * S, V, H, k))
+            f32 = dict(dtype=torch.float32, device=self.device)
+            cache[key] = dict(ids=torch.empty((B, S, k), dtype=torch.int64, device=self.device), probs=torch.empty((B, S, k), **f32),
+                              logits=torch.empty((B, S, k), **f32), lse=torch.empty((B, S), **f32), label=torch.zeros((B, S), **f32),
+                              scratch=torch.empty(need, dtype=torch.uint8, device=self.device))
+        return cache[key]
+
+    def _forward(self, batch, topk):
         self._raise_on_bad_ids()
         src = self._dev(batch["src_idx"])
         B, S = src.shape
@@ -570,6 +606,23 @@ class RealiseModule(nn.Module):
         no_logits = (need_grad and not self.train_logits and self.compute_dtype == "bf16" and self.vocab_size % 8 == 0
                      and self.vocab_size <= 22528 and B * S <= 65536)
         loss = torch.zeros((), dtype=torch.float32, device=self.device) if tgt is not None else None
+        if topk:
+            # predict(): the decode request is installed for this one call and cleared behind it, whatever happens
+            bufs = self._decode_buffers(B, S, topk)
+            req = _capi.Decode()
+            req.k, req.ids, req.values, req.probs, req.lse = topk, bufs["ids"].data_ptr(), bufs["logits"].data_ptr(), bufs["probs"].data_ptr(), bufs["lse"].data_ptr()
+            req.label_logit, req.scratch, req.scratch_bytes = bufs["label"].data_ptr(), bufs["scratch"].data_ptr(), bufs["scratch"].numel()
+            cb.logits_out = None
+            cb.loss_out = loss.data_ptr() if loss is not None else None
+            lib = _capi.load()
+            lib.realise_engine_set_decode(self._engine, C.byref(req))
+            try:
+                _capi.check(lib.realise_engine_forward(self._engine, self._stream(), C.byref(cb)), "realise_engine_forward (predict)")
+            finally:
+                lib.realise_engine_set_decode(self._engine, None)
+            self._last = keep
+            self._gate_gen = self._fwd_gen
+            return Prediction(bufs["ids"].clone(), bufs["probs"].clone(), bufs["logits"].clone(), bufs["lse"].clone(), loss)
         if no_logits:
             logits = None
             cb.logits_out = None

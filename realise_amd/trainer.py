@@ -165,13 +165,15 @@ def train(model, items, *, batch_size=64, max_seq_length=128, epochs=1, lr=5e-5,
 
 @torch.no_grad()
 def evaluate(model, items, *, batch_size=64, max_seq_length=128, device="cuda", build_batch=None, tokenizer=None,
-             vocab_path=None, label_path=None, output_dir=None, prefix="", live_rows=False):
+             vocab_path=None, label_path=None, output_dir=None, prefix="", live_rows=False, fused_decode=False):
     """run.py:239-280: mean eval loss and the arg-max ids.  The arg-max runs on the device (``model.decode``), so only
     [B, S] ids cross PCIe instead of the [B, S, 21128] logits.  With ``vocab_path`` + ``label_path`` + ``output_dir`` the
     predictions are also written as ``preds.txt`` / ``labels.txt`` and scored like the reference (``results`` dict).
     ``live_rows=True``: the forwards skip the padding rows behind every sentence's last attended position (``model.eval_live_rows``:
     -12 % per forward at B = 64, S = 128) - the loss and the ids of the real tokens, all the scorer reads (it cuts at ``lengths``), are
-    unchanged; the ids returned for padding positions are then arbitrary."""
+    unchanged; the ids returned for padding positions are then arbitrary.
+    ``fused_decode=True``: every batch goes through ``model.predict`` - the arg-max and the loss leave the classifier kernel itself and
+    no [B, S, V] logits tensor exists at any point; the default is the forward + ``decode`` path."""
     from .metric import Metric
     build_batch = build_batch or type(model).build_batch
     model.eval()
@@ -186,10 +188,14 @@ def evaluate(model, items, *, batch_size=64, max_seq_length=128, device="cuda", 
         model.eval_live_rows = bool(live_rows)
     try:
         for batch in data_helper(items, batch_size, max_seq_length, build_batch, tokenizer, is_eval=True):
-            with torch.no_grad():
-                loss, logits = model(batch)[:2]
+            if fused_decode:
+                pred = model.predict(batch)
+                loss, ids = pred.loss, pred.ids[..., 0].cpu()
+            else:
+                with torch.no_grad():
+                    loss, logits = model(batch)[:2]
+                ids = model.decode(logits).cpu()
             losses.append(loss.detach())
-            ids = model.decode(logits).cpu()
             preds.append(ids)
             if label_path is not None:
                 batch["src_idx"] = batch["src_idx"].cpu().numpy()
