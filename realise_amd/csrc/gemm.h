@@ -104,11 +104,11 @@ template <typename T> struct EpiParams {
 };
 
 // ---- operand loaders ---------------------------------------------------------------------------
-// A loader maps (row, k) of a logical K-contiguous operand to the global address of a 16-byte chunk
-// (or to a zero page when out of range), for direct-to-LDS staging.  Ctx = per-row state, KPos =
-// per-column state that is advanced incrementally from K-tile to K-tile (no integer divisions in
-// the main loop).
+// A loader maps (row, k) of a logical K-contiguous operand to the source of a 16-byte chunk for direct-to-LDS staging; kDense tells
+// the kernels which of the two interfaces it has.  DenseLoader: a 64-bit global address (or a zero page when out of range); Ctx =
+// per-row state, KPos = per-column state.  ConvLoader: a 32-bit buffer offset (Row32 / Tap32 / voff32, below).
 template <typename T> struct DenseLoader {
+  static constexpr bool kDense = true;
   const T* base;
   int64_t ld;
   int rows, K;
@@ -131,6 +131,7 @@ template <typename T> struct DenseLoader {
 // mode 1: data-gradient gather, source pixel ((y + pad - kh)/stride, ...) when divisible.
 // img_index (optional) redirects image n to table row img_index[n] (glyph lookup by token id).
 template <typename T> struct ConvLoader {
+  static constexpr bool kDense = false;
   const T* src;
   const int64_t* img_index;
   int rows, Hr, Wr, Hs, Ws, C, KH, KW, stride, pad, mode, K;
@@ -147,7 +148,7 @@ template <typename T> struct ConvLoader {
     }
     return images * per < 0xFFFFFE00ll;
   }
-  // Parity-class form of a stride-2 data gradient (mode 1, 32-bit addressing only): par = 2*py + px in 0..3 restricts the rows to the
+  // Parity-class form of a stride-2 data gradient (mode 1): par = 2*py + px in 0..3 restricts the rows to the
   // input pixels (2*yy + py, 2*xx + px) - rows = N * Hr/2 * Wr/2 - and K to the taps that can reach such a pixel,
   // kh = kh0 + 2i < KH with kh0 = (py + pad) & 1 (3x3 pad 1: one tap for an even coordinate, two for an odd one), so no fetched tap
   // is a stride miss: 1 + 2 + 2 + 4 = 9 tap-GEMMs over a quarter of the rows each instead of 9 over all rows (4x less work).
@@ -156,8 +157,6 @@ template <typename T> struct ConvLoader {
   int tap_sel = -1;                                // class reduced to ONE tap kh * KW + kw (a 2x2 map under a 1x1 output: pixel (y, x) is
                                                    // reached by tap (y + pad, x + pad) only); the B operand then points at that tap's slot
   int kh0 = 0, kw0 = 0, nkw = 1, kstep = 1;        // set by finalize()
-  struct Ctx { const T* img; int y, x; };
-  struct KPos { int kh, kw, ch, k; };
   __device__ __forceinline__ void clamp_rows() { if (rows_dev != nullptr) rows = min(rows, par >= 0 ? (*rows_dev >> 2) : *rows_dev); }
   void finalize() {
     K = KH * KW * C;
@@ -176,37 +175,10 @@ template <typename T> struct ConvLoader {
       w_shift = 0; while ((1 << w_shift) < Wr) ++w_shift;
     }
   }
-  __device__ __forceinline__ Ctx prepare(int row) const {
-    Ctx c; c.img = nullptr; c.y = 0; c.x = 0;
-    if (row < rows) {
-      int n, rem;
-      if (hw_shift >= 0) {
-        n = row >> hw_shift; rem = row & ((1 << hw_shift) - 1);
-        c.y = rem >> w_shift; c.x = rem & ((1 << w_shift) - 1);
-      } else {
-        const int hw = Hr * Wr;
-        n = row / hw; rem = row - n * hw;
-        c.y = rem / Wr; c.x = rem - c.y * Wr;
-      }
-      const int64_t ns = img_index ? img_index[n] : (int64_t)n;
-      c.img = src + ns * Hs * Ws * C;
-    }
-    return c;
-  }
-  __device__ __forceinline__ KPos kpos(int k) const {
-    KPos q; q.k = k;
-    const int tap = k / C;
-    q.ch = k - tap * C; q.kh = tap / KW; q.kw = tap - q.kh * KW;
-    return q;
-  }
-  __device__ __forceinline__ void advance(KPos& q, int dk) const {
-    q.k += dk; q.ch += dk;
-    while (q.ch >= C) { q.ch -= C; if (++q.kw == KW) { q.kw = 0; ++q.kh; } }
-  }
   // ---- 32-bit addressing for raw-buffer LDS-DMA fetches (one VGPR offset per fetch, the descriptor in SGPRs).  A row keeps the
   // byte offset of its ANCHOR pixel (the tap-(0,0) source pixel, possibly inside the zero padding; arithmetic is mod 2^32) and the
   // anchor's coordinates; a lane keeps its current tap (kh, kw, channel) and the tap's byte offset relative to the anchor.  Per
-  // fetch: two adds, two unsigned compares, one select - instead of a 64-bit address recomputed from (n, y, x, kh, kw) each time.
+  // fetch: two adds, two unsigned compares, one select - no 64-bit address, no integer division in the main loop.
   // A fetch that must read zeros (padding, row / K tails, stride-2 parity misses) gets an offset beyond num_records: the buffer
   // range check returns zeros.
   static constexpr uint32_t OOB = 0xFFFFFF00u;          // with num_records = RECORDS below
@@ -280,25 +252,6 @@ template <typename T> struct ConvLoader {
     const int sy = ty / stride, sx = tx / stride;
     const bool ok = ty >= 0 && tx >= 0 && sy * stride == ty && sx * stride == tx && sy < Hs && sx < Ws;
     return ok ? r.off + (uint32_t)((sy * Ws + sx) * C * (int)sizeof(T)) + q.toff : OOB;
-  }
-  __device__ __forceinline__ const void* addr(const Ctx& c, const KPos& q, const void* zero) const {
-    if (c.img == nullptr || q.k >= K) return zero;
-    int sy, sx;
-    if (mode == 0) {
-      sy = c.y * stride + q.kh - pad; sx = c.x * stride + q.kw - pad;
-    } else {
-      const int ty = c.y + pad - q.kh, tx = c.x + pad - q.kw;
-      if (ty < 0 || tx < 0) return zero;
-      if (stride == 2) {
-        if ((ty | tx) & 1) return zero;
-        sy = ty >> 1; sx = tx >> 1;
-      } else {
-        sy = ty / stride; sx = tx / stride;
-        if (sy * stride != ty || sx * stride != tx) return zero;
-      }
-    }
-    if (sy < 0 || sy >= Hs || sx < 0 || sx >= Ws) return zero;
-    return (const void*)(c.img + ((int64_t)(sy * Ws + sx) * C + q.ch));
   }
 };
 

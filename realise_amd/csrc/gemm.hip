@@ -81,17 +81,17 @@ gemm_nt_kernel(ALoader la, DenseLoader<T> lb, int M, int N, int K, int tiles_n, 
   const int lrow = lane >> 3;                        // row inside the 8-row group written by one instruction
   const int kchunk = ((lane & 7) ^ lrow) * G::VEC;   // logical K offset of the chunk this lane fetches
 
-  constexpr bool kDenseA = sizeof(typename ALoader::KPos) == sizeof(typename DenseLoader<T>::KPos);
-  typename ALoader::Ctx actx[kDenseA ? NA : 1];
-  typename DenseLoader<T>::Ctx bctx[NB];
+  constexpr bool kDenseA = ALoader::kDense;
+  // dense A operand (ALoader = DenseLoader<T>): the same per-row / per-column state as B
+  typename DenseLoader<T>::Ctx actx[kDenseA ? NA : 1], bctx[NB];
+  typename DenseLoader<T>::KPos aq = {}, bq = lb.kpos(kchunk);
   if constexpr (kDenseA) {
 #pragma unroll
     for (int j = 0; j < NA; ++j) actx[j] = la.prepare(m0 + (wave * NA + j) * 8 + lrow);
+    aq = la.kpos(kchunk);
   }
 #pragma unroll
   for (int j = 0; j < NB; ++j) bctx[j] = lb.prepare(n0 + (wave * NB + j) * 8 + lrow);
-  typename ALoader::KPos aq = la.kpos(kchunk);
-  typename DenseLoader<T>::KPos bq = lb.kpos(kchunk);
   // gathered (implicit-im2col) A operand: 32-bit buffer addressing, see ConvLoader::Row32 / Tap32
   ConvRows<ALoader, NA> crow;
   if constexpr (!kDenseA) crow.init(la, m0 + wave * NA * 8 + lrow, kchunk);
@@ -283,31 +283,79 @@ void set_nt_variant(int v) { g_nt_variant = (v == 9 || v == 12 || v == 14 || v =
 static int g_tn_split = 0;
 void set_tn_split(int n) { g_tn_split = n; }
 
-template <typename T, typename ALoader, int WM, int WN, int NSTAGE = 2, int NF = 4, bool SPREAD = false, bool X3 = false, int DEC = 0>
+// One kernel instantiation KERN: raise its dynamic-LDS limit to lds_attr on the first call, then launch it (RL_LAUNCH: inside an open
+// ProfScope the dispatch carries the scope's events).
+template <auto KERN, typename... Args>
+static void launch_lds(int lds_attr, dim3 grid, dim3 block, size_t lds, hipStream_t st, const Args&... args) {
+  static bool attr_set = false;
+  if (!attr_set) { (void)hipFuncSetAttribute((const void*)KERN, hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr); attr_set = true; }
+  RL_LAUNCH(KERN, grid, block, lds, st, args...);
+}
+
+// The 4-wave NT tiles: NtPath -> (WM, WN, NSTAGE, NF, SPREAD), 64 WM rows x 16 NF WN columns.  The launches (launch_nt_4w), the
+// cost rule (nt_cost_path) and the decode slab count (nt_decode_slabs) all read the tile from here.
+template <int PATH> struct NtTile;
+template <int WM_, int WN_, int NSTAGE_, int NF_, bool SPREAD_> struct NtTileOf {
+  static constexpr int WM = WM_, WN = WN_, NSTAGE = NSTAGE_, NF = NF_, BM = 64 * WM_, BN = 16 * NF_ * WN_;
+  static constexpr bool SPREAD = SPREAD_;
+};
+template <> struct NtTile<NT_PATH_4W_256x64> : NtTileOf<4, 1, 2, 4, false> {};
+template <> struct NtTile<NT_PATH_4W_128x128> : NtTileOf<2, 2, 2, 4, false> {};
+template <> struct NtTile<NT_PATH_4W_128x96> : NtTileOf<2, 2, 2, 3, false> {};
+template <> struct NtTile<NT_PATH_4W_256x128> : NtTileOf<4, 2, 3, 4, true> {};      // 8 waves, three stages, fetches spread
+
+template <typename T, typename ALoader, int PATH, bool X3, int DEC>
 static int launch_nt_tile(hipStream_t st, const ALoader& la, const DenseLoader<T>& lb, int M, int N, int K, const EpiParams<T>& ep) {
-  constexpr int BM_ = 64 * WM, BN_ = 16 * NF * WN;
+  typedef NtTile<PATH> Tl;
+  constexpr int BM_ = Tl::BM, BN_ = Tl::BN;
   const int tiles_m = (M + BM_ - 1) / BM_, tiles_n = (N + BN_ - 1) / BN_;
   const int ntiles = tiles_m * tiles_n;
-  const size_t ring = NSTAGE * (size_t)(BM_ + BN_) * 128, etile = (size_t)WM * WN * 64 * (16 * NF + 4) * 4;
+  const size_t ring = Tl::NSTAGE * (size_t)(BM_ + BN_) * 128, etile = (size_t)Tl::WM * Tl::WN * 64 * (16 * Tl::NF + 4) * 4;
   const size_t lds = ring > etile ? ring : etile;        // the epilogue re-uses the ring as per-wave transpose tiles
-  static bool attr_set = false;
-  if (!attr_set) {
-    (void)hipFuncSetAttribute((const void*)gemm_nt_kernel<T, ALoader, WM, WN, NSTAGE, NF, SPREAD, X3, DEC>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
-    attr_set = true;
-  }
-  ProfScope ps(st, sizeof(typename ALoader::KPos) == sizeof(typename DenseLoader<T>::KPos) ? PK_GEMM_NT : PK_CONV_NT, 2.0 * M * N * K);
-  if constexpr (sizeof(typename ALoader::KPos) == sizeof(typename DenseLoader<T>::KPos))      // (the conv families are scaled by the live-glyph fraction in bench.py)
+  ProfScope ps(st, ALoader::kDense ? PK_GEMM_NT : PK_CONV_NT, 2.0 * M * N * K);
+  if constexpr (ALoader::kDense)      // (the conv families are scaled by the live-glyph fraction in bench.py)
     if (la.rows_dev != nullptr) prof_set_exec(la.rows_dev, 2.0 * N * K, BM_, M);   // device-side row bound: surplus tiles exit at once
   EpiParams<T> epp = ep;
   epp.wide = (N % 8 == 0) && (ep.ldo % 8 == 0) && (ep.aux == nullptr || ep.ldaux % 8 == 0);
-  RL_LAUNCH((gemm_nt_kernel<T, ALoader, WM, WN, NSTAGE, NF, SPREAD, X3, DEC>), dim3(ntiles), dim3(64 * WM * WN), lds, st, la, lb, M, N, K, tiles_n, ntiles, epp);
+  launch_lds<gemm_nt_kernel<T, ALoader, Tl::WM, Tl::WN, Tl::NSTAGE, Tl::NF, Tl::SPREAD, X3, DEC>>(
+      (int)lds, dim3(ntiles), dim3(64 * Tl::WM * Tl::WN), lds, st, la, lb, M, N, K, tiles_n, ntiles, epp);
   return hipGetLastError() == hipSuccess ? RL_OK : RL_ERR_LAUNCH;
 }
+// The instantiations that exist: X3 for fp32 only (the callers), no decode form of the 256-row tiles, the 256 x 128 tile for exact
+// dense bf16 only.  Anything else is refused.
+template <typename T, typename ALoader, bool X3, int DEC>
+static int launch_nt_4w_mma(hipStream_t st, int path, const ALoader& la, const DenseLoader<T>& lb, int M, int N, int K, const EpiParams<T>& ep) {
+  switch (path) {
+    case NT_PATH_4W_128x128: return launch_nt_tile<T, ALoader, NT_PATH_4W_128x128, X3, DEC>(st, la, lb, M, N, K, ep);
+    case NT_PATH_4W_128x96: return launch_nt_tile<T, ALoader, NT_PATH_4W_128x96, X3, DEC>(st, la, lb, M, N, K, ep);
+    case NT_PATH_4W_256x64:
+      if constexpr (DEC == 0) return launch_nt_tile<T, ALoader, NT_PATH_4W_256x64, X3, DEC>(st, la, lb, M, N, K, ep);
+      break;
+    case NT_PATH_4W_256x128:
+      if constexpr (DEC == 0 && !X3 && ALoader::kDense && sizeof(T) == 2) return launch_nt_tile<T, ALoader, NT_PATH_4W_256x128, X3, DEC>(st, la, lb, M, N, K, ep);
+      break;
+    default: break;
+  }
+  return RL_ERR_ARG;
+}
+// exact, or bf16x3 where EpiParams::x3 asks for it (fp32, dense operands; a gathered launch ignores it)
+template <typename T, typename ALoader, int DEC>
+static int launch_nt_4w(hipStream_t st, int path, const ALoader& la, const DenseLoader<T>& lb, int M, int N, int K, const EpiParams<T>& ep) {
+  if constexpr (ALoader::kDense && sizeof(T) == 4) {
+    if (ep.x3) return launch_nt_4w_mma<T, ALoader, true, DEC>(st, path, la, lb, M, N, K, ep);
+  }
+  return launch_nt_4w_mma<T, ALoader, false, DEC>(st, path, la, lb, M, N, K, ep);
+}
 
-static double nt_tile_cost(int M, int N, int bn) {       // the tile-width rule of nt_path (below)
-  const long tiles = (long)((M + 127) / 128) * ((N + bn - 1) / bn);
+// The tile-width rule of nt_path (below): 128 or 96 columns, whichever minimises  width x f(tiles per CU).
+template <int PATH> static double nt_tile_cost(int M, int N) {
+  typedef NtTile<PATH> Tl;
+  const long tiles = (long)((M + Tl::BM - 1) / Tl::BM) * ((N + Tl::BN - 1) / Tl::BN);
   const long tpc = (tiles + 255) / 256;
-  return bn * (tpc == 1 ? 1.0 : 0.75 * (double)tpc);
+  return Tl::BN * (tpc == 1 ? 1.0 : 0.75 * (double)tpc);
+}
+static int nt_cost_path(int M, int N) {
+  return (g_nt_n96 && nt_tile_cost<NT_PATH_4W_128x96>(M, N) < nt_tile_cost<NT_PATH_4W_128x128>(M, N)) ? NT_PATH_4W_128x96 : NT_PATH_4W_128x128;
 }
 // Which kernel a launch reaches: ONE pure host function of the shape, the epilogue and the knobs (g_nt_variant, g_nt_n96), called by
 // launch_nt itself and exported as realise_debug_nt_path (NtPath, gemm.h) so that a test can pin the choice it relies on.
@@ -320,7 +368,6 @@ static int nt_path(bool dense, bool rows_dev, int M, int N, int K, const EpiPara
   // minimise  width x f(tiles per CU)  with f(1) = 1 and f(n) = 0.75 n (two co-resident tiles overlap each other's
   // stalls): e.g. M = 8192, N = 768 -> 8 x 96 columns = 512 tiles, two per CU on every CU, instead of 384 tiles of
   // 128 columns (half the CUs run two, half run one): +25 % measured (tools/nt_probe.cpp, n96 knob).
-  auto cost = [&](int bn) { return nt_tile_cost(M, N, bn); };
   if constexpr (sizeof(T) == 2) {
     if (dense) {
       // Production path for the big dense GEMMs: the ping-pong 8-wave kernel (gemm_nt8.hip), tile by chip fill.  Variants 12 / 14 / 16
@@ -355,13 +402,12 @@ static int nt_path(bool dense, bool rows_dev, int M, int N, int K, const EpiPara
       if ((long)((M + 127) / 128) * ((N + 127) / 128) >= 4096 && (K % Geo<T>::BK) == 0) return NT_PATH_4W_256x128;
     }
   }
-  if (g_nt_n96 && cost(96) < cost(128)) return NT_PATH_4W_128x96;
-  return NT_PATH_4W_128x128;
+  return nt_cost_path(M, N);
 }
 
 template <typename T, typename ALoader>
 static int launch_nt(hipStream_t st, const ALoader& la, const T* B, int64_t ldb, int M, int N, int K, const EpiParams<T>& ep) {
-  constexpr bool kDense = sizeof(typename ALoader::KPos) == sizeof(typename DenseLoader<T>::KPos);
+  constexpr bool kDense = ALoader::kDense;
   int64_t lda = 0;
   if constexpr (kDense) lda = la.ld;
   const int path = nt_path<T>(kDense, la.rows_dev != nullptr, M, N, K, ep, lda, ldb);
@@ -383,26 +429,10 @@ static int launch_nt(hipStream_t st, const ALoader& la, const T* B, int64_t ldb,
         e2.m_dev = la.rows_dev; e2.m_exact = 1;
         return gemm_nt8(st, la.base, la.ld, B, ldb, M, N, K, e2, 0);
       }
-      case NT_PATH_4W_256x128: return launch_nt_tile<T, ALoader, 4, 2, 3, 4, true>(st, la, lb, M, N, K, ep);
       default: break;
     }
   }
-  if constexpr (kDense && sizeof(T) == 4) {      // bf16x3: the same three tiles, multiplied by MmaBF16x3
-    if (ep.x3) {
-      switch (path) {
-        case NT_PATH_4W_256x64: return launch_nt_tile<T, ALoader, 4, 1, 2, 4, false, true>(st, la, lb, M, N, K, ep);
-        case NT_PATH_4W_128x96: return launch_nt_tile<T, ALoader, 2, 2, 2, 3, false, true>(st, la, lb, M, N, K, ep);
-        case NT_PATH_4W_128x128: return launch_nt_tile<T, ALoader, 2, 2, 2, 4, false, true>(st, la, lb, M, N, K, ep);
-        default: return RL_ERR_ARG;
-      }
-    }
-  }
-  switch (path) {
-    case NT_PATH_4W_256x64: return launch_nt_tile<T, ALoader, 4, 1>(st, la, lb, M, N, K, ep);
-    case NT_PATH_4W_128x96: return launch_nt_tile<T, ALoader, 2, 2, 2, 3>(st, la, lb, M, N, K, ep);
-    case NT_PATH_4W_128x128: return launch_nt_tile<T, ALoader, 2, 2>(st, la, lb, M, N, K, ep);
-    default: return RL_ERR_ARG;
-  }
+  return launch_nt_4w<T, ALoader, 0>(st, path, la, lb, M, N, K, ep);
 }
 
 // the argument checks of gemm_nt, then the choice of launch_nt (dense operands)
@@ -445,16 +475,17 @@ int gemm_nt_decode_path(int M, int N, int K, int64_t lda, int64_t ldb, int k, in
   const int p = nt_path<T>(true, false, M, N, K, ep, lda, ldb);
   if (p == NT_PATH_REFUSED || p == NT_PATH_NONE) return NT_PATH_REFUSED;
   if ((p == NT_PATH_8P && k == 1) || p == NT_PATH_4W_128x128 || p == NT_PATH_4W_128x96) return p;
-  return (g_nt_n96 && nt_tile_cost(M, N, 96) < nt_tile_cost(M, N, 128)) ? NT_PATH_4W_128x96 : NT_PATH_4W_128x128;
+  return nt_cost_path(M, N);
 }
 template int gemm_nt_decode_path<bf16_t>(int, int, int, int64_t, int64_t, int, int);
 template int gemm_nt_decode_path<float>(int, int, int, int64_t, int64_t, int, int);
 // slabs per row: one per wave along N - 96 columns on the persistent tile (192 x 2 waves), 64 / 48 on the 4-wave tiles
+template <int PATH> static int nt_tile_slabs(int N) { return ((N + NtTile<PATH>::BN - 1) / NtTile<PATH>::BN) * NtTile<PATH>::WN; }
 int nt_decode_slabs(int path, int N) {
   switch (path) {
     case NT_PATH_8P: return ((N + 191) / 192) * 2;
-    case NT_PATH_4W_128x128: return ((N + 127) / 128) * 2;
-    case NT_PATH_4W_128x96: return ((N + 95) / 96) * 2;
+    case NT_PATH_4W_128x128: return nt_tile_slabs<NT_PATH_4W_128x128>(N);
+    case NT_PATH_4W_128x96: return nt_tile_slabs<NT_PATH_4W_128x96>(N);
     default: return 0;
   }
 }
@@ -476,23 +507,13 @@ int gemm_nt_decode(hipStream_t st, const T* A, int64_t lda, const T* B, int64_t 
   ep.dec.labels = labels; ep.dec.label_logit = labels ? d.label_logit : nullptr;
   DenseLoader<T> la{A, lda, M, K};
   DenseLoader<T> lb{B, ldb, N, K};
-  typedef DenseLoader<T> DL;
   int rc = RL_ERR_ARG;
-  const bool one = ep.dec.kc == 1, n96 = path == NT_PATH_4W_128x96;
-  if constexpr (sizeof(T) == 2) {
-    if (path == NT_PATH_8P) rc = gemm_nt8p_decode(st, A, lda, B, ldb, M, N, K, ep);
-  }
-  if (path != NT_PATH_8P) {
-    if constexpr (sizeof(T) == 4) {
-      if (x3) {
-        rc = n96 ? (one ? launch_nt_tile<T, DL, 2, 2, 2, 3, false, true, 1>(st, la, lb, M, N, K, ep) : launch_nt_tile<T, DL, 2, 2, 2, 3, false, true, 4>(st, la, lb, M, N, K, ep))
-                 : (one ? launch_nt_tile<T, DL, 2, 2, 2, 4, false, true, 1>(st, la, lb, M, N, K, ep) : launch_nt_tile<T, DL, 2, 2, 2, 4, false, true, 4>(st, la, lb, M, N, K, ep));
-      }
-    }
-    if (!x3) {
-      rc = n96 ? (one ? launch_nt_tile<T, DL, 2, 2, 2, 3, false, false, 1>(st, la, lb, M, N, K, ep) : launch_nt_tile<T, DL, 2, 2, 2, 3, false, false, 4>(st, la, lb, M, N, K, ep))
-               : (one ? launch_nt_tile<T, DL, 2, 2, 2, 4, false, false, 1>(st, la, lb, M, N, K, ep) : launch_nt_tile<T, DL, 2, 2, 2, 4, false, false, 4>(st, la, lb, M, N, K, ep));
-    }
+  if (path == NT_PATH_8P) {
+    if constexpr (sizeof(T) == 2) rc = gemm_nt8p_decode(st, A, lda, B, ldb, M, N, K, ep);
+  } else if (ep.dec.kc == 1) {
+    rc = launch_nt_4w<T, DenseLoader<T>, 1>(st, path, la, lb, M, N, K, ep);
+  } else {
+    rc = launch_nt_4w<T, DenseLoader<T>, 4>(st, path, la, lb, M, N, K, ep);
   }
   if (rc != RL_OK) return rc;
   return decode_merge(st, ep.dec.rec, ep.dec.kc, ep.dec.nslab, M, d.k, d.ids, d.values, d.probs, d.lse);
@@ -632,17 +653,15 @@ __device__ __forceinline__ void tn_tile_body(const T* __restrict__ A, int64_t ld
   const int p_end = max(p_begin, min(Pe, p_begin + pchunk));
   const void* zero = (const void*)g_zero16;
   // live-tile list (unsplit dense reductions): the t-th tile of the loop is block tile_list[t] of the rows
-  constexpr bool kDenseB0 = sizeof(typename BLoader::KPos) == sizeof(typename DenseLoader<T>::KPos);
-  const bool listed = kDenseB0 && ep.tile_list != nullptr && nsplit == 1;
+  constexpr bool kDenseB = BLoader::kDense;
+  const bool listed = kDenseB && ep.tile_list != nullptr && nsplit == 1;
   // 16-row form of the list (bf16, 128 x 128 tiles: wave w fetches rows 16w .. 16w + 15 of both operand tiles): a reduction tile is
   // any FOUR live 16-row blocks, wave w takes block list[4 t + w] - 68 % instead of 84 % of the rows of a SIGHAN-shaped batch
   const bool sub16 = listed && ep.list_rows == 16 && sizeof(T) == 2 && WI == 2 && WJ == 2;
 
   // per-lane chunk coordinates are the same for every reduction tile: only the row base moves
-  constexpr bool kDenseB = sizeof(typename BLoader::KPos) == sizeof(typename DenseLoader<T>::KPos);
-  int apl[NA], bpl[NB];
+  int apl[NA], bpl[NB], bcol[NB];
   const T* acol[NA];
-  typename BLoader::KPos bq[NB];
   bool bok[NB];
   ConvTaps<BLoader, NB> ctap;          // gathered B operand: the lane's tap per piece is fixed, the row moves (32-bit buffer addressing)
 #pragma unroll
@@ -658,8 +677,8 @@ __device__ __forceinline__ void tn_tile_body(const T* __restrict__ A, int64_t ld
     bpl[q] = off / RPB;
     const int col = j0 + ((off % RPB) ^ tn_swz<T, RPB>(bpl[q])) / (int)sizeof(T);
     bok[q] = col < J;
-    bq[q] = lb.kpos(bok[q] ? col : 0);
-    if constexpr (!kDenseB) ctap.set(lb, q, bok[q] ? col : 0);
+    bcol[q] = bok[q] ? col : 0;
+    if constexpr (!kDenseB) ctap.set(lb, q, bcol[q]);
   }
   if constexpr (!kDenseB) ctap.init(lb);
 
@@ -695,11 +714,8 @@ __device__ __forceinline__ void tn_tile_body(const T* __restrict__ A, int64_t ld
   if constexpr (kDenseB) {
 #pragma unroll
     for (int q = 0; q < NB; ++q) {
-      const typename BLoader::Ctx c0 = lb.prepare(0);
-      const typename BLoader::Ctx c1 = lb.prepare(1);
-      const char* r0 = (const char*)lb.addr(c0, bq[q], zero);
-      const char* r1 = (const char*)lb.addr(c1, bq[q], zero);
-      const int64_t ldb_bytes = r1 - r0;                                       // row pitch of the dense B operand
+      const char* r0 = (const char*)(lb.base + bcol[q]);                       // row 0 of the lane's column
+      const int64_t ldb_bytes = lb.ld * (int64_t)sizeof(T);                    // row pitch of the dense B operand
       pb[q] = bok[q] ? r0 + (int64_t)(p_begin + (sub16 ? bpl[q] - 16 * wave : bpl[q])) * ldb_bytes : (const char*)zero;
       incb[q] = bok[q] ? (int64_t)BP * ldb_bytes : 0;
     }
@@ -1066,28 +1082,21 @@ static int launch_tn_tile(hipStream_t st, const T* A, int64_t lda, const BLoader
   const int lds_attr = (int)(2 * (size_t)G::BP * (BI + BJ) * sizeof(T)) + TN_LIST_LDS_MAX;
   dim3 grid(ntiles * nsplit);
   {
-    ProfScope ps(st, sizeof(typename BLoader::KPos) == sizeof(typename DenseLoader<T>::KPos) ? PK_GEMM_TN : PK_CONV_TN, 2.0 * P * I * J);
-    if constexpr (sizeof(typename BLoader::KPos) == sizeof(typename DenseLoader<T>::KPos))
+    ProfScope ps(st, BLoader::kDense ? PK_GEMM_TN : PK_CONV_TN, 2.0 * P * I * J);
+    if constexpr (BLoader::kDense)
       if (lb.rows_dev != nullptr) prof_set_exec(lb.rows_dev, 2.0 * I * J, G::BP, P);       // the reduction stops at the device-side row bound
-    constexpr bool kDenseB = sizeof(typename BLoader::KPos) == sizeof(typename DenseLoader<T>::KPos);
-    bool x3_done = false;
-    if constexpr (kDenseB && sizeof(T) == 4) {
-      if (ep.x3) {
-        static bool a3 = false;
-        if (!a3) { (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<T, BLoader, false, WI, WJ, true>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr); a3 = true; }
-        RL_LAUNCH((gemm_tn_kernel<T, BLoader, false, WI, WJ, true>), grid, dim3(256), lds, st, A, lda, lb, P, I, J, tiles_j, ntiles, nsplit, pchunk, how, ep);
-        x3_done = true;
-      }
-    }
-    if (x3_done) {
-    } else if (sizeof(T) == 2 && g_tn_tr) {
-      static bool a1 = false;
-      if (!a1) { (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<T, BLoader, true, WI, WJ>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr); a1 = true; }
-      RL_LAUNCH((gemm_tn_kernel<T, BLoader, true, WI, WJ>), grid, dim3(256), lds, st, A, lda, lb, P, I, J, tiles_j, ntiles, nsplit, pchunk, how, ep);
+    constexpr std::true_type yes;
+    constexpr std::false_type no;
+    auto launch = [&](auto tr, auto x3) {
+      launch_lds<gemm_tn_kernel<T, BLoader, decltype(tr)::value, WI, WJ, decltype(x3)::value>>(
+          lds_attr, grid, dim3(256), lds, st, A, lda, lb, P, I, J, tiles_j, ntiles, nsplit, pchunk, how, ep);
+    };
+    if constexpr (sizeof(T) == 2) {             // transposed LDS reads, or 16-bit gathers (realise_set_tn_transpose_read)
+      if (g_tn_tr) launch(yes, no); else launch(no, no);
+    } else if constexpr (BLoader::kDense) {     // the exact fp32 atom, or bf16x3
+      if (ep.x3) launch(no, yes); else launch(no, no);
     } else {
-      static bool a2 = false;
-      if (!a2) { (void)hipFuncSetAttribute((const void*)gemm_tn_kernel<T, BLoader, false, WI, WJ>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr); a2 = true; }
-      RL_LAUNCH((gemm_tn_kernel<T, BLoader, false, WI, WJ>), grid, dim3(256), lds, st, A, lda, lb, P, I, J, tiles_j, ntiles, nsplit, pchunk, how, ep);
+      launch(no, no);
     }
     if (how == TN_OUT_SLAB) tn_fold_launch(st, ep, nsplit, I, J);
   }
@@ -1142,14 +1151,14 @@ int gemm_tn_group(hipStream_t st, int n, const TnGroupProblem<T>* probs, int P, 
   const int lds_attr = (int)(2 * (size_t)G::BP * 256 * sizeof(T)) + TN_LIST_LDS_MAX;
   ProfScope ps(st, PK_GEMM_TN, flops);
   if (grp.tile_list != nullptr) prof_set_exec(grp.n_tiles, flops / P * grp.list_rows, sizeof(T) == 2 && grp.list_rows == 16 ? 4 : 1, P / grp.list_rows);   // live blocks only
-#define RL_TN_GROUP(TRV, X3V) do { \
-    static bool attr = false; \
-    if (!attr) { (void)hipFuncSetAttribute((const void*)gemm_tn_group_kernel<T, TRV, X3V>, hipFuncAttributeMaxDynamicSharedMemorySize, lds_attr); attr = true; } \
-    RL_LAUNCH((gemm_tn_group_kernel<T, TRV, X3V>), dim3(total), dim3(256), lds, st, grp, P, pchunk); } while (0)
-  if (sizeof(T) == 2 && g_tn_tr) RL_TN_GROUP(true, false);
-  else if (sizeof(T) == 4 && grp.x3) RL_TN_GROUP(false, (sizeof(T) == 4));
-  else RL_TN_GROUP(false, false);
-#undef RL_TN_GROUP
+  const dim3 grid(total), block(256);
+  if constexpr (sizeof(T) == 2) {
+    if (g_tn_tr) launch_lds<gemm_tn_group_kernel<T, true, false>>(lds_attr, grid, block, lds, st, grp, P, pchunk);
+    else launch_lds<gemm_tn_group_kernel<T, false, false>>(lds_attr, grid, block, lds, st, grp, P, pchunk);
+  } else {
+    if (grp.x3) launch_lds<gemm_tn_group_kernel<T, false, true>>(lds_attr, grid, block, lds, st, grp, P, pchunk);
+    else launch_lds<gemm_tn_group_kernel<T, false, false>>(lds_attr, grid, block, lds, st, grp, P, pchunk);
+  }
   return hipGetLastError() == hipSuccess ? RL_OK : RL_ERR_LAUNCH;
 }
 template int gemm_tn_group<bf16_t>(hipStream_t, int, const TnGroupProblem<bf16_t>*, int, float, int, const int*, const int*, int, int);
