@@ -261,6 +261,16 @@ int realise_batchnorm_bwd_rows(void* stream, int dtype, const void* dy, const vo
 /* how many workspace plans the engine has installed (= whole-workspace zero fills) since it was created: a loop that alternates
  * batch shapes over per-shape workspace buffers (realise_engine_forget_workspace in realise_hip.h) must count one per shape */
 int64_t realise_engine_plan_installs(const realise_engine* e);
+/* Read-only: descriptor i of the engine's table of Linear weights and their operand copies (the CastDesc table the refresh and the
+ * AdamW sweep launch over), so that a test can find the copies a sweep wrote (tests/test_optim_edges_gpu.py).  src_off: element offset
+ * of the fp32 master W [R][C] inside the trainable parameter arena; dst_off / dstT_off: byte offsets inside the bound shadow buffer of
+ * the compute-dtype copies W [R][C] and W^T [C][ldT] (ldT >= R: the classifier's W^T is padded to a multiple of 64 columns, which
+ * stay zero), -1 for a copy the engine does not keep; group: 0 = the BERT stack's launch, 1 = classifier / head / pinyin and output
+ * stacks / GRU (tile ids restart per group).  Returns the number of descriptors (out may be NULL to ask for it alone), or
+ * -REALISE_ERR_ARG for a NULL engine, an index outside [0, count) with out != NULL, or before the engine has built the table (it does
+ * at its first forward / refresh). */
+typedef struct realise_cast_desc_info { int64_t src_off, dst_off, dstT_off; int32_t R, C, ldT, group; } realise_cast_desc_info;
+int realise_debug_engine_cast_desc(const realise_engine* e, int i, realise_cast_desc_info* out);
 
 
 #ifdef __cplusplus

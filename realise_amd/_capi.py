@@ -32,6 +32,12 @@ class Gate(C.Structure):
                 ("dbias", C.c_void_p), ("row_live", C.c_void_p), ("nsrc", C.c_int32)]
 
 
+class CastDescInfo(C.Structure):
+    """realise_cast_desc_info (include/realise_hip_debug.h)"""
+    _fields_ = [("src_off", C.c_int64), ("dst_off", C.c_int64), ("dstT_off", C.c_int64), ("R", C.c_int32), ("C", C.c_int32),
+                ("ldT", C.c_int32), ("group", C.c_int32)]
+
+
 class AdamwGroup(C.Structure):
     _fields_ = [("lr", C.c_float), ("beta1", C.c_float), ("beta2", C.c_float), ("eps", C.c_float), ("weight_decay", C.c_float),
                 ("correct_bias", C.c_int32)]
@@ -170,6 +176,7 @@ SYMBOLS = {
     "realise_engine_workspace_bytes": (_L, [_P, _I, _I, _I]),
     "realise_engine_forget_workspace": (None, [_P, _P]),
     "realise_engine_plan_installs": (_L, [_P]),
+    "realise_debug_engine_cast_desc": (_I, [_P, _I, C.POINTER(CastDescInfo)]),
     "realise_debug_tn_list_lds": (_I, [_L]),
     "realise_debug_tn_plan": (_I, [_I, _I, _I, _I, _I, _I, _I, _L, C.POINTER(TnPlan)]),
     "realise_gemm_tn_ex": (_I, [_P, _I, _P, _L, _P, _L, _I, _I, _I, _P, _L, _P, _L, _P, _F, _P, _P, _I, _I, _I, _I, _I]),

@@ -490,6 +490,7 @@ int realise_batchnorm_bwd_rows(void* stream, int dtype, const void* dy, const vo
                                 to_bn_branch<E>(xb, mean_b, rstd_b, gamma_b, dxb, dgamma_b, dbeta_b), sums, bn_rows(rows_dev, counts, hw, slots)));
 }
 int64_t realise_engine_plan_installs(const realise_engine* e) { return e ? e->impl->plan_install_count() : -1; }
+int realise_debug_engine_cast_desc(const realise_engine* e, int i, realise_cast_desc_info* out) { return e ? e->impl->cast_desc_info(i, out) : -RL_ERR_ARG; }
 void realise_engine_forget_workspace(realise_engine* e, void* workspace) { if (e) e->impl->forget_workspace(workspace); }
 int realise_engine_refresh_shadows(realise_engine* e, void* stream) { return e ? e->impl->refresh_shadows((hipStream_t)stream) : RL_ERR_ARG; }
 int realise_engine_refresh_shadows_ex(realise_engine* e, void* stream, int linear_current) {

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/realise_hip.h"
+#include "../../include/realise_hip_debug.h"
 
 namespace rl {
 struct AdamwGroups;
@@ -28,6 +29,7 @@ struct EngineBase {
   virtual int bind(void* shadow, void* workspace, int64_t bytes) = 0;
   virtual void forget_workspace(void* workspace) = 0;
   virtual int64_t plan_install_count() const = 0;
+  virtual int cast_desc_info(int i, ::realise_cast_desc_info* out) const = 0;   // realise_debug_engine_cast_desc
   virtual int refresh_shadows(hipStream_t st) = 0;
   virtual int refresh_shadows_ex(hipStream_t st, int skip_linear) = 0;
   virtual int adamw_step(hipStream_t st, float* m, float* v, const uint8_t* group_of_block, const struct AdamwGroups& gs, const float* norm_sq,

@@ -1237,6 +1237,17 @@ template <typename T> struct Engine : EngineBase {
   }
   int64_t plan_installs = 0;               // workspace zero fills so far (realise_engine_plan_installs: tests / bench count them)
   int64_t plan_install_count() const override { return plan_installs; }
+  int cast_desc_info(int i, realise_cast_desc_info* out) const override {
+    if (!descs_built || !sh) return -RL_ERR_ARG;
+    const int n = (int)desc_host.size();
+    if (out == nullptr) return n;
+    if (i < 0 || i >= n) return -RL_ERR_ARG;
+    const CastDesc& d = desc_host[i];
+    auto off = [&](const void* q) -> int64_t { return q ? (int64_t)((const char*)q - (const char*)sh) : -1; };
+    out->src_off = d.src - P; out->dst_off = off(d.dst); out->dstT_off = off(d.dstT);
+    out->R = d.R; out->C = d.C; out->ldT = d.ldT; out->group = i < n_descs_a ? 0 : 1;
+    return n;
+  }
   int install_plan(hipStream_t st, const Plan& p) {
     if (p.total > ws_bytes) { fprintf(stderr, "[realise_hip] workspace too small: need %lld have %lld\n", (long long)p.total, (long long)ws_bytes); return RL_ERR_ARG; }
     pl = p;

@@ -904,6 +904,24 @@ int sumsq_accum(hipStream_t st, const float* g, int64_t n, float* out) {
   return RL_LAUNCH_CHECK();
 }
 
+// One element of an AdamW step: the one statement of the arithmetic that every sweep kernel below shares (flat, grouped, chunk list,
+// LDS tile, register tile).  Contraction is switched off inside it: left to the compiler, each kernel fused its own choice of the
+// multiply-adds, and the register tile's p differed in the last bit from the LDS tile's (tests/test_optim_edges_gpu.py) although both
+// were documented as the same bits.  Every product and sum now rounds on its own, in every kernel alike.
+__device__ __forceinline__ void adamw_elem(float& p, float g, float& m, float& v, float clip, float lr, float beta1, float beta2,
+                                           float eps, float wd, float step_size) {
+#pragma clang fp contract(off)
+  const float gi = g * clip;
+  const float mi = m * beta1 + (1.0f - beta1) * gi;
+  const float vi = v * beta2 + (1.0f - beta2) * gi * gi;
+  float pi = p - step_size * (mi / (sqrtf(vi) + eps));
+  if (wd > 0.f) pi -= lr * wd * pi;                 // decoupled decay AFTER the update (optimization.py:162-167)
+  m = mi; v = vi; p = pi;
+}
+__device__ __forceinline__ void adamw_elem(float& p, float g, float& m, float& v, float clip, const AdamwGroup& h) {
+  adamw_elem(p, g, m, v, clip, h.lr, h.beta1, h.beta2, h.eps, h.weight_decay, h.step_size);
+}
+
 __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m, float* __restrict__ v,
                              int64_t n, float lr, float beta1, float beta2, float eps, float wd, float bc1, float bc2,
                              const float* __restrict__ norm_sq, float max_norm) {
@@ -914,11 +932,8 @@ __global__ void adamw_kernel(float* __restrict__ p, const float* __restrict__ g,
   }
   const float step_size = lr * sqrtf(bc2) / bc1;     // optimization.py:156-160
   for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
-    const float gi = g[i] * clip;
-    const float mi = m[i] * beta1 + (1.0f - beta1) * gi;
-    const float vi = v[i] * beta2 + (1.0f - beta2) * gi * gi;
-    float pi = p[i] - step_size * (mi / (sqrtf(vi) + eps));
-    if (wd > 0.f) pi -= lr * wd * pi;                 // decoupled decay AFTER the update (:162-167)
+    float pi = p[i], mi = m[i], vi = v[i];
+    adamw_elem(pi, g[i], mi, vi, clip, lr, beta1, beta2, eps, wd, step_size);
     m[i] = mi; v[i] = vi; p[i] = pi;
   }
 }
@@ -946,11 +961,8 @@ __global__ void adamw_grouped_kernel(float* __restrict__ p, const float* __restr
     if (gid >= gs.n) continue;
     if (skip_block != nullptr && skip_block[i >> 6]) continue;      // stepped by adamw_cast_multi_kernel (the Linear weights)
     const AdamwGroup h = gs.g[gid];
-    const float gi = g[i] * clip;
-    const float mi = m[i] * h.beta1 + (1.0f - h.beta1) * gi;
-    const float vi = v[i] * h.beta2 + (1.0f - h.beta2) * gi * gi;
-    float pi = p[i] - h.step_size * (mi / (sqrtf(vi) + h.eps));
-    if (h.weight_decay > 0.f) pi -= h.lr * h.weight_decay * pi;
+    float pi = p[i], mi = m[i], vi = v[i];
+    adamw_elem(pi, g[i], mi, vi, clip, h);
     m[i] = mi; v[i] = vi; p[i] = pi;
   }
 }
@@ -979,11 +991,8 @@ __global__ void __launch_bounds__(256) adamw_chunks_kernel(float* __restrict__ p
       const int gid = group_of_block[i >> 6];
       if (gid >= gs.n) continue;
       const AdamwGroup h = gs.g[gid];
-      const float gi = g[i] * clip;
-      const float mi = m[i] * h.beta1 + (1.0f - h.beta1) * gi;
-      const float vi = v[i] * h.beta2 + (1.0f - h.beta2) * gi * gi;
-      float pi = p[i] - h.step_size * (mi / (sqrtf(vi) + h.eps));
-      if (h.weight_decay > 0.f) pi -= h.lr * h.weight_decay * pi;
+      float pi = p[i], mi = m[i], vi = v[i];
+      adamw_elem(pi, g[i], mi, vi, clip, h);
       m[i] = mi; v[i] = vi; p[i] = pi;
     }
   for (int k = threadIdx.x * 4; k + 3 < ch.len; k += 1024) {
@@ -992,14 +1001,12 @@ __global__ void __launch_bounds__(256) adamw_chunks_kernel(float* __restrict__ p
     if (gid >= gs.n) continue;
     const AdamwGroup h = gs.g[gid];
     floatx4 pv = *(const floatx4*)(p + i), mv = *(const floatx4*)(m + i), vv = *(const floatx4*)(v + i);
-    const floatx4 gv = *(const floatx4*)(g + i) * clip;
+    const floatx4 gv = *(const floatx4*)(g + i);
 #pragma unroll
     for (int j = 0; j < 4; ++j) {
-      mv[j] = mv[j] * h.beta1 + (1.0f - h.beta1) * gv[j];
-      vv[j] = vv[j] * h.beta2 + (1.0f - h.beta2) * gv[j] * gv[j];
-      float pi = pv[j] - h.step_size * (mv[j] / (sqrtf(vv[j]) + h.eps));
-      if (h.weight_decay > 0.f) pi -= h.lr * h.weight_decay * pi;
-      pv[j] = pi;
+      float pi = pv[j], mi = mv[j], vi = vv[j];
+      adamw_elem(pi, gv[j], mi, vi, clip, h);
+      pv[j] = pi; mv[j] = mi; vv[j] = vi;
     }
     *(floatx4*)(m + i) = mv; *(floatx4*)(v + i) = vv; *(floatx4*)(p + i) = pv;
   }
@@ -1052,15 +1059,13 @@ __global__ void __launch_bounds__(256) adamw_cast_multi_kernel(const CastDesc* _
       const int gid = group_of_block[e >> 6];           // a quad never straddles a 64-element block (base % 64 == 0, C % 4 == 0)
       if (gid < gs.n) {
         const AdamwGroup h = gs.g[gid];
-        const floatx4 gv = *(const floatx4*)(G0 + e) * clip;
+        const floatx4 gv = *(const floatx4*)(G0 + e);
         floatx4 mv = *(const floatx4*)(M0 + e), vv = *(const floatx4*)(V0 + e);
 #pragma unroll
         for (int j = 0; j < 4; ++j) {
-          mv[j] = mv[j] * h.beta1 + (1.0f - h.beta1) * gv[j];
-          vv[j] = vv[j] * h.beta2 + (1.0f - h.beta2) * gv[j] * gv[j];
-          float pi = pv[j] - h.step_size * (mv[j] / (sqrtf(vv[j]) + h.eps));
-          if (h.weight_decay > 0.f) pi -= h.lr * h.weight_decay * pi;
-          pv[j] = pi;
+          float pi = pv[j], mi = mv[j], vi = vv[j];
+          adamw_elem(pi, gv[j], mi, vi, clip, h);
+          pv[j] = pi; mv[j] = mi; vv[j] = vi;
         }
         *(floatx4*)(M0 + e) = mv; *(floatx4*)(V0 + e) = vv; *(floatx4*)(P0 + e) = pv;
       }
@@ -1089,7 +1094,8 @@ __global__ void __launch_bounds__(256) adamw_cast_multi_kernel(const CastDesc* _
 // The same tile without LDS (round 6): a thread owns a 4 x 4 block - rows r0 + 4 y .. + 3, columns c0 + 4 q .. + 3 - so the transposed
 // copy is an in-register transpose (four 8-byte stores of four consecutive W^T columns each), all sixteen 16-byte loads of the thread
 // are in flight together, there is no barrier, and - the reason it was written - a workgroup that needs no LDS can share a CU with the
-// two 80 KB GEMM workgroups of a running forward (the pipelined sweep, engine.hip adamw_step).  Same arithmetic per element: same bits.
+// two 80 KB GEMM workgroups of a running forward (the pipelined sweep, engine.hip adamw_step).  The same adamw_elem per element: the same
+// bits (tests/test_optim_edges_gpu.py).
 template <typename T>
 __global__ void __launch_bounds__(256) adamw_cast_multi_reg_kernel(const CastDesc* __restrict__ descs, int n, float* __restrict__ P0,
                                                                    const float* __restrict__ G0, float* __restrict__ M0, float* __restrict__ V0,
@@ -1135,14 +1141,11 @@ __global__ void __launch_bounds__(256) adamw_cast_multi_reg_kernel(const CastDes
     const int64_t e = base + (int64_t)r * d.C + c;
     if (gid[k] < gs.n) {
       const AdamwGroup h = gs.g[gid[k]];
-      const floatx4 g4 = gv[k] * clip;
 #pragma unroll
       for (int j = 0; j < 4; ++j) {
-        mv[k][j] = mv[k][j] * h.beta1 + (1.0f - h.beta1) * g4[j];
-        vv[k][j] = vv[k][j] * h.beta2 + (1.0f - h.beta2) * g4[j] * g4[j];
-        float pi = pv[k][j] - h.step_size * (mv[k][j] / (sqrtf(vv[k][j]) + h.eps));
-        if (h.weight_decay > 0.f) pi -= h.lr * h.weight_decay * pi;
-        pv[k][j] = pi;
+        float pi = pv[k][j], mi = mv[k][j], vi = vv[k][j];
+        adamw_elem(pi, gv[k][j], mi, vi, clip, h);
+        pv[k][j] = pi; mv[k][j] = mi; vv[k][j] = vi;
       }
       *(floatx4*)(M0 + e) = mv[k]; *(floatx4*)(V0 + e) = vv[k]; *(floatx4*)(P0 + e) = pv[k];
     }
