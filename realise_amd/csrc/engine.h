@@ -7,7 +7,7 @@
 
 namespace rl {
 struct AdamwGroups;
-void set_wgrad_overlap(int on);
+void set_wgrad_overlap(int on);   // weight-gradient GEMMs of the BERT layers on an engine-owned side stream (default on)
 void set_wgrad_group(int on);     // the four wgrad GEMMs of a transformer layer as one grouped launch (default on)
 void set_dgrad_parity(int on);    // stride-2 conv data gradients by input-pixel parity classes (default on)
 void set_fwd_order(int o);        // enqueue order of the forward branches: 0 bert first, 1 bert last
@@ -20,7 +20,7 @@ void set_bn_fold(int on);          // K9 (evaluation): BatchNorm on running stat
 void set_live_rows(int on);        // bf16 training steps: layer GEMMs / attention forward over the live 16-row blocks only (default 1)
 void set_cls_splitk(int n);        // K-ranges of the classifier's data gradient (default 3, 0 / 1: one launch over the whole K)
 void set_stream_priority(int which, int pri);   // 0 pinyin branch, 1 glyph branch, 2 weight-gradient stream; -1 high, 0 default, +1 low (read at stream creation)
-void set_branch_overlap(int on);  // bert | pho | glyph branches on three streams inside forward / whole-pass backward (default on)   // weight-gradient GEMMs of the BERT layers on an engine-owned side stream (default off)
+void set_branch_overlap(int on);  // bert | pho | glyph branches on three streams inside forward / whole-pass backward (default on)
 
 struct EngineBase {
   virtual ~EngineBase() {}

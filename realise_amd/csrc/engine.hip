@@ -159,9 +159,9 @@ template <typename T> struct Engine : EngineBase {
     StackAct bert, pho, outb;
     BlockAct blk[TOWER_MAX_BLOCKS];
     int64_t mask_add, out_d, dlogits, count, loss_internal;
-    int64_t cls_act, cls_inv, cls_nact, cls_xc, cls_gc, cls_slab;
+    int64_t cls_act, cls_inv, cls_nact, cls_xc, cls_gc, cls_slab;      // classifier backward over the rows that enter the loss only (stage_head)
     int64_t live_rows = 0;                // ascending list of the live rows (row-granular layer GEMMs)
-    int64_t row_live, live_t64, live_t32, live_t16, live_n, live_rlen;          // padding rows: exact-zero gradient rows the backward skips (row_liveness)     // classifier backward over the rows that enter the loss only (stage_head)
+    int64_t row_live, live_t64, live_t32, live_t16, live_n, live_rlen;          // padding rows: exact-zero gradient rows the backward skips (row_liveness)
     int64_t ids_clean = 0, pho_clean = 0;                 // range-checked copies of src_idx / pho_idx (sanitize_ids)
     int64_t gru_table, gru_hs, gru_rzn, gru_gh, gru_out;
     int64_t res_xhat, res_rstd, res_h, gate_mean, gate_msum, gate_g, fused;
@@ -293,7 +293,14 @@ template <typename T> struct Engine : EngineBase {
     return rl::gemm_tn_group<U>(st, n, probs, P_, alpha, overwrite, tile_list, n_tiles, list_rows, sizeof(U) == 4 ? x3() : 0);
   }
   const int* live_rlen() const { return dead_ok ? wp<int>(pl.live_rlen) : nullptr; }
-  bool cls_compact = false;                // the last forward wrote compacted classifier-gradient rows (stage_head must match)
+  // What the last forward's head left for stage_head, its only record of that forward: reset at the top of forward(), filled on every
+  // exit a backward may follow.
+  struct HeadSaved {
+    bool compact = false;                  // the gradient rows (pl.dlogits) are the compacted loss rows (pl.cls_act / cls_inv / cls_nact)
+    const T* dec_in = nullptr;             // the classifier's (MLM head: the decoder's) input rows as its weight gradient reads them
+    const T* head_in = nullptr;            // MLM head: the transform's input rows as its weight gradient reads them
+    const int* row_map = nullptr;          // MLM head: compacted row r = saved row row_map[r] of head_z / head_x / head_rstd (null: identity)
+  } hs;
 
   template <typename U> U* wp(int64_t off) const { return (U*)(ws + off); }
   template <typename U> U* sp(int64_t off) const { return (U*)(sh + off); }
@@ -1269,9 +1276,6 @@ template <typename T> struct Engine : EngineBase {
   // transform of `rows` rows of x (n_dev, nullable: a device-side count of the rows that matter): dense + erf GELU in the GEMM's epilogue,
   // then LayerNorm -> pl.head_y, the decoder's input.  A forward a backward can follow keeps the pre-activation and xhat (in place).
   // The LayerNorm takes no device count: it also normalises the stale (finite) rows behind *n_dev, which nothing reads.
-  const T* dec_in_bwd = nullptr;           // the decoder's input rows / the head's input rows as the backward's weight gradients read them
-  const T* head_in_bwd = nullptr;
-  const int* head_idx = nullptr;           // compacted gradient rows of a forward that saved every row: compact row r = saved row head_idx[r]
   int head_forward(hipStream_t st, const T* x, int rows, const int* n_dev) {
     EpiParams<T> ep; ep.mode = EPI_GELU; ep.out = wp<T>(pl.head_x); ep.out2 = bwd_follows() ? wp<T>(pl.head_z) : nullptr; ep.ldo = H; ep.bias = pp(L.head_b);
     RL_TRY(gemm_nt<T>(st, x, H, sp<T>(sh_head_w), H, rows, H, H, ep, n_dev));
@@ -1289,11 +1293,103 @@ template <typename T> struct Engine : EngineBase {
     return row_liveness(st, b.masks, b.loss_masks, pl.B, pl.S, wp<uint8_t>(pl.row_live), wp<int>(pl.live_t64), wp<int>(pl.live_t32),
                         wp<int>(pl.live_t16), wp<int>(pl.live_n), wp<int>(pl.live_rlen), wp<int>(pl.live_rows));
   }
+  // The head's three forms, and every batch the head refuses - decided here, before forward() launches anything.
+  //   HEAD_DECODE (predict()): no [B*S, V] tensor, the classifier GEMM's epilogue decodes (gemm_nt_decode); no backward follows.
+  //   HEAD_LOSS_ROWS (K13, training without logits): the classifier over the loss rows only, written into the gradient buffer.
+  //   HEAD_LOGITS: the logits of every row, and the loss when the batch brings targets.
+  enum HeadMode { HEAD_DECODE, HEAD_LOSS_ROWS, HEAD_LOGITS };
+  int head_mode(const realise_batch& b, HeadMode* mode) const {
+    const bool loss_io = b.loss_masks && b.loss_out;
+    if (b.logits_out != nullptr) { *mode = HEAD_LOGITS; return b.tgt_idx && !loss_io ? RL_ERR_ARG : RL_OK; }
+    if (!b.training && dec_req.k != 0) { *mode = HEAD_DECODE; return b.tgt_idx && !(loss_io && dec_req.label_logit) ? RL_ERR_ARG : RL_OK; }
+    *mode = HEAD_LOSS_ROWS;
+    return sizeof(T) != 2 || !b.tgt_idx || !loss_io || !b.want_dlogits || !g_cls_compact || (int64_t)b.B * b.S > 65536 ? RL_ERR_ARG : RL_OK;
+  }
+  // The head (models.py:859-869): final dropout, [MLM transform,] tied vocabulary classifier, cross-entropy - and hs, what stage_head reads.
+  int head_fwd(hipStream_t st, const realise_batch& b, HeadMode mode, const T* top) {
+    const int Tk = b.B * b.S;
+    const bool want_loss = b.tgt_idx != nullptr, loss_rows = mode == HEAD_LOSS_ROWS;
+    const DropParams dfin = site(5000, cfg.hidden_dropout);
+    const T* head_in = top;      // the rows that enter the transform (MLM head) or the classifier
+    if (dfin.thresh) { RL_TRY(dropout_apply<T>(st, top, wp<T>(pl.out_d), Tk, H, dfin)); head_in = wp<T>(pl.out_d); }
+    // Backward of the classifier over the rows that enter the loss only (loss_masks: no [CLS] / [SEP] / padding - 60 % of the
+    // rows of a SIGHAN-shaped batch): the gradient rows are written compacted, the classifier input is gathered to match; the
+    // other rows' gradients are exact zeros in the dense form, so the weight / bias / data gradients are the same sums.
+    // (the padding rows the backward skips: row_liveness at the top of forward())
+    const bool compact = loss_rows || (mode == HEAD_LOGITS && want_loss && g_cls_compact && b.want_dlogits && Tk <= 65536);
+    int* const act = wp<int>(pl.cls_act);
+    int* const n_act = wp<int>(pl.cls_nact);
+    CeCompact cc;
+    if (compact) { cc.act_idx = act; cc.inv = wp<int>(pl.cls_inv); cc.n_act = n_act; }
+    // K13 (round 6; models.py:859-869 as the training loop consumes it, run.py:191 takes the loss alone): no [B*S, V] logits.  The
+    // classifier runs over the rows that enter the loss only - listed first (phase 1), the head's input gathered to match - and writes
+    // their logits rows, compacted and at the gradient's row pitch, INTO the gradient buffer; the cross-entropy kernel (phase 2) reads
+    // each row once into registers and stores the row's gradient over it.  Same fp32 accumulators, same bf16 rounding, same row kernel
+    // as the two-buffer form: loss and every gradient bit-identical (tests/test_round6_gpu.py).
+    const int* n_rows = nullptr;      // device count of the rows the head computes (null: all Tk)
+    if (loss_rows) {
+      cc.phase = 1;
+      RL_TRY(ce_loss<T>(st, nullptr, Vp, b.tgt_idx, b.loss_masks, Tk, V, b.loss_out, wp<float>(pl.count), wp<T>(pl.dlogits),
+                        wp<float>(pl.loss_internal), Vp, cc));
+      T* xc = wp<T>(vr.mlm_head ? pl.head_xc : pl.cls_xc);
+      RL_TRY(gather_rows<T>(st, head_in, act, n_act, Tk, H, xc));
+      head_in = xc; n_rows = n_act;
+    }
+    const T* dec_in = head_in;
+    if (vr.mlm_head) {      // the transform over the rows the classifier reads; the decoder reads its output
+      RL_TRY(head_forward(st, head_in, Tk, n_rows));
+      dec_in = wp<T>(pl.head_y);
+    }
+    if (mode == HEAD_DECODE) {
+      // Inference (models.py:859-869 + np.argmax(preds, -1) of src/run.py:262-263 / src/test.py:143) without a [B*S, V] tensor: the
+      // classifier GEMM's epilogue reduces its tiles to per-row candidates and softmax partials (gemm_nt_decode), every row, every dtype.
+      DecodeOut o; o.k = dec_req.k; o.ids = dec_req.ids; o.values = dec_req.values; o.probs = dec_req.probs; o.lse = dec_req.lse;
+      o.label_logit = dec_req.label_logit; o.scratch = dec_req.scratch; o.scratch_bytes = dec_req.scratch_bytes;
+      RL_TRY(gemm_nt_decode<T>(st, dec_in, H, sp<T>(sh_cls_w), H, Tk, V, H, pp(L.cls_b), want_loss ? b.tgt_idx : nullptr, o, sizeof(T) == 4 ? x3() : 0));
+      if (want_loss) RL_TRY(decode_loss(st, dec_req.lse, dec_req.label_logit, b.tgt_idx, b.loss_masks, Tk, b.loss_out));
+      return RL_OK;
+    }
+    // tied vocabulary classifier (models.py:859): the loss rows into the gradient buffer, or every row into the caller's logits
+    T* const logits = loss_rows ? wp<T>(pl.dlogits) : (T*)b.logits_out;
+    const int64_t ldl = loss_rows ? Vp : V;
+    EpiParams<T> ep; ep.mode = EPI_STORE; ep.out = logits; ep.ldo = ldl; ep.bias = pp(L.cls_b);
+    // logits_f32_out (round 6): the fp32 logits the reference returns (models.py:859) written by the classifier's own epilogue next
+    // to the compute-dtype ones the loss reads - no cast pass over [B*S, V]; a shape the persistent kernel does not take is cast here
+    const bool want_f32 = !loss_rows && b.logits_f32_out != nullptr;
+    int rc = RL_ERR_ARG;
+    if (want_f32 && sizeof(T) == 2) {
+      EpiParams<T> e2 = ep; e2.out_f32 = b.logits_f32_out; e2.ldo_f32 = V;
+      rc = gemm_nt<T>(st, dec_in, H, sp<T>(sh_cls_w), H, Tk, V, H, e2);
+      if (rc != RL_OK && rc != RL_ERR_ARG) return rc;
+    }
+    if (rc != RL_OK) {
+      RL_TRY(gemm_nt<T>(st, dec_in, H, sp<T>(sh_cls_w), H, Tk, V, H, ep, n_rows));
+      if (want_f32) RL_TRY(cast_to_f32<T>(st, logits, b.logits_f32_out, (int64_t)Tk * V));
+    }
+    if (!want_loss) return RL_OK;
+    if (loss_rows) { cc.phase = 2; cc.logits_compact = 1; }
+    RL_TRY(ce_loss<T>(st, logits, ldl, b.tgt_idx, b.loss_masks, Tk, V, b.loss_out, wp<float>(pl.count),
+                      b.want_dlogits ? wp<T>(pl.dlogits) : nullptr, wp<float>(pl.loss_internal), Vp, cc));
+    hs.compact = compact; hs.dec_in = dec_in; hs.head_in = head_in;
+    if (compact && !loss_rows) {      // the weight gradients read their input rows compacted; the MLM head's saved tensors stay where they are
+      RL_TRY(gather_rows<T>(st, dec_in, act, n_act, Tk, H, wp<T>(pl.cls_xc)));
+      hs.dec_in = wp<T>(pl.cls_xc);
+      if (vr.mlm_head) {
+        RL_TRY(gather_rows<T>(st, head_in, act, n_act, Tk, H, wp<T>(pl.head_xc)));
+        hs.head_in = wp<T>(pl.head_xc); hs.row_map = act;
+      }
+    }
+    have_fwd = b.training && b.want_dlogits;
+    return RL_OK;
+  }
   int forward(hipStream_t st, const realise_batch& b) override {
     if (!sh || !ws) return RL_ERR_ARG;
     if (b.B < 1 || b.S < 1 || b.S > cfg.max_pos) return RL_ERR_ARG;       // (S > 128: the tiled attention kernels, attention.hip)
     const int Tp = vr.pho ? b.Tp : 1;
     if (vr.pho && (Tp < 1 || !b.pho_idx || !b.pho_perm || !b.pho_lens_sorted || (!b.n_alive && !b.n_alive_dev))) return RL_ERR_ARG;
+    have_fwd = false; hs = HeadSaved();      // whatever happens below, a backward finds nothing of the forward before this one
+    HeadMode mode;
+    RL_TRY(head_mode(b, &mode));
     if (pl.B != b.B || pl.S != b.S || pl.Tp != Tp) {
       RL_TRY(install_plan(st, make_plan(b.B, b.S, Tp)));
     }
@@ -1301,14 +1397,13 @@ template <typename T> struct Engine : EngineBase {
     last.Tp = Tp;
     RL_TRY(wait_opt(st, 0));           // a pipelined optimizer sweep: its first piece holds everything the first kernels read
     have_glyph_fwd = false;            // the activations a glyph_backward would read are about to be overwritten
-    dead_ok = false; rows_live = false; cls_compact = false;
+    dead_ok = false; rows_live = false;
     last_alive.assign(Tp, 0);
     // host counts (the reference's contract: pho_lens is a host list) or, after realise_build_pho, device counts: every
     // step is then launched over all B*S rows and bounded on the device
     if (vr.pho) for (int t = 0; t < Tp; ++t) last_alive[t] = b.n_alive ? b.n_alive[t] : b.B * b.S;
     alive_dev = (vr.pho && !b.n_alive) ? b.n_alive_dev : nullptr;
     last.n_alive = nullptr;
-    have_fwd = false;
     const int Tk = b.B * b.S;
     RL_TRY(mask_to_additive(st, b.masks, wp<float>(pl.mask_add), Tk));
     // everything below (and the backward) reads range-checked copies of the ids: a bad id raises in the module, never faults here
@@ -1374,94 +1469,7 @@ template <typename T> struct Engine : EngineBase {
       RL_TRY(stack_forward(st, 2, L.outb, sh_out, pl.outb, nullptr, wp<T>(pl.fused), 1, &top));
     }
     RL_TRY(sync_optimizer(st));
-    const DropParams dfin = site(5000, cfg.hidden_dropout);
-    const T* cls_in = top;
-    if (dfin.thresh) { RL_TRY(dropout_apply<T>(st, top, wp<T>(pl.out_d), Tk, H, dfin)); cls_in = wp<T>(pl.out_d); }
-    if (b.logits_out == nullptr && !b.training && dec_req.k != 0) {
-      // Inference (models.py:859-869 + np.argmax(preds, -1) of src/run.py:262-263 / src/test.py:143) without a [B*S, V] tensor: the
-      // classifier GEMM's epilogue reduces its tiles to per-row candidates and softmax partials (gemm_nt_decode), every row, every dtype.
-      const bool want_loss = b.tgt_idx != nullptr;
-      if (want_loss && (!b.loss_masks || !b.loss_out || !dec_req.label_logit)) return RL_ERR_ARG;
-      if (vr.mlm_head) {
-        RL_TRY(head_forward(st, cls_in, Tk, nullptr));
-        cls_in = wp<T>(pl.head_y);
-      }
-      DecodeOut o; o.k = dec_req.k; o.ids = dec_req.ids; o.values = dec_req.values; o.probs = dec_req.probs; o.lse = dec_req.lse;
-      o.label_logit = dec_req.label_logit; o.scratch = dec_req.scratch; o.scratch_bytes = dec_req.scratch_bytes;
-      RL_TRY(gemm_nt_decode<T>(st, cls_in, H, sp<T>(sh_cls_w), H, Tk, V, H, pp(L.cls_b), want_loss ? b.tgt_idx : nullptr, o, sizeof(T) == 4 ? x3() : 0));
-      if (want_loss) RL_TRY(decode_loss(st, dec_req.lse, dec_req.label_logit, b.tgt_idx, b.loss_masks, Tk, b.loss_out));
-      have_fwd = false;
-      return RL_OK;
-    }
-    if (b.logits_out == nullptr) {
-      // K13 (round 6; models.py:859-869 as the training loop consumes it, run.py:191 takes the loss alone): no [B*S, V] logits.  The
-      // classifier runs over the rows that enter the loss only - listed first, the classifier input gathered to match - and writes
-      // their logits rows, compacted and at the gradient's row pitch, INTO the gradient buffer; the cross-entropy kernel reads each
-      // row once into registers and stores the row's gradient over it.  Same fp32 accumulators, same bf16 rounding, same row kernel
-      // as the two-buffer form: loss and every gradient bit-identical (tests/test_round6_gpu.py).
-      if (sizeof(T) != 2 || !b.tgt_idx || !b.loss_masks || !b.loss_out || !b.want_dlogits || !g_cls_compact || Tk > 65536) return RL_ERR_ARG;
-      cls_compact = true;
-      CeCompact cc; cc.act_idx = wp<int>(pl.cls_act); cc.inv = wp<int>(pl.cls_inv); cc.n_act = wp<int>(pl.cls_nact);
-      cc.phase = 1;
-      RL_TRY(ce_loss<T>(st, nullptr, Vp, b.tgt_idx, b.loss_masks, Tk, V, b.loss_out, wp<float>(pl.count), wp<T>(pl.dlogits),
-                        wp<float>(pl.loss_internal), Vp, cc));
-      const T* dec_c = wp<T>(pl.cls_xc);
-      if (vr.mlm_head) {      // the transform over the rows that enter the loss only
-        RL_TRY(gather_rows<T>(st, cls_in, wp<int>(pl.cls_act), wp<int>(pl.cls_nact), Tk, H, wp<T>(pl.head_xc)));
-        RL_TRY(head_forward(st, wp<T>(pl.head_xc), Tk, wp<int>(pl.cls_nact)));
-        dec_c = wp<T>(pl.head_y);
-        dec_in_bwd = dec_c; head_in_bwd = wp<T>(pl.head_xc); head_idx = nullptr;
-      } else {
-      RL_TRY(gather_rows<T>(st, cls_in, wp<int>(pl.cls_act), wp<int>(pl.cls_nact), Tk, H, wp<T>(pl.cls_xc)));
-      }
-      EpiParams<T> ep; ep.mode = EPI_STORE; ep.out = wp<T>(pl.dlogits); ep.ldo = Vp; ep.bias = pp(L.cls_b);
-      RL_TRY(gemm_nt<T>(st, dec_c, H, sp<T>(sh_cls_w), H, Tk, V, H, ep, wp<int>(pl.cls_nact)));
-      cc.phase = 2; cc.logits_compact = 1;
-      RL_TRY(ce_loss<T>(st, wp<T>(pl.dlogits), Vp, b.tgt_idx, b.loss_masks, Tk, V, b.loss_out, wp<float>(pl.count), wp<T>(pl.dlogits),
-                        wp<float>(pl.loss_internal), Vp, cc));
-      have_fwd = b.training != 0;
-      return RL_OK;
-    }
-    const T* head_in = cls_in;
-    if (vr.mlm_head) {      // logits of every row: the transform over every row; the decoder reads its output
-      RL_TRY(head_forward(st, cls_in, Tk, nullptr));
-      cls_in = wp<T>(pl.head_y);
-      dec_in_bwd = cls_in; head_in_bwd = head_in; head_idx = nullptr;
-    }
-    {  // tied vocabulary classifier (models.py:859)
-      EpiParams<T> ep; ep.mode = EPI_STORE; ep.out = (T*)b.logits_out; ep.ldo = V; ep.bias = pp(L.cls_b);
-      // logits_f32_out (round 6): the fp32 logits the reference returns (models.py:859) written by the classifier's own epilogue next
-      // to the compute-dtype ones the loss reads - no cast pass over [B*S, V]; a shape the persistent kernel does not take is cast here
-      int rc = RL_ERR_ARG;
-      if (b.logits_f32_out != nullptr && sizeof(T) == 2) {
-        EpiParams<T> e2 = ep; e2.out_f32 = b.logits_f32_out; e2.ldo_f32 = V;
-        rc = gemm_nt<T>(st, cls_in, H, sp<T>(sh_cls_w), H, Tk, V, H, e2);
-        if (rc != RL_OK && rc != RL_ERR_ARG) return rc;
-      }
-      if (rc != RL_OK) {
-        RL_TRY(gemm_nt<T>(st, cls_in, H, sp<T>(sh_cls_w), H, Tk, V, H, ep));
-        if (b.logits_f32_out != nullptr) RL_TRY(cast_to_f32<T>(st, (const T*)b.logits_out, b.logits_f32_out, (int64_t)Tk * V));
-      }
-    }
-    if (b.tgt_idx != nullptr) {
-      if (!b.loss_masks || !b.loss_out) return RL_ERR_ARG;
-      // Backward of the classifier over the rows that enter the loss only (loss_masks: no [CLS] / [SEP] / padding - 60 % of the
-      // rows of a SIGHAN-shaped batch): the gradient rows are written compacted, the classifier input is gathered to match; the
-      // other rows' gradients are exact zeros in the dense form, so the weight / bias / data gradients are the same sums.
-      // (the padding rows the backward skips: row_liveness at the top of this call)
-      cls_compact = g_cls_compact && b.want_dlogits && Tk <= 65536;
-      CeCompact cc;
-      if (cls_compact) { cc.act_idx = wp<int>(pl.cls_act); cc.inv = wp<int>(pl.cls_inv); cc.n_act = wp<int>(pl.cls_nact); }
-      RL_TRY(ce_loss<T>(st, (const T*)b.logits_out, V, b.tgt_idx, b.loss_masks, Tk, V, b.loss_out, wp<float>(pl.count),
-                        b.want_dlogits ? wp<T>(pl.dlogits) : nullptr, wp<float>(pl.loss_internal), Vp, cc));
-      if (cls_compact) RL_TRY(gather_rows<T>(st, cls_in, wp<int>(pl.cls_act), wp<int>(pl.cls_nact), Tk, H, wp<T>(pl.cls_xc)));
-      if (cls_compact && vr.mlm_head) {      // the transform's weight gradient reads its input rows compacted; the saved tensors stay where they are
-        RL_TRY(gather_rows<T>(st, head_in, wp<int>(pl.cls_act), wp<int>(pl.cls_nact), Tk, H, wp<T>(pl.head_xc)));
-        dec_in_bwd = wp<T>(pl.cls_xc); head_in_bwd = wp<T>(pl.head_xc); head_idx = wp<int>(pl.cls_act);
-      }
-    }
-    have_fwd = b.training && b.tgt_idx != nullptr && b.want_dlogits;
-    return RL_OK;
+    return head_fwd(st, b, mode, top);
   }
 
   // ---------------------------------------------------------------- glyph-only entry points (BASELINE configs[3])
@@ -1550,82 +1558,63 @@ template <typename T> struct Engine : EngineBase {
   void set_loss_grad(const float* g) override { loss_grad = g; }
   realise_decode dec_req = realise_decode();      // k == 0: no decode request installed
   void set_decode(const realise_decode* d) override { if (d) dec_req = *d; else dec_req = realise_decode(); }
-  int stage_head(const Lane& la) {      // classifier + final dropout ; leaves d(top hidden) in gA
-    const hipStream_t st = la.st;
+  // The decoder's / classifier's data gradient (K = Vp: the padding columns are exact zeros on both sides), the one place that chooses
+  // between its two forms and applies the loss-gradient scalar.  Compacted bf16 rows of 1024 and more: split-K over the vocabulary,
+  // the planes folded in plane order through fold_map into fold_out, scaled, with fold_drop (*folded = true).  Otherwise, and when the
+  // split launcher refuses the shape: one launch into `out`, scaled here (scale_out) or left to a scatter that scales as it stores.
+  int head_dgrad(hipStream_t st, const int* n_act, T* out, bool scale_out, const int* fold_map, T* fold_out, const DropParams& fold_drop, bool* folded) {
     const int Tk = pl.B * pl.S;
     const T* dl = wp<T>(pl.dlogits);
-    T* gA = wp<T>(pl.gA);
-    const DropParams dfin = site(5000, cfg.hidden_dropout);
-    const T* top = vr.arch ? wp<T>(pl.outb.layers.back().y2) : wp<T>(pl.bert.layers.back().y2);
-    const T* cls_in = dfin.thresh ? wp<T>(pl.out_d) : top;
-    if (vr.mlm_head) return stage_head_mlm(la, dfin);
-    if (cls_compact) {
-      const int* n_act = wp<int>(pl.cls_nact);
-      { TnEpi te; te.slab = wp<float>(la.sc->tn_slab); te.slab_elems = TN_SLAB_ELEMS; te.colsum = gp(L.cls_b); te.out = gp(L.cls_w); te.ldo = H;
-        te.alpha_dev = loss_grad;
-        RL_TRY(gemm_tn<T>(st, dl, Vp, wp<T>(pl.cls_xc), H, Tk, V, H, te, n_act)); }
-      if constexpr (sizeof(T) == 2) {
-        const int ns = g_cls_splitk;
-        if (ns >= 2 && pl.cls_slab != 0 && Tk >= 1024 &&
-            gemm_nt8_splitk(st, dl, Vp, sp<T>(sh_cls_wT), Vp, Tk, H, Vp, ns, wp<float>(pl.cls_slab), (int64_t)Tk * H, n_act) == RL_OK)
-          return scatter_rows_drop_slab<T>(st, wp<float>(pl.cls_slab), ns, (int64_t)Tk * H, wp<int>(pl.cls_inv), Tk, H, gA, dfin, loss_grad);
+    *folded = false;
+    if constexpr (sizeof(T) == 2) {
+      const int ns = g_cls_splitk;
+      if (hs.compact && ns >= 2 && pl.cls_slab != 0 && Tk >= 1024 &&
+          gemm_nt8_splitk(st, dl, Vp, sp<T>(sh_cls_wT), Vp, Tk, H, Vp, ns, wp<float>(pl.cls_slab), (int64_t)Tk * H, n_act) == RL_OK) {
+        *folded = true;
+        return scatter_rows_drop_slab<T>(st, wp<float>(pl.cls_slab), ns, (int64_t)Tk * H, fold_map, Tk, H, fold_out, fold_drop, loss_grad);
       }
-      { EpiParams<T> ep; ep.mode = EPI_STORE; ep.out = wp<T>(pl.cls_gc); ep.ldo = H; ep.m_dev = n_act;
-        RL_TRY(gemm_nt<T>(st, dl, Vp, sp<T>(sh_cls_wT), Vp, Tk, H, Vp, ep)); }
-      return scatter_rows_drop<T>(st, wp<T>(pl.cls_gc), wp<int>(pl.cls_inv), Tk, H, gA, dfin, loss_grad);      // rows outside the loss: zero; + the final dropout's map
     }
-    { TnEpi te; te.slab = wp<float>(la.sc->tn_slab); te.slab_elems = TN_SLAB_ELEMS; te.colsum = gp(L.cls_b); te.out = gp(L.cls_w); te.ldo = H; te.alpha_dev = loss_grad;
-      RL_TRY(gemm_tn<T>(st, dl, Vp, cls_in, H, Tk, V, H, te)); }
-    { EpiParams<T> ep; ep.mode = EPI_STORE; ep.out = gA; ep.ldo = H;
-      RL_TRY(gemm_nt<T>(st, dl, Vp, sp<T>(sh_cls_wT), Vp, Tk, H, Vp, ep)); }      // K = Vp: the padding columns are exact zeros on both sides
-    if (loss_grad != nullptr) RL_TRY(scale_by_dev<T>(st, gA, (int64_t)Tk * H, loss_grad));      // (dense fallback: a pass over [T, H], not over the logits)
-    if (dfin.thresh) RL_TRY(dropout_apply<T>(st, gA, gA, Tk, H, dfin));
+    EpiParams<T> ep; ep.mode = EPI_STORE; ep.out = out; ep.ldo = H; ep.m_dev = n_act;
+    RL_TRY(gemm_nt<T>(st, dl, Vp, sp<T>(sh_cls_wT), Vp, Tk, H, Vp, ep));
+    if (scale_out && loss_grad != nullptr) RL_TRY(scale_by_dev<T>(st, out, (int64_t)Tk * H, loss_grad));      // (a pass over [T, H], not over the logits)
     return RL_OK;
   }
-
-  // The MLM head's backward (modeling_bert.py:419-462): decoder weight / bias / data gradient as the plain classifier's, then ONE row pass for
-  // LayerNorm' and GELU' (ln_gelu_bwd), the transform's weight gradient with its bias gradient as the column sum, its data gradient, and
-  // the scatter / final-dropout map.  The loss-gradient scalar reaches the decoder's weight and bias gradients in their epilogue, as
-  // before, and everything behind the decoder through the decoder's DATA gradient, which is scaled once where it is stored: dz, the
-  // transform's four gradients and d(top hidden) are linear in it and get no factor of their own.
-  int stage_head_mlm(const Lane& la, const DropParams& dfin) {
+  // The head's backward; leaves d(top hidden) in gA.  Reads hs and nothing else about the forward.  Plain classifier: weight / bias
+  // gradient, data gradient, the finish.  MLM head (modeling_bert.py:419-462): between the decoder's data gradient and the finish ONE row
+  // pass for LayerNorm' and GELU' (ln_gelu_bwd), the transform's weight gradient with its bias gradient as the column sum, and its data
+  // gradient.  The loss-gradient scalar reaches the decoder's weight and bias gradients in their epilogue; everything behind the
+  // decoder gets it through the decoder's DATA gradient, scaled once where it is stored: dz, the transform's four gradients and
+  // d(top hidden) are linear in it and get no factor of their own.  (The plain compacted form scales in the scatter that follows.)
+  int stage_head(const Lane& la) {
     const hipStream_t st = la.st;
     const int Tk = pl.B * pl.S;
-    const T* dl = wp<T>(pl.dlogits);
     T* gA = wp<T>(pl.gA);
-    T* dy = wp<T>(pl.cls_gc);
-    T* dz = wp<T>(pl.head_dz);
-    const int* n_act = cls_compact ? wp<int>(pl.cls_nact) : nullptr;
+    T* dy = wp<T>(pl.cls_gc);      // compacted rows, and the MLM head's dense ones: d(decoder input), then d(head input)
+    const DropParams dfin = site(5000, cfg.hidden_dropout);
+    const int* n_act = hs.compact ? wp<int>(pl.cls_nact) : nullptr;
+    const int* inv = wp<int>(pl.cls_inv);
     { TnEpi te; te.slab = wp<float>(la.sc->tn_slab); te.slab_elems = TN_SLAB_ELEMS; te.colsum = gp(L.cls_b); te.out = gp(L.cls_w); te.ldo = H;
       te.alpha_dev = loss_grad;
-      RL_TRY(gemm_tn<T>(st, dl, Vp, dec_in_bwd, H, Tk, V, H, te, n_act)); }
-    bool have_dy = false;
-    if constexpr (sizeof(T) == 2) {      // split-K over the vocabulary, the planes folded in plane order (and scaled) into the compacted rows
-      const int ns = g_cls_splitk;
-      if (cls_compact && ns >= 2 && pl.cls_slab != 0 && Tk >= 1024 &&
-          gemm_nt8_splitk(st, dl, Vp, sp<T>(sh_cls_wT), Vp, Tk, H, Vp, ns, wp<float>(pl.cls_slab), (int64_t)Tk * H, n_act) == RL_OK) {
-        RL_TRY(scatter_rows_drop_slab<T>(st, wp<float>(pl.cls_slab), ns, (int64_t)Tk * H, wp<int>(pl.head_ident), Tk, H, dy, DropParams(), loss_grad));
-        have_dy = true;
-      }
-    }
-    if (!have_dy) {
-      EpiParams<T> ep; ep.mode = EPI_STORE; ep.out = dy; ep.ldo = H; ep.m_dev = n_act;
-      RL_TRY(gemm_nt<T>(st, dl, Vp, sp<T>(sh_cls_wT), Vp, Tk, H, Vp, ep));      // K = Vp: the padding columns are exact zeros on both sides
-      if (loss_grad != nullptr) RL_TRY(scale_by_dev<T>(st, dy, (int64_t)Tk * H, loss_grad));
-    }
-    { LnGeluBwdArgs<T> a; a.rows = Tk; a.H = H; a.n_dev = n_act; a.idx = head_idx; a.saved_rows = Tk;
-      a.dy = dy; a.xhat = wp<T>(pl.head_x); a.rstd = wp<float>(pl.head_rstd); a.z = wp<T>(pl.head_z); a.gamma = pp(L.head_ln_g); a.dz = dz;
-      a.dgamma = gp(L.head_ln_g); a.dbeta = gp(L.head_ln_b); a.slots = ln_region(la, LN_FOLD_MAX);
-      RL_TRY(ln_gelu_bwd<T>(st, a)); }
-    { TnEpi te; te.slab = wp<float>(la.sc->tn_slab); te.slab_elems = TN_SLAB_ELEMS; te.colsum = gp(L.head_b); te.out = gp(L.head_w); te.ldo = H;
-      RL_TRY(gemm_tn<T>(st, dz, H, head_in_bwd, H, Tk, H, H, te, n_act)); }
-    if (cls_compact) {
-      EpiParams<T> ep; ep.mode = EPI_STORE; ep.out = dy; ep.ldo = H; ep.m_dev = n_act;      // (dy is consumed: its buffer takes d(head input), compacted)
+      RL_TRY(gemm_tn<T>(st, wp<T>(pl.dlogits), Vp, hs.dec_in, H, Tk, V, H, te, n_act)); }
+    const float* scale = nullptr;  // the loss-gradient scalar, where the scatter still has to apply it
+    bool folded = false;
+    if (vr.mlm_head) {             // the planes fold into the compacted rows where they are (head_ident)
+      T* dz = wp<T>(pl.head_dz);
+      RL_TRY(head_dgrad(st, n_act, dy, true, wp<int>(pl.head_ident), dy, DropParams(), &folded));
+      { LnGeluBwdArgs<T> a; a.rows = Tk; a.H = H; a.n_dev = n_act; a.idx = hs.row_map; a.saved_rows = Tk;
+        a.dy = dy; a.xhat = wp<T>(pl.head_x); a.rstd = wp<float>(pl.head_rstd); a.z = wp<T>(pl.head_z); a.gamma = pp(L.head_ln_g); a.dz = dz;
+        a.dgamma = gp(L.head_ln_g); a.dbeta = gp(L.head_ln_b); a.slots = ln_region(la, LN_FOLD_MAX);
+        RL_TRY(ln_gelu_bwd<T>(st, a)); }
+      { TnEpi te; te.slab = wp<float>(la.sc->tn_slab); te.slab_elems = TN_SLAB_ELEMS; te.colsum = gp(L.head_b); te.out = gp(L.head_w); te.ldo = H;
+        RL_TRY(gemm_tn<T>(st, dz, H, hs.head_in, H, Tk, H, H, te, n_act)); }
+      EpiParams<T> ep; ep.mode = EPI_STORE; ep.out = hs.compact ? dy : gA; ep.ldo = H; ep.m_dev = n_act;      // (dy is consumed: its buffer takes d(head input), compacted)
       RL_TRY(gemm_nt<T>(st, dz, H, sp<T>(sh_head_wT), H, Tk, H, H, ep));
-      return scatter_rows_drop<T>(st, dy, wp<int>(pl.cls_inv), Tk, H, gA, dfin, nullptr);      // rows outside the loss: zero; + the final dropout's map
+    } else {                       // the planes fold straight into gA through cls_inv with the final dropout's map: that is the finish
+      RL_TRY(head_dgrad(st, n_act, hs.compact ? dy : gA, !hs.compact, inv, gA, dfin, &folded));
+      if (folded) return RL_OK;
+      scale = loss_grad;
     }
-    { EpiParams<T> ep; ep.mode = EPI_STORE; ep.out = gA; ep.ldo = H;
-      RL_TRY(gemm_nt<T>(st, dz, H, sp<T>(sh_head_wT), H, Tk, H, H, ep)); }
+    if (hs.compact) return scatter_rows_drop<T>(st, dy, inv, Tk, H, gA, dfin, scale);      // rows outside the loss: zero; + the final dropout's map
     if (dfin.thresh) RL_TRY(dropout_apply<T>(st, gA, gA, Tk, H, dfin));
     return RL_OK;
   }
