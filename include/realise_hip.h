@@ -161,6 +161,17 @@ int realise_layernorm_gelu_bwd(void* stream, int dtype, const void* dy, const vo
  * ordered fold is).  tests/test_row_edges_gpu.py pins all of this. */
 int realise_masked_ce(void* stream, int dtype, const void* logits, int64_t ld, const int64_t* labels,
                       const int64_t* loss_mask, int rows, int V, float* loss_out, float* count_scratch, void* dlogits);
+/* realise_masked_ce whose row pass also ranks (replaces `active_logits.argmax(dim=-1)`, src/models.py:1343-1346, and the comparison
+ * run_pretrain.py:100-104 / 240-243 scores accuracy from): same arguments, same loss, count and gradient rows bit for bit, plus
+ * pred_out [rows] - the arg-max column of every row that enters the loss, -1 for every other row - and hits[0] = how many of those
+ * predictions equal their label.  Ranking rule (realise_argmax, realise_gemm_nt_decode): on the stored compute-dtype value a beats b
+ * when a > b or a is NaN and b is not, the lower column wins on equal values, -0.0 ranks as +0.0, the tail [V, ld) enters nothing.
+ * The row kernels keep each row in registers (bf16) or rank during the walk that finds the row maximum: no second read of the logits,
+ * and the prediction is taken before a gradient row is stored.  EMPTY SELECTION: every pred_out entry is -1, hits[0] = 0, the loss as
+ * documented above. */
+int realise_masked_ce_pred(void* stream, int dtype, const void* logits, int64_t ld, const int64_t* labels,
+                           const int64_t* loss_mask, int rows, int V, float* loss_out, float* count_scratch, void* dlogits,
+                           int64_t* pred_out, int32_t* hits);
 
 /* One time step of the pinyin GRU (nn.GRU over pack_padded_sequence, src/models.py:818-826) on the n_alive longest sequences
  * (tokens sorted by decreasing length: perm[i] = original token of sorted row i, lens[i] its length).  The input projection is a
@@ -288,14 +299,19 @@ typedef struct {
                               * glyph table is the nn.Embedding [V, 1024] (models.py:1043,1134), so it needs num_fonts == 1, glyph_size == 32,
                               * 4 = SpellBertPho2ResArch3MLM (models.py:874-1020): Arch3 with one font whose classifier is BertOnlyMLMHead
                               * (cls.predictions.*: dense -> erf GELU -> LayerNorm -> untied decoder + bias); num_fonts == 1,
-                              * glyph_size == 32 and tie_classifier == 0 */
+                              * glyph_size == 32 and tie_classifier == 0,
+                              * 5 = Pho2Pretrain (models.py:1286-1347; run_pretrain.py's 'pho2-pretrain'): the pinyin branch alone -
+                              * pho_embeddings, pho_gru, pho_model (pho_layers deep; bert_layers is carried and ignored) - under a
+                              * BertOnlyMLMHead named cls2.  No bert stack, fusion, glyph tower or output block; src_idx is the batch's
+                              * tgt_idx (models.py:1319); tie_classifier == 0, with_pho == 1 and with_res == 0 (the branches it has: a
+                              * type-5 config that claims a glyph branch is refused); gradient buckets: 0 = cls2, 1 = the pinyin branch */
   int32_t dtype;
   int32_t hidden, heads, intermediate, vocab, max_pos, type_vocab;
   int32_t bert_layers, pho_layers, out_layers;
   int32_t num_fonts, glyph_size, pho_vocab;
   float hidden_dropout, attn_dropout, ln_eps;
   int32_t tie_classifier;    /* classifier.weight aliases bert word embeddings (models.py:700-701) */
-  /* model_type 2 only (ignored otherwise; run.py:373-375): 1 = the pinyin branch / the glyph branch is present; fusion 0 = gate over
+  /* model_type 2, and model_type 5 as (1, 0, 0) (ignored otherwise; run.py:373-375): 1 = the pinyin branch / the glyph branch is present; fusion 0 = gate over
    * the G = 1 + with_pho + with_res sources (gate_net [G, (G+1)H]), 1 = sum (needs both branches) */
   int32_t with_pho, with_res, fusion;
   /* the glyph encoder (run.py:292,419-421 --image_model_type; models.py:681-686): 0 = CharResNet (char_cnn.py:36-55: five blocks,
@@ -363,6 +379,18 @@ void realise_engine_set_loss_grad(realise_engine* e, const float* grad_dev);
  * loss_masks, writes the masked mean of lse - label_logit to loss_out (d->label_logit is then required).  The struct is copied; NULL
  * clears the request.  Without a request a NULL logits_out behaves as before. */
 void realise_engine_set_decode(realise_engine* e, const realise_decode* d);
+/* What a pretraining loop reads next to the loss (replaces src/models.py:1343-1346 `active_logits.argmax(dim=-1)` and
+ * `input_ids.view(-1)[active_loss]`, the second and third entry of Pho2Pretrain.forward's tuple): with a request installed, every
+ * realise_engine_forward that computes the cross-entropy (logits or no-logits form; not the decode form) also writes, for the j-th
+ * row that enters the loss in ascending row order, pred_ids[j] = the arg-max column of its logits (realise_masked_ce_pred's rule)
+ * and labels[j] = its tgt_idx, n_active[0] = how many such rows, hits[0] = how many predictions equal their label.  All device
+ * pointers, written on the forward's stream; entries j >= capacity are not written; labels / n_active / hits are nullable.  The
+ * ranking rides the cross-entropy pass that holds the row: no [B*S, V] tensor is read again.  B * S <= 65536.  The struct is copied;
+ * NULL clears the request.  Every model type takes it. */
+typedef struct {
+  int64_t* pred_ids; int64_t* labels; int32_t* n_active; int32_t* hits; int64_t capacity;
+} realise_pred;
+void realise_engine_set_pred(realise_engine* e, const realise_pred* d);
 
 typedef struct {
   int32_t B, S, Tp;

@@ -7,7 +7,7 @@ is no CPU or PyTorch fallback.
 import ctypes as C
 import os
 
-from .config import MODEL_TYPES
+from .config import MODEL_TYPES, model_type_number  # noqa: F401
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "librealise_hip.so")
@@ -89,6 +89,11 @@ class Batch(C.Structure):
                 ("n_alive_dev", C.c_void_p), ("eval_live_rows", C.c_int32), ("logits_f32_out", C.c_void_p)]
 
 
+class Pred(C.Structure):
+    """realise_pred (include/realise_hip.h)"""
+    _fields_ = [("pred_ids", C.c_void_p), ("labels", C.c_void_p), ("n_active", C.c_void_p), ("hits", C.c_void_p), ("capacity", C.c_int64)]
+
+
 class Decode(C.Structure):
     _fields_ = [("k", C.c_int32), ("ids", C.c_void_p), ("values", C.c_void_p), ("probs", C.c_void_p), ("lse", C.c_void_p),
                 ("label_logit", C.c_void_p), ("scratch", C.c_void_p), ("scratch_bytes", C.c_int64)]
@@ -163,6 +168,8 @@ SYMBOLS = {
     "realise_gemm_nt_decode_scratch_bytes": (_L, [_I, _I, _I, _I, _I]),
     "realise_gemm_nt_decode": (_I, [_P, _I, _P, _L, _P, _L, _I, _I, _I, _P, _P, C.POINTER(Decode)]),
     "realise_engine_set_decode": (None, [_P, C.POINTER(Decode)]),
+    "realise_engine_set_pred": (None, [_P, C.POINTER(Pred)]),
+    "realise_masked_ce_pred": (_I, [_P, _I, _P, _L, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
     "realise_build_pho": (_I, [_P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P]),
     "realise_layout_count": (_I, [C.POINTER(Config)]),
     "realise_layout_entry": (_I, [C.POINTER(Config), _I, C.c_char_p, _I, C.POINTER(C.c_int32), C.POINTER(_L),
@@ -256,7 +263,7 @@ def check(rc, what):
 
 def make_config(cfg, model_type, dtype, tie=True):
     c = Config()
-    c.model_type = MODEL_TYPES[model_type]
+    c.model_type = model_type_number(model_type)
     c.dtype = dtype
     c.hidden, c.heads, c.intermediate = cfg["hidden_size"], cfg["num_attention_heads"], cfg["intermediate_size"]
     c.vocab, c.max_pos, c.type_vocab = cfg["vocab_size"], cfg["max_position_embeddings"], cfg["type_vocab_size"]
@@ -269,6 +276,8 @@ def make_config(cfg, model_type, dtype, tie=True):
     c.with_pho = 1 if cfg.get("with_pho", "yes") == "yes" else 0
     c.with_res = 1 if cfg.get("with_res", "yes") == "yes" else 0
     c.fusion = 1 if cfg.get("fusion", "gate") == "sum" else 0
+    if c.model_type == 5:      # Pho2Pretrain is the pinyin branch without the glyph branch, whatever the config's ablation switches say
+        c.with_pho, c.with_res, c.fusion = 1, 0, 0
     # the glyph encoder (run.py:419-421): 0 = CharResNet, 1 = CharResNet1; read where the model has a glyph branch
     c.image_model_type = int(cfg.get("image_model_type", 0))
     return c

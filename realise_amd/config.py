@@ -127,16 +127,45 @@ _MODELS = {
     "arch3-mlm": (4, "SpellBertPho2ResArch3MLM", 894),
 }
 MODEL_TYPES = {k: row[0] for k, row in _MODELS.items()}
+# run_pretrain.py:33-36 keeps a MODEL_CLASSES table of its own, and so do the pretraining models here: same row format, the ABI numbers
+# go on where MODEL_TYPES' stop.  variant_of / tensor_specs / validate / _capi.make_config take a name from either table.
+_PRETRAIN_MODELS = {
+    "pho2-pretrain": (5, "Pho2Pretrain", None),
+}
+PRETRAIN_MODEL_TYPES = {k: row[0] for k, row in _PRETRAIN_MODELS.items()}
+# run_pretrain.py's other entries, named so that they are refused with their reason instead of as an unknown string
+_PRETRAIN_NOT_BUILT = {
+    "pho2res-pretrain": "Pho2ResPretrain (models.py:1216-1284) is not implemented: only 'pho2-pretrain' runs here",
+    "res-pretrain": "ResPretrain (models.py:1349-1420) is not implemented: about a thousand steps over 256 glyphs that finish in a minute "
+                    "on any device; only 'pho2-pretrain' runs here",
+}
+
+
+def model_type_number(model_type):
+    """the C ABI's realise_config.model_type of a name from MODEL_TYPES or PRETRAIN_MODEL_TYPES"""
+    if model_type in MODEL_TYPES:
+        return MODEL_TYPES[model_type]
+    if model_type in PRETRAIN_MODEL_TYPES:
+        return PRETRAIN_MODEL_TYPES[model_type]
+    variant_of({}, model_type)      # raises with the reason
 
 # What a model computes: csrc/layout.h's ``Variant`` field for field (``gates`` is G: 0 without a gate_net, otherwise its ``nsrc``),
 # then what only Python needs: ``one_font`` (the hard-wired [V, 1024] glyph table, at src/models.py:``one_font_line``) and the
-# reference class name for messages.  Every Python-side decision reads this, not ``model_type``.
-Variant = collections.namedtuple("Variant", "arch pho res gate gates gate_softmax mlm_head one_font one_font_line reference_class")
+# reference class name for messages, ``head_prefix`` (the state_dict prefix of an MLM head: "cls." or Pho2Pretrain's "cls2.", else None).
+# ``bert``: the model has the bert stack (false: Pho2Pretrain, the pinyin branch alone).  Every Python-side decision reads this, not
+# ``model_type``.
+Variant = collections.namedtuple("Variant", "arch pho res gate gates gate_softmax mlm_head one_font one_font_line reference_class bert head_prefix")
 
 
 def variant_of(cfg, model_type):
+    if model_type in _PRETRAIN_NOT_BUILT:
+        raise ValueError("model_type %r: %s" % (model_type, _PRETRAIN_NOT_BUILT[model_type]))
+    if model_type in _PRETRAIN_MODELS:      # Pho2Pretrain (models.py:1286-1347): pho_embeddings, pho_gru, pho_model and the MLM head cls2
+        _, reference_class, _ = _PRETRAIN_MODELS[model_type]
+        return Variant(arch=False, pho=True, res=False, gate=False, gates=0, gate_softmax=False, mlm_head=True, one_font=False,
+                       one_font_line=None, reference_class=reference_class, bert=False, head_prefix="cls2.")
     if model_type not in _MODELS:
-        raise ValueError("model_type must be 'bert', 'arch3', 'arch3-abla', 'arch4' or 'arch3-mlm'")
+        raise ValueError("model_type must be 'bert', 'arch3', 'arch3-abla', 'arch4' or 'arch3-mlm' (or 'pho2-pretrain' of PRETRAIN_MODEL_TYPES)")
     _, reference_class, one_font_line = _MODELS[model_type]
     arch = model_type != "bert"
     abla = model_type == "arch3-abla"      # src/models_abla.py:37-45: the switches drop whole branches; (yes, yes, gate) is arch3
@@ -145,4 +174,5 @@ def variant_of(cfg, model_type):
     gate = arch and (not abla or cfg.get("fusion", "gate") == "gate")
     return Variant(arch=arch, pho=pho, res=res, gate=gate, gates=(1 + pho + res) if gate else 0,
                    gate_softmax=model_type == "arch4", mlm_head=model_type == "arch3-mlm",
-                   one_font=one_font_line is not None, one_font_line=one_font_line, reference_class=reference_class)
+                   one_font=one_font_line is not None, one_font_line=one_font_line, reference_class=reference_class, bert=True,
+                   head_prefix="cls." if model_type == "arch3-mlm" else None)

@@ -265,6 +265,13 @@ int realise_masked_ce(void* stream, int dtype, const void* logits, int64_t ld, c
                       int rows, int V, float* loss_out, float* count_scratch, void* dlogits) {
   RL_BY_DTYPE(0, ce_loss<E>((hipStream_t)stream, (const E*)logits, ld, labels, loss_mask, rows, V, loss_out, count_scratch, (E*)dlogits));
 }
+int realise_masked_ce_pred(void* stream, int dtype, const void* logits, int64_t ld, const int64_t* labels, const int64_t* loss_mask,
+                           int rows, int V, float* loss_out, float* count_scratch, void* dlogits, int64_t* pred_out, int32_t* hits) {
+  if (pred_out == nullptr || hits == nullptr) return RL_ERR_ARG;
+  CePred pr; pr.pred = pred_out; pr.hits = hits; pr.capacity = rows;
+  RL_BY_DTYPE(0, ce_loss<E>((hipStream_t)stream, (const E*)logits, ld, labels, loss_mask, rows, V, loss_out, count_scratch, (E*)dlogits, nullptr, 0,
+                            CeCompact(), &pr));
+}
 
 // ---- remaining fine-grained operators of the path (per-op parity tests call these) ------------------------------------------------
 int realise_gru_step_fwd(void* stream, int dtype, const realise_gru_step* a) {
@@ -501,6 +508,7 @@ void realise_engine_set_grads_fresh(realise_engine* e, int fresh) { if (e) e->im
 void realise_engine_set_id_flag(realise_engine* e, int32_t* flag) { if (e) e->impl->set_id_flag((int*)flag); }
 void realise_engine_set_loss_grad(realise_engine* e, const float* grad_dev) { if (e) e->impl->set_loss_grad(grad_dev); }
 void realise_engine_set_decode(realise_engine* e, const realise_decode* d) { if (e) e->impl->set_decode(d); }
+void realise_engine_set_pred(realise_engine* e, const realise_pred* d) { if (e) e->impl->set_pred(d); }
 int realise_engine_forward(realise_engine* e, void* stream, const realise_batch* batch) {
   return (e && batch) ? e->impl->forward((hipStream_t)stream, *batch) : RL_ERR_ARG;
 }

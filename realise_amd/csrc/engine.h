@@ -40,6 +40,7 @@ struct EngineBase {
   virtual void set_grads_fresh(int fresh) = 0;
   virtual void set_loss_grad(const float* grad_dev) = 0;
   virtual void set_decode(const realise_decode* d) = 0;      // NULL clears; copied
+  virtual void set_pred(const realise_pred* d) = 0;          // NULL clears; copied
   virtual int forward(hipStream_t st, const realise_batch& b) = 0;
   virtual int backward(hipStream_t st, int first, int last) = 0;
   virtual int backward_signalled(hipStream_t st, void* const* bucket_events, int n_events) = 0;

@@ -327,7 +327,7 @@ template <typename T> struct Engine : EngineBase {
         v[l].out_w = b.take((int64_t)I * H * e); v[l].out_wT = b.take((int64_t)I * H * e);
       }
     };
-    plan_stack(sh_bert, cfg.bert_layers);
+    plan_stack(sh_bert, vr.bert ? cfg.bert_layers : 0);
     sh_cls_w = b.take((int64_t)V * H * e);
     sh_cls_wT = b.take((int64_t)Vp * H * e);      // [H][Vp], columns >= V stay zero (the shadow arena is zero-initialised)
     if (vr.pho) plan_stack(sh_pho, cfg.pho_layers);
@@ -417,7 +417,7 @@ template <typename T> struct Engine : EngineBase {
     if (ovl) RL_TRY(fork(st));
     const CastDesc* dd = (const CastDesc*)(sh + sh_descs);
     if (!skip_linear) {
-      RL_TRY(cast_transpose_multi<T>(st, dd, n_descs_a, desc_tiles_a));
+      if (n_descs_a > 0) RL_TRY(cast_transpose_multi<T>(st, dd, n_descs_a, desc_tiles_a));
       RL_TRY(cast_transpose_multi<T>(s_b, dd + n_descs_a, n_descs - n_descs_a, desc_tiles));
     }
     if (vr.res) {
@@ -556,7 +556,7 @@ template <typename T> struct Engine : EngineBase {
       opt_pending = true;
       return RL_OK;
     }
-    RL_TRY(adamw_cast_multi<T>(st, dd, n_descs_a, desc_tiles_a, P, G, m, v, group_of_block, gs, norm_sq, max_norm));
+    if (n_descs_a > 0) RL_TRY(adamw_cast_multi<T>(st, dd, n_descs_a, desc_tiles_a, P, G, m, v, group_of_block, gs, norm_sq, max_norm));
     RL_TRY(adamw_cast_multi<T>(st, dd + n_descs_a, n_descs - n_descs_a, desc_tiles, P, G, m, v, group_of_block, gs, norm_sq, max_norm));
     return adamw_chunks(st, P, G, m, v, (const FillChunk*)(sh + sh_skip), n_achunks, group_of_block, gs, norm_sq, max_norm);
   }
@@ -606,7 +606,7 @@ template <typename T> struct Engine : EngineBase {
     p.ids_clean = b.take(Tk * 8);
     p.pho_clean = (!glyph_only && vr.pho) ? b.take(Tk * (int64_t)(Tp > 0 ? Tp : 1) * 8) : 0;
     if (!glyph_only) {
-      plan_stack(p.bert, cfg.bert_layers, "bert");
+      if (vr.bert) plan_stack(p.bert, cfg.bert_layers, "bert");
       p.out_d = b.take(Tk * H * e);
       p.dlogits = b.take(Tk * Vp * e);
       tap("dlogits", p.dlogits, Tk * Vp);
@@ -713,6 +713,17 @@ template <typename T> struct Engine : EngineBase {
       p.head_xc = b.take(Tk * H * e); p.head_dz = b.take(Tk * H * e); p.head_ident = b.take(Tk * 4);
       tap("head.z", p.head_z, Tk * H); tap("head.y", p.head_y, Tk * H);
       tap("head.d_in", p.gA, Tk * H);      // d(head input) = d(top hidden) after stage_head
+    }
+    if (!vr.bert && vr.pho && !glyph_only) {      // Pho2Pretrain: the pinyin branch is the whole model (only a model_type 5 plan has these takes)
+      plan_stack(p.pho, cfg.pho_layers, "pho_model");
+      p.gru_table = b.take(64LL * 3 * H * 4);
+      p.gru_hs = b.take((int64_t)Tp * Tk * H * e);
+      p.gru_rzn = b.take((int64_t)Tp * Tk * 3 * H * e);
+      p.gru_gh = b.take((int64_t)Tp * Tk * 3 * H * e);
+      p.gru_out = b.take(Tk * H * e);
+      tap("pho_gru", p.gru_out, Tk * H);
+      p.gru_dh = b.take(Tk * H * e); p.gru_dgi = b.take(Tk * 3 * H * e); p.gru_dgh = b.take(Tk * 3 * H * e);
+      p.gru_onehot = b.take(Tk * 64 * e); p.gru_dtable = b.take(64LL * 3 * H * 4);
     }
     p.total = b.off;
     return p;
@@ -1368,8 +1379,21 @@ template <typename T> struct Engine : EngineBase {
     }
     if (!want_loss) return RL_OK;
     if (loss_rows) { cc.phase = 2; cc.logits_compact = 1; }
+    // a ranking request (realise_engine_set_pred; models.py:1343-1346): the cross-entropy pass also writes the arg-max of the active
+    // rows, their labels and the hit count, entry j for the j-th active row.  Where the gradient rows are not compacted (an evaluation
+    // forward with logits, key 4 off) the active rows are listed for the request alone.
+    CePred pr;
+    const bool ranking = pred_req.pred_ids != nullptr;
+    if (ranking) {
+      pr.pred = pred_req.pred_ids; pr.labels_out = pred_req.labels; pr.hits = pred_req.hits; pr.n_active = pred_req.n_active; pr.capacity = pred_req.capacity;
+      if (!compact) {
+        CeCompact c1; c1.act_idx = act; c1.inv = wp<int>(pl.cls_inv); c1.n_act = n_act; c1.phase = 1;
+        RL_TRY(ce_loss<T>(st, nullptr, Vp, b.tgt_idx, b.loss_masks, Tk, V, b.loss_out, wp<float>(pl.count), wp<T>(pl.dlogits), wp<float>(pl.loss_internal), Vp, c1));
+        pr.inv = wp<int>(pl.cls_inv); pr.n_src = n_act;
+      }
+    }
     RL_TRY(ce_loss<T>(st, logits, ldl, b.tgt_idx, b.loss_masks, Tk, V, b.loss_out, wp<float>(pl.count),
-                      b.want_dlogits ? wp<T>(pl.dlogits) : nullptr, wp<float>(pl.loss_internal), Vp, cc));
+                      b.want_dlogits ? wp<T>(pl.dlogits) : nullptr, wp<float>(pl.loss_internal), Vp, cc, ranking ? &pr : nullptr));
     hs.compact = compact; hs.dec_in = dec_in; hs.head_in = head_in;
     if (compact && !loss_rows) {      // the weight gradients read their input rows compacted; the MLM head's saved tensors stay where they are
       RL_TRY(gather_rows<T>(st, dec_in, act, n_act, Tk, H, wp<T>(pl.cls_xc)));
@@ -1442,8 +1466,13 @@ template <typename T> struct Engine : EngineBase {
     if (ovl) RL_TRY(fork(st));                                    // bert | pinyin GRU + pho_model | glyph ResNet
     // Enqueue order (g_fwd_order): the host needs ~0.6 ms to enqueue the 150 launches of the bert stack; enqueued first (0) the two
     // shorter branches reach the GPU only after that, enqueued last (1) they start at once and bert joins them ~0.4 ms later.
-    if (!(ovl && g_fwd_order == 1)) RL_TRY(stack_forward(st, 0, L.bert, sh_bert, pl.bert, last.src_idx, nullptr, 0, &bert_h));
+    if (vr.bert && !(ovl && g_fwd_order == 1)) RL_TRY(stack_forward(st, 0, L.bert, sh_bert, pl.bert, last.src_idx, nullptr, 0, &bert_h));
     const T* top = bert_h;
+    if (!vr.bert) {      // Pho2Pretrain (models.py:1327-1336): pinyin GRU -> pho_model on the caller's stream - there is nothing to fork
+      RL_TRY(sync_optimizer(st));
+      RL_TRY(gru_forward(st));
+      RL_TRY(stack_forward(st, 1, L.pho, sh_pho, pl.pho, nullptr, wp<T>(pl.gru_out), 0, &top));
+    }
     if (vr.arch) {
       if (vr.pho) {
         RL_TRY(wait_opt(s_pho, opt_groups));                        // (pipelined sweep: pinyin / output stacks and the GRU are one piece)
@@ -1558,6 +1587,8 @@ template <typename T> struct Engine : EngineBase {
   void set_loss_grad(const float* g) override { loss_grad = g; }
   realise_decode dec_req = realise_decode();      // k == 0: no decode request installed
   void set_decode(const realise_decode* d) override { if (d) dec_req = *d; else dec_req = realise_decode(); }
+  realise_pred pred_req = realise_pred();         // pred_ids == nullptr: no ranking request installed
+  void set_pred(const realise_pred* d) override { if (d) pred_req = *d; else pred_req = realise_pred(); }
   // The decoder's / classifier's data gradient (K = Vp: the padding columns are exact zeros on both sides), the one place that chooses
   // between its two forms and applies the loss-gradient scalar.  Compacted bf16 rows of 1024 and more: split-K over the vocabulary,
   // the planes folded in plane order through fold_map into fold_out, scaled, with fold_drop (*folded = true).  Otherwise, and when the
@@ -1620,7 +1651,7 @@ template <typename T> struct Engine : EngineBase {
   }
 
   // stages = gradient buckets.  SpellBert: bert layer groups | bert embeddings.  The Arch3 family: 0 output_block | 1 fusion (+ glyph
-  // ResNet) | 2 pinyin branch (when present) | bert layer groups | bert embeddings
+  // ResNet) | 2 pinyin branch (when present) | bert layer groups | bert embeddings.  Pho2Pretrain (no bert stack): 0 head | 1 pinyin branch
   int first_bert_stage() const { return !vr.arch ? 0 : (vr.pho ? 3 : 2); }
   int stage_out_block(const Lane& la) {      // head + output_block; leaves d fused in gB (set 0)
     T* gA = wp<T>(pl.gA);
@@ -1648,7 +1679,7 @@ template <typename T> struct Engine : EngineBase {
     return resnet_backward(la, wp<T>(pl.r_dout));
   }
   int stage_pho(const Lane& la) {            // pho_model + GRU
-    T* g2 = wp<T>(pl.X2);
+    T* g2 = wp<T>(vr.arch ? pl.X2 : pl.gA);      // the gradient arrives from the fusion in X2, from the head (Pho2Pretrain) in gA
     T* gE = wp<T>(la.sc->gE);
     RL_TRY(layers_backward(la, 1, L.pho, sh_pho, pl.pho, cfg.pho_layers - 1, 0, g2));
     RL_TRY(emb_backward(la, 1, L.pho, pl.pho, nullptr, 0, g2, gE));       // gE = d gru_out (original order)
@@ -1695,7 +1726,8 @@ template <typename T> struct Engine : EngineBase {
     int rc = RL_OK;
     for (int s = first; rc == RL_OK && s <= last_stage; ++s) {
       hipStream_t fin = st;                  // the stream that runs last for bucket s
-      if (s >= b0) rc = stage_bert(bert, s - b0);
+      if (!vr.bert) rc = s == 0 ? stage_head(bert) : stage_pho(pho);      // Pho2Pretrain: 0 head | 1 pinyin branch, nothing else exists
+      else if (s >= b0) rc = stage_bert(bert, s - b0);
       else if (s == 0) rc = stage_out_block(bert);
       else if (s == 1) {                     // fusion (before the fork) + glyph ResNet
         rc = stage_fuse(st);

@@ -72,8 +72,10 @@ inline int64_t align64(int64_t x) { return (x + 63) & ~(int64_t)63; }
 // What a configuration computes: SpellBert is the bert stack alone, SpellBertPho2ResArch3 has every branch, the ablation model
 // (model_type 2, src/models_abla.py:33-96) what its switches keep, SpellBertPho2ResArch4 (model_type 3, models.py:1023-1170) every
 // branch with a softmax over the gates, SpellBertPho2ResArch3MLM (model_type 4, models.py:874-1020) Arch3 with BertOnlyMLMHead as
-// its classifier.  Every layout / engine decision reads this, not model_type.
+// its classifier, Pho2Pretrain (model_type 5, models.py:1286-1347) the pinyin branch alone under a BertOnlyMLMHead named cls2: no
+// bert stack, no fusion, no output block.  Every layout / engine decision reads this, not model_type.
 struct Variant {
+  bool bert = true;      // the bert stack under a (tied or untied) classifier; false: the model starts at the pinyin branch (model_type 5)
   bool arch = false;     // output_block behind a fusion of the branches (model_type 1, 2, 3, 4)
   bool pho = false;      // pinyin branch: pho_embeddings, pho_gru, pho_model
   bool res = false;      // glyph branch: glyph table, resnet, resnet_layernorm
@@ -85,6 +87,7 @@ struct Variant {
 };
 inline Variant variant_of(const realise_config& c) {
   Variant v;
+  if (c.model_type == 5) { v.bert = false; v.pho = true; v.mlm_head = true; return v; }
   v.arch = c.model_type == 1 || c.model_type == 2 || c.model_type == 3 || c.model_type == 4;
   if (!v.arch) return v;
   const bool abla = c.model_type == 2;
@@ -99,8 +102,12 @@ inline Variant variant_of(const realise_config& c) {
 // model_type 2 fields in range, sum fusion only with both branches (the reference's sum path adds None otherwise).  model_type 3 keeps
 // its glyph table as nn.Embedding(vocab, 1024) viewed as [N, 1, 32, 32] (models.py:1043,1134): one font, 32x32 glyphs, nothing else.
 // model_type 4 has the same table (models.py:894,985) and a decoder of its own (tie_cls_weight is a `pass`, models.py:915-917): untied only.
+// model_type 5 has no word table to tie its decoder to: untied only.  It is the pinyin branch without the glyph branch, and its config
+// says so in the branch switches (with_pho == 1, with_res == 0): a type-5 config that claims a glyph branch, such as another model's
+// config with the number changed, describes no model and is refused.
 inline bool variant_valid(const realise_config& c) {
-  if (c.model_type < 0 || c.model_type > 4) return false;
+  if (c.model_type < 0 || c.model_type > 5) return false;
+  if (c.model_type == 5) return c.tie_classifier == 0 && c.with_pho == 1 && c.with_res == 0;
   if (c.model_type == 3) return c.num_fonts == 1 && c.glyph_size == 32;
   if (c.model_type == 4) return c.num_fonts == 1 && c.glyph_size == 32 && c.tie_classifier == 0;
   if (c.model_type != 2) return true;
@@ -189,7 +196,32 @@ inline Layout build_layout(const realise_config& c) {
 
   const Variant vr = variant_of(c);
   int64_t begin = 0;
-  L.bert.layers.resize(c.bert_layers);
+  if (vr.bert) L.bert.layers.resize(c.bert_layers);
+  // the pinyin branch: pho_model, GRU, pinyin embedding (one bucket)
+  auto add_pho = [&]() {
+    L.pho.layers.resize(c.pho_layers);
+    add_layers_desc(L.pho, "pho_model.", c.pho_layers - 1, 0);
+    add_emb(L.pho, "pho_model.", false);
+    L.gru_w_hh = add(AR_TRAIN, "pho_gru.weight_hh_l0", {3 * H, H});
+    L.gru_b_hh = add(AR_TRAIN, "pho_gru.bias_hh_l0", {3 * H});
+    L.gru_w_ih = add(AR_TRAIN, "pho_gru.weight_ih_l0", {3 * H, H});
+    L.gru_b_ih = add(AR_TRAIN, "pho_gru.bias_ih_l0", {3 * H});
+    L.pho_emb = add(AR_TRAIN, "pho_embeddings.weight", {c.pho_vocab, H});
+    close_bucket(begin);
+  };
+  if (!vr.bert) {
+    // Pho2Pretrain (models.py:1286-1347): bucket 0 = BertOnlyMLMHead `cls2` in backward completion order, bucket 1 = the pinyin branch.
+    // num_hidden_layers is carried and ignored (models.py:1302 hard-wires the 4 pho layers); no bert.*, classifier.* or cls.* keys.
+    L.cls_b = add(AR_TRAIN, "cls2.predictions.bias", {V});
+    L.cls_w = add(AR_TRAIN, "cls2.predictions.decoder.weight", {V, H});
+    L.head_ln_g = add(AR_TRAIN, "cls2.predictions.transform.LayerNorm.weight", {H});
+    L.head_ln_b = add(AR_TRAIN, "cls2.predictions.transform.LayerNorm.bias", {H});
+    L.head_w = add(AR_TRAIN, "cls2.predictions.transform.dense.weight", {H, H});
+    L.head_b = add(AR_TRAIN, "cls2.predictions.transform.dense.bias", {H});
+    close_bucket(begin);
+    add_pho();
+    return L;
+  }
   // ---- bucket 0: classifier bias (+ untied weight), output_block
   if (vr.mlm_head) {
     // BertOnlyMLMHead (modeling_bert.py:419-462) in backward completion order: decoder bias and weight, the transform's LayerNorm, its dense
@@ -231,17 +263,7 @@ inline Layout build_layout(const realise_config& c) {
     }
     close_bucket(begin);
     // ---- bucket 2 (with the pinyin branch): pho_model, GRU, pinyin embedding
-    if (vr.pho) {
-      L.pho.layers.resize(c.pho_layers);
-      add_layers_desc(L.pho, "pho_model.", c.pho_layers - 1, 0);
-      add_emb(L.pho, "pho_model.", false);
-      L.gru_w_hh = add(AR_TRAIN, "pho_gru.weight_hh_l0", {3 * H, H});
-      L.gru_b_hh = add(AR_TRAIN, "pho_gru.bias_hh_l0", {3 * H});
-      L.gru_w_ih = add(AR_TRAIN, "pho_gru.weight_ih_l0", {3 * H, H});
-      L.gru_b_ih = add(AR_TRAIN, "pho_gru.bias_ih_l0", {3 * H});
-      L.pho_emb = add(AR_TRAIN, "pho_embeddings.weight", {c.pho_vocab, H});
-      close_bucket(begin);
-    }
+    if (vr.pho) add_pho();
     // models.py:674-679: one font -> nn.Embedding "char_images.weight" [V, 1024]; several -> Parameter [V, F, 32, 32].  Same bytes.
     if (vr.res) {
       if (c.num_fonts == 1) L.glyph = add(AR_FROZEN, "char_images.weight", {V, (int64_t)c.glyph_size * c.glyph_size});

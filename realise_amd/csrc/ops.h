@@ -129,9 +129,20 @@ template <typename T> int dropout_apply(hipStream_t st, const T* x, T* y, int ro
 // (cc.act_idx[j] = its token row, cc.inv[row] = j or -1, *cc.n_act = how many; all written here); rows outside the loss are neither
 // visited nor written.  The classifier's data / weight gradients then run over *n_act rows instead of all of them.
 struct CeCompact { int* act_idx = nullptr; int* inv = nullptr; int* n_act = nullptr; int phase = 0; int logits_compact = 0; };      // (phase / logits_compact: ce_loss)
+// The ranking pass (models.py:1346 `active_logits.argmax(dim=-1)`, which run_pretrain.py:100-104 scores accuracy from): with
+// pr != nullptr the row kernels run their ranking instantiation - the row maximum carries its column under argmax_rows' rule (on the
+// stored value a beats b when a > b or a is NaN and b is not, the lower column wins on equal values, -0.0 ranks as +0.0, the tail
+// [V, ld) enters nothing), taken from the logits as read, before an in-place gradient row overwrites them.  The workgroup of an
+// active row writes pred[j] (and labels_out[j], nullable) and adds 1 to *hits (zeroed here) when pred == label.  j: compacted
+// gradient rows (cc.act_idx) - the j-th active row; otherwise inv[row] when inv is given (a list made by a phase-1 call), else the
+// row itself, where rows outside the loss get pred = -1.  *n_active (nullable) = *n_src.  j >= capacity (> 0) is not written.
+// pr == nullptr: the kernels, the launches and the results are what they were before the ranking pass existed.
+struct CePred { int64_t* pred = nullptr; int64_t* labels_out = nullptr; int32_t* hits = nullptr; int32_t* n_active = nullptr;
+                const int* inv = nullptr; const int* n_src = nullptr; int64_t capacity = 0; };
 template <typename T>
 int ce_loss(hipStream_t st, const T* logits, int64_t ld, const int64_t* labels, const int64_t* loss_mask, int rows, int V,
-            float* loss_out, float* count_buf, T* dlogits, float* row_loss = nullptr, int64_t ld_dl = 0, const CeCompact& cc = CeCompact());
+            float* loss_out, float* count_buf, T* dlogits, float* row_loss = nullptr, int64_t ld_dl = 0, const CeCompact& cc = CeCompact(),
+            const CePred* pr = nullptr);
 // out[j] = in[idx[j]], j < *n_dev (rows of H elements); out[row] = inv[row] >= 0 ? in[inv[row]] * dropout mask : 0
 template <typename T> int gather_rows(hipStream_t st, const T* in, const int* idx, const int* n_dev, int max_rows, int H, T* out);
 // scale_dev (nullable): a device scalar multiplied into every stored value - the incoming loss gradient, never read on the host

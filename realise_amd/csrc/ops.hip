@@ -1670,11 +1670,57 @@ __global__ void __launch_bounds__(1024) active_rows_kernel(const int64_t* __rest
   if (threadIdx.x == 0) { *n_act = base_s; *count = (float)base_s; }
 }
 
-template <typename T>
+// the project's ranking rule (argmax_rows, gemm_nt_decode, the ranking cross-entropy): a NaN beats a number, then the larger value,
+// then the lower column (-0.0 == +0.0: the lower column)
+__device__ __forceinline__ bool amax_better(float v, int i, float bv, int bi) {
+  const bool vn = v != v, bn = bv != bv;
+  if (vn || bn) return vn && (!bn || i < bi);
+  return v > bv || (v == bv && i < bi);
+}
+// The ranking switch of the cross-entropy row kernels (ops.h: CePred).  Off, a kernel takes an empty struct in the place of the request
+// and every ranking statement is discarded at compile time: the instantiation is the kernel as it was.  On, each thread looks among the
+// elements it already holds for the lowest column equal to the row maximum - one compare and one select per element, in the loop that
+// sums the exponentials -, the workgroup reduces to the minimum and thread 0 writes the row's prediction.
+struct CeNoPred {};
+template <bool RANK> struct CeRankArg { typedef CeNoPred type; };
+template <> struct CeRankArg<true> { typedef CePred type; };
+// Fast form (every row without a NaN): the row maximum mx is known from the pass's own reduction, so the prediction is the LOWEST
+// column whose value equals mx (float equality: -0.0 == +0.0) - one compare and one select per element, then an integer minimum over the
+// workgroup (ce_rank_min).  The comparator's other cases, uniform per workgroup and rare: a row whose sum of exponentials is NaN (it
+// holds a NaN, or a +inf) is scanned once more for its lowest NaN column, which wins if there is one; a row whose every element is
+// -inf matches nothing (the maximum is clamped at -3e38) and gets column 0, the lowest of its equal values.
+__device__ __forceinline__ int ce_rank_min(int bi, int* si) {
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) bi = min(bi, __shfl_xor(bi, o, 64));
+  __syncthreads();
+  if ((threadIdx.x & 63) == 0) si[threadIdx.x >> 6] = bi;
+  __syncthreads();
+  return min(min(si[0], si[1]), min(si[2], si[3]));
+}
+__device__ __forceinline__ void ce_rank_write(int bi, const CePred& pr, int64_t j, int64_t lab64) {
+  if (threadIdx.x == 0) {
+    if (j >= 0 && (pr.capacity <= 0 || j < pr.capacity)) {
+      if (pr.pred != nullptr) pr.pred[j] = bi;
+      if (pr.labels_out != nullptr) pr.labels_out[j] = lab64;
+    }
+    if (pr.hits != nullptr && (int64_t)bi == lab64) atomicAdd(pr.hits, 1);
+  }
+}
+// where an active row's prediction goes: compacted form - the workgroup's index; a given list - the row's entry; else the row
+__device__ __forceinline__ int64_t ce_rank_slot(const CePred& pr, const int* act_idx, int row) {
+  if (act_idx != nullptr) return (int64_t)blockIdx.x;
+  return pr.inv != nullptr ? (int64_t)pr.inv[row] : (int64_t)row;
+}
+// a row outside the loss, dense form without a list: its prediction is -1
+__device__ __forceinline__ void ce_rank_inactive(const CePred& pr, const int* act_idx, int row) {
+  if (threadIdx.x == 0 && act_idx == nullptr && pr.inv == nullptr && pr.pred != nullptr && (pr.capacity <= 0 || row < pr.capacity)) pr.pred[row] = -1;
+}
+
+template <typename T, bool RANK = false>
 __global__ void __launch_bounds__(256)
 ce_kernel(const T* __restrict__ logits, int64_t ld, const int64_t* __restrict__ labels, const int64_t* __restrict__ loss_mask,
           int V, float* loss_out, const float* __restrict__ count, T* __restrict__ dlogits, float* __restrict__ row_loss, int64_t ld_dl,
-          const int* __restrict__ act_idx, const int* __restrict__ n_act, int logits_compact) {
+          const int* __restrict__ act_idx, const int* __restrict__ n_act, int logits_compact, typename CeRankArg<RANK>::type pr) {
   __shared__ float sm[4];
   // compacted form (act_idx != nullptr): workgroup j works on the j-th ACTIVE row and writes gradient row j; the rows outside the loss
   // are not visited at all (their loss terms were zeroed by active_rows_kernel, their gradient rows do not exist)
@@ -1691,6 +1737,7 @@ ce_kernel(const T* __restrict__ logits, int64_t ld, const int64_t* __restrict__ 
     if (row_loss != nullptr && threadIdx.x == 0) row_loss[row] = 0.f;
     if (dx != nullptr)
       for (int c = threadIdx.x * 4; c < V; c += 1024) store4<T>(dx + c, floatx4{0.f, 0.f, 0.f, 0.f});
+    if constexpr (RANK) ce_rank_inactive(pr, act_idx, row);
     return;
   }
   float mx = -3.0e38f;
@@ -1700,11 +1747,31 @@ ce_kernel(const T* __restrict__ logits, int64_t ld, const int64_t* __restrict__ 
   }
   mx = block_reduce(mx, sm, true);
   float s = 0.f;
+  int bi = 0x7fffffff;
   for (int c = threadIdx.x * 4; c < V; c += 1024) {
     const floatx4 v = load4<T>(x + c);
     s += exp_t<T>(v[0] - mx) + exp_t<T>(v[1] - mx) + exp_t<T>(v[2] - mx) + exp_t<T>(v[3] - mx);
+    if constexpr (RANK) {      // (columns ascend inside a thread: the first match is its lowest)
+#pragma unroll
+      for (int j = 3; j >= 0; --j) bi = v[j] == mx ? min(bi, c + j) : bi;
+    }
   }
   s = block_reduce(s, sm, false);
+  if constexpr (RANK) {      // (this kernel is never run in place: the logits are still there for the general walk)
+    __shared__ int rk_i[4];
+    bi = ce_rank_min(bi, rk_i);
+    if (s != s) {
+      int bn = 0x7fffffff;
+      for (int c = threadIdx.x; c < V; c += 256) {
+        const float v = to_f<T>(x[c]);
+        bn = v != v ? min(bn, c) : bn;
+      }
+      bn = ce_rank_min(bn, rk_i);
+      bi = bn != 0x7fffffff ? bn : bi;
+    }
+    bi = bi == 0x7fffffff ? 0 : bi;
+    ce_rank_write(bi, pr, ce_rank_slot(pr, act_idx, row), lab64);
+  }
   const float inv_n = 1.0f / count[0];
   // a label outside [0, V) is an error PyTorch raises on; here it poisons the loss (NaN) instead of reading out of bounds
   const bool lab_ok = lab64 >= 0 && lab64 < V;
@@ -1730,11 +1797,30 @@ ce_kernel(const T* __restrict__ logits, int64_t ld, const int64_t* __restrict__ 
 // is read ONCE into registers (NCH 16-byte chunks per thread, all loads in flight together) and the maximum, the sum of exponentials
 // and the gradient row come from the registers; the generic kernel walks the row three times with 8-byte loads and, with thousands of
 // rows in flight, every walk comes from HBM (PMC round 3: 659 MB read per launch for 207 MB of active rows).
+// the lowest column of this thread's chunks whose value is a NaN, or INT_MAX - on the packed bf16 bits (a NaN: exponent all ones and a
+// mantissa, (h & 0x7fff) > 0x7f80; element 2w of a chunk is the low half of word w).  Descending over the chunks and inside a chunk: a later
+// match is a lower column and simply replaces the earlier one.  (The filler chunks beyond the row are -inf: no NaN.)
 template <int NCH>
+__device__ __forceinline__ int ce_row16_nan_scan(const uint4 (&r)[NCH]) {
+  int bi = 0x7fffffff;
+#pragma unroll
+  for (int i = NCH - 1; i >= 0; --i) {
+    const uint32_t w[4] = {r[i].x, r[i].y, r[i].z, r[i].w};
+    int m = 8;
+#pragma unroll
+    for (int q = 3; q >= 0; --q) {
+      m = ((w[q] >> 16) & 0x7fffu) > 0x7f80u ? 2 * q + 1 : m;
+      m = (w[q] & 0x7fffu) > 0x7f80u ? 2 * q : m;
+    }
+    bi = m < 8 ? 8 * ((int)threadIdx.x + 256 * i) + m : bi;
+  }
+  return bi;
+}
+template <int NCH, bool RANK = false>
 __global__ void __launch_bounds__(256)
 ce_row16_kernel(const bf16_t* logits, int64_t ld, const int64_t* __restrict__ labels, const int64_t* __restrict__ loss_mask,
                 int V, float* loss_out, const float* __restrict__ count, bf16_t* dlogits, float* __restrict__ row_loss, int64_t ld_dl,
-                const int* __restrict__ act_idx, const int* __restrict__ n_act, int logits_compact) {
+                const int* __restrict__ act_idx, const int* __restrict__ n_act, int logits_compact, typename CeRankArg<RANK>::type pr) {
   __shared__ float sm[4];
   if (act_idx != nullptr && (int)blockIdx.x >= *n_act) return;
   const int row = act_idx != nullptr ? act_idx[blockIdx.x] : (int)blockIdx.x;
@@ -1751,6 +1837,7 @@ ce_row16_kernel(const bf16_t* logits, int64_t ld, const int64_t* __restrict__ la
     if (row_loss != nullptr && threadIdx.x == 0) row_loss[row] = 0.f;
     if (dx != nullptr)
       for (int k = threadIdx.x; k < nch; k += 256) *(uint4*)(dx + 8 * k) = uint4{0u, 0u, 0u, 0u};
+    if constexpr (RANK) ce_rank_inactive(pr, act_idx, row);
     return;
   }
   uint4 r[NCH];
@@ -1776,14 +1863,31 @@ ce_row16_kernel(const bf16_t* logits, int64_t ld, const int64_t* __restrict__ la
   }
   mx = block_reduce(mx, sm, true);
   float s = 0.f;
+  int bi = 0x7fffffff;
 #pragma unroll
   for (int i = 0; i < NCH; ++i) {
     float v[8];
     unpack8(r[i], v);
 #pragma unroll
     for (int j = 0; j < 8; ++j) s += exp_t<bf16_t>(v[j] - mx);
+    if constexpr (RANK) {      // the chunk's lowest column equal to mx, on the values the sum just used (chunks ascend: the first match stays)
+      int m = 8;
+#pragma unroll
+      for (int j = 7; j >= 0; --j) m = v[j] == mx ? j : m;
+      bi = min(bi, m < 8 ? 8 * ((int)threadIdx.x + 256 * i) + m : 0x7fffffff);
+    }
   }
   s = block_reduce(s, sm, false);
+  if constexpr (RANK) {      // from the registers: the row as read, whatever other waves have stored over it since (in-place form)
+    __shared__ int rk_i[4];
+    bi = ce_rank_min(bi, rk_i);
+    if (s != s) {      // a NaN (or +inf) in the row: the lowest NaN column wins, still from the registers
+      const int bn = ce_rank_min(ce_row16_nan_scan<NCH>(r), rk_i);
+      bi = bn != 0x7fffffff ? bn : bi;
+    }
+    bi = bi == 0x7fffffff ? 0 : bi;
+    ce_rank_write(bi, pr, ce_rank_slot(pr, act_idx, row), lab64);
+  }
   const float inv_n = 1.0f / count[0];
   const bool lab_ok = lab64 >= 0 && lab64 < V;
   const int lab = lab_ok ? (int)lab64 : 0;
@@ -1809,15 +1913,32 @@ ce_row16_kernel(const bf16_t* logits, int64_t ld, const int64_t* __restrict__ la
   }
 }
 template <typename T>
-static bool ce_row16_launch(hipStream_t, const T*, int64_t, const int64_t*, const int64_t*, int, int, float*, float*, T*, float*, int64_t, const int*, const int*, int) { return false; }
+static bool ce_row16_launch(hipStream_t, const T*, int64_t, const int64_t*, const int64_t*, int, int, float*, float*, T*, float*, int64_t, const int*, const int*, int,
+                            const CePred*) { return false; }
 template <>
 bool ce_row16_launch<bf16_t>(hipStream_t st, const bf16_t* logits, int64_t ld, const int64_t* labels, const int64_t* loss_mask, int rows, int V,
-                             float* loss_out, float* count_buf, bf16_t* dlogits, float* row_loss, int64_t ld_dl, const int* act_idx, const int* n_act, int compact) {
+                             float* loss_out, float* count_buf, bf16_t* dlogits, float* row_loss, int64_t ld_dl, const int* act_idx, const int* n_act, int compact,
+                             const CePred* pr) {
   constexpr int NCH = 11;          // 256 threads x 11 chunks x 8 = 22528 >= 21128
   if (!g_ce_fast || (V & 7) || (ld & 7) || (ld_dl & 7) || V > 256 * 8 * NCH || ((uintptr_t)logits & 15) || ((uintptr_t)dlogits & 15)) return false;
-  hipLaunchKernelGGL((ce_row16_kernel<NCH>), dim3(rows), dim3(256), 0, st, logits, ld, labels, loss_mask, V, loss_out, count_buf, dlogits, row_loss, ld_dl,
-                     act_idx, n_act, compact);
+  if (pr != nullptr)
+    hipLaunchKernelGGL((ce_row16_kernel<NCH, true>), dim3(rows), dim3(256), 0, st, logits, ld, labels, loss_mask, V, loss_out, count_buf, dlogits, row_loss,
+                       ld_dl, act_idx, n_act, compact, *pr);
+  else
+    hipLaunchKernelGGL((ce_row16_kernel<NCH>), dim3(rows), dim3(256), 0, st, logits, ld, labels, loss_mask, V, loss_out, count_buf, dlogits, row_loss, ld_dl,
+                       act_idx, n_act, compact, CeNoPred());
   return true;
+}
+// the generic row kernel, ranking or not
+template <typename T>
+static void ce_generic_launch(hipStream_t st, const T* logits, int64_t ld, const int64_t* labels, const int64_t* loss_mask, int rows, int V, float* loss_out,
+                              float* count_buf, T* dlogits, float* row_loss, int64_t ld_dl, const int* act_idx, const int* n_act, int compact, const CePred* pr) {
+  if (pr != nullptr)
+    hipLaunchKernelGGL((ce_kernel<T, true>), dim3(rows), dim3(256), 0, st, logits, ld, labels, loss_mask, V, loss_out, count_buf, dlogits, row_loss, ld_dl,
+                       act_idx, n_act, compact, *pr);
+  else
+    hipLaunchKernelGGL((ce_kernel<T>), dim3(rows), dim3(256), 0, st, logits, ld, labels, loss_mask, V, loss_out, count_buf, dlogits, row_loss, ld_dl,
+                       act_idx, n_act, compact, CeNoPred());
 }
 
 // loss = sum of the per-row terms in a fixed order (256 strided partial sums, then a fixed tree): bitwise reproducible
@@ -1835,9 +1956,13 @@ __global__ void __launch_bounds__(256) ce_fold_kernel(const float* __restrict__ 
 }
 template <typename T>
 int ce_loss(hipStream_t st, const T* logits, int64_t ld, const int64_t* labels, const int64_t* loss_mask, int rows, int V,
-            float* loss_out, float* count_buf, T* dlogits, float* row_loss, int64_t ld_dl, const CeCompact& cc) {
+            float* loss_out, float* count_buf, T* dlogits, float* row_loss, int64_t ld_dl, const CeCompact& cc, const CePred* pr) {
   if (ld_dl <= 0) ld_dl = ld;
   if ((V & 3) || (ld & 3) || (ld_dl & 3) || ld_dl < V) return RL_ERR_ARG;
+  if (pr != nullptr && cc.phase != 1) {      // the ranking pass: the hit counter starts at zero, the active-row count is passed on
+    if (pr->pred == nullptr) return RL_ERR_ARG;
+    if (pr->hits != nullptr && hipMemsetAsync(pr->hits, 0, sizeof(int32_t), st) != hipSuccess) return RL_ERR_LAUNCH;
+  }
   if (cc.act_idx != nullptr) {       // compacted gradient rows (needs the per-row loss terms: the ordered fold is the only sum)
     if (row_loss == nullptr || cc.inv == nullptr || cc.n_act == nullptr || rows > 65536) return RL_ERR_ARG;
     // phases: 1 = list the active rows, 2 = loss + gradient rows, 0 = both (cc.logits_compact needs the list before the logits exist:
@@ -1845,27 +1970,32 @@ int ce_loss(hipStream_t st, const T* logits, int64_t ld, const int64_t* labels, 
     if (cc.phase != 2)
       hipLaunchKernelGGL(active_rows_kernel, dim3(1), dim3(1024), 0, st, loss_mask, labels, rows, cc.act_idx, cc.inv, cc.n_act, count_buf, row_loss);
     if (cc.phase == 1) return RL_LAUNCH_CHECK();
+    if (pr != nullptr && pr->n_active != nullptr &&
+        hipMemcpyAsync(pr->n_active, cc.n_act, sizeof(int32_t), hipMemcpyDeviceToDevice, st) != hipSuccess) return RL_ERR_LAUNCH;
     const bool fast = ce_row16_launch<T>(st, logits, ld, labels, loss_mask, rows, V, loss_out, count_buf, dlogits, row_loss, ld_dl, (const int*)cc.act_idx,
-                                         (const int*)cc.n_act, cc.logits_compact);
+                                         (const int*)cc.n_act, cc.logits_compact, pr);
     if (!fast) {
       if (cc.logits_compact && (const void*)logits == (const void*)dlogits) return RL_ERR_ARG;      // (the generic kernel walks a row three times: not in place)
-      hipLaunchKernelGGL((ce_kernel<T>), dim3(rows), dim3(256), 0, st, logits, ld, labels, loss_mask, V, loss_out, count_buf, dlogits, row_loss, ld_dl,
-                         (const int*)cc.act_idx, (const int*)cc.n_act, cc.logits_compact);
+      ce_generic_launch<T>(st, logits, ld, labels, loss_mask, rows, V, loss_out, count_buf, dlogits, row_loss, ld_dl, (const int*)cc.act_idx,
+                           (const int*)cc.n_act, cc.logits_compact, pr);
     }
     hipLaunchKernelGGL(ce_fold_kernel, dim3(1), dim3(256), 0, st, row_loss, rows, loss_out);
     return RL_LAUNCH_CHECK();
   }
+  if (pr != nullptr && pr->n_active != nullptr && pr->n_src != nullptr &&
+      hipMemcpyAsync(pr->n_active, pr->n_src, sizeof(int32_t), hipMemcpyDeviceToDevice, st) != hipSuccess) return RL_ERR_LAUNCH;
   (void)hipMemsetAsync(loss_out, 0, sizeof(float), st);
   (void)hipMemsetAsync(count_buf, 0, sizeof(float), st);
   hipLaunchKernelGGL(count_active_kernel, dim3(64), dim3(256), 0, st, loss_mask, labels, rows, count_buf);
-  if (!ce_row16_launch<T>(st, logits, ld, labels, loss_mask, rows, V, loss_out, count_buf, dlogits, row_loss, ld_dl, nullptr, nullptr, 0))
-    hipLaunchKernelGGL((ce_kernel<T>), dim3(rows), dim3(256), 0, st, logits, ld, labels, loss_mask, V, loss_out, count_buf, dlogits, row_loss, ld_dl,
-                       (const int*)nullptr, (const int*)nullptr, 0);
+  if (!ce_row16_launch<T>(st, logits, ld, labels, loss_mask, rows, V, loss_out, count_buf, dlogits, row_loss, ld_dl, nullptr, nullptr, 0, pr))
+    ce_generic_launch<T>(st, logits, ld, labels, loss_mask, rows, V, loss_out, count_buf, dlogits, row_loss, ld_dl, nullptr, nullptr, 0, pr);
   if (row_loss != nullptr) hipLaunchKernelGGL(ce_fold_kernel, dim3(1), dim3(256), 0, st, row_loss, rows, loss_out);
   return RL_LAUNCH_CHECK();
 }
-template int ce_loss<bf16_t>(hipStream_t, const bf16_t*, int64_t, const int64_t*, const int64_t*, int, int, float*, float*, bf16_t*, float*, int64_t, const CeCompact&);
-template int ce_loss<float>(hipStream_t, const float*, int64_t, const int64_t*, const int64_t*, int, int, float*, float*, float*, float*, int64_t, const CeCompact&);
+template int ce_loss<bf16_t>(hipStream_t, const bf16_t*, int64_t, const int64_t*, const int64_t*, int, int, float*, float*, bf16_t*, float*, int64_t, const CeCompact&,
+                             const CePred*);
+template int ce_loss<float>(hipStream_t, const float*, int64_t, const int64_t*, const int64_t*, int, int, float*, float*, float*, float*, int64_t, const CeCompact&,
+                            const CePred*);
 
 // out[j] = in[idx[j]] for j < *n (rows of H elements, 16 bytes per lane)
 template <typename T>
@@ -2579,11 +2709,6 @@ template int segment_sum_chw4<float>(hipStream_t, const float*, const int*, int,
 // Row-wise argmax: one 256-thread workgroup per row, 16-byte loads, (value, index) pairs reduced with the
 // first-occurrence tie rule.
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ bool amax_better(float v, int i, float bv, int bi) {
-  const bool vn = v != v, bn = bv != bv;
-  if (vn || bn) return vn && (!bn || i < bi);
-  return v > bv || (v == bv && i < bi);
-}
 template <typename T>
 __global__ void __launch_bounds__(256) argmax_kernel(const T* __restrict__ logits, int64_t ld, int V, int64_t* __restrict__ ids) {
   __shared__ float sv[4];

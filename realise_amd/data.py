@@ -83,6 +83,20 @@ def synthetic_batch(batch_size, seq_len, vocab_size=21128, seed=0, with_pho=True
     return batch
 
 
+def synthetic_pretrain_batch(batch_size, seq_len, seed=0, hole_rate=0.25, empty_sentence=None, **kw):
+    """A pretraining-shaped batch (run_pretrain.py:51-78 + models.py:1309-1316): ``synthetic_batch`` whose ``loss_masks`` has holes - the
+    pretraining mask is 1 on single Chinese characters only, so punctuation, digits and word pieces inside a sentence carry no loss -
+    and, with ``empty_sentence = b``, one sentence without any loss position.  The model reads ``tgt_idx`` as its input."""
+    batch = synthetic_batch(batch_size, seq_len, seed=seed, **kw)
+    g = np.random.Generator(np.random.Philox(key=[0x9E7A1, seed]))
+    lm = batch["loss_masks"].numpy().copy()
+    lm[g.random(lm.shape) < hole_rate] = 0
+    if empty_sentence is not None:
+        lm[empty_sentence] = 0
+    batch["loss_masks"] = torch.from_numpy(lm)
+    return batch
+
+
 def synthetic_vocab(vocab_size=21128):
     """A BERT-style Chinese vocabulary stand-in (``vocab.txt`` of chinese-roberta-wwm-ext is not in the tree): the special
     tokens at their real ids ([PAD] 0, [UNK] 100, [CLS] 101, [SEP] 102, [MASK] 103), ``[unusedN]`` fillers, printable ASCII,

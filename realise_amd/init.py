@@ -122,6 +122,27 @@ def tensor_specs(cfg, model_type="arch3"):
         msg = "%s (%s) keeps its glyphs in char_images.weight [V, 1024] (models.py:%d): it needs num_fonts=1, got %d"
         raise ValueError(msg % (model_type, v.reference_class, v.one_font_line, cfg["num_fonts"]))
     arch, with_pho, with_res, gate, G = v.arch, v.pho, v.res, v.gate, v.gates
+
+    def pho_branch():
+        specs.append(("pho_embeddings.weight", (cfg["pho_vocab_size"], H), "normal"))
+        specs.append(("pho_gru.weight_ih_l0", (3 * H, H), "gru"))
+        specs.append(("pho_gru.weight_hh_l0", (3 * H, H), "gru"))
+        specs.append(("pho_gru.bias_ih_l0", (3 * H,), "gru"))
+        specs.append(("pho_gru.bias_hh_l0", (3 * H,), "gru"))
+        bert("pho_model.", cfg["pho_layers"])
+
+    def mlm_head(p):      # BertOnlyMLMHead (modeling_bert.py:419-462); init_weights (modeling_bert.py:496-506): Linear weights normal, biases zero, LayerNorm one / zero; the decoder has no bias of its own
+        specs.append((p + "predictions.bias", (V,), "zeros"))
+        specs.append((p + "predictions.transform.dense.weight", (H, H), "normal"))
+        specs.append((p + "predictions.transform.dense.bias", (H,), "zeros"))
+        specs.append((p + "predictions.transform.LayerNorm.weight", (H,), "ones"))
+        specs.append((p + "predictions.transform.LayerNorm.bias", (H,), "zeros"))
+        specs.append((p + "predictions.decoder.weight", (V, H), "normal"))
+
+    if not v.bert:      # Pho2Pretrain (models.py:1286-1305): the pinyin branch and the head cls2, nothing else
+        pho_branch()
+        mlm_head(v.head_prefix)
+        return specs
     if arch and with_res:
         F_ = cfg["num_fonts"]
         if F_ == 1:      # models.py:674-676: the single-font model keeps the table as an nn.Embedding [V, 1024]
@@ -131,12 +152,7 @@ def tensor_specs(cfg, model_type="arch3"):
     bert("bert.", cfg["num_hidden_layers"])
     if arch:
         if with_pho:
-            specs.append(("pho_embeddings.weight", (cfg["pho_vocab_size"], H), "normal"))
-            specs.append(("pho_gru.weight_ih_l0", (3 * H, H), "gru"))
-            specs.append(("pho_gru.weight_hh_l0", (3 * H, H), "gru"))
-            specs.append(("pho_gru.bias_ih_l0", (3 * H,), "gru"))
-            specs.append(("pho_gru.bias_hh_l0", (3 * H,), "gru"))
-            bert("pho_model.", cfg["pho_layers"])
+            pho_branch()
         if with_res:
             chans = tower_channels(cfg)
             for b in range(1, len(chans)):
@@ -161,13 +177,8 @@ def tensor_specs(cfg, model_type="arch3"):
             specs.append(("gate_net.weight", (G, (G + 1) * H), "normal"))
             specs.append(("gate_net.bias", (G,), "zeros"))
         bert("output_block.", cfg["out_layers"])
-    if v.mlm_head:      # BertOnlyMLMHead (modeling_bert.py:419-462); init_weights (modeling_bert.py:496-506): Linear weights normal, biases zero, LayerNorm one / zero; the decoder has no bias of its own
-        specs.append(("cls.predictions.bias", (V,), "zeros"))
-        specs.append(("cls.predictions.transform.dense.weight", (H, H), "normal"))
-        specs.append(("cls.predictions.transform.dense.bias", (H,), "zeros"))
-        specs.append(("cls.predictions.transform.LayerNorm.weight", (H,), "ones"))
-        specs.append(("cls.predictions.transform.LayerNorm.bias", (H,), "zeros"))
-        specs.append(("cls.predictions.decoder.weight", (V, H), "normal"))
+    if v.mlm_head:
+        mlm_head(v.head_prefix)
         return specs
     specs.append(("classifier.weight", (V, H), "normal"))
     specs.append(("classifier.bias", (V,), "zeros"))

@@ -538,6 +538,10 @@ class RealiseModule(nn.Module):
                               scratch=torch.empty(need, dtype=torch.uint8, device=self.device))
         return cache[key]
 
+    def _install_requests(self):
+        """called by ``_forward`` once the engine exists and is bound, before the engine call: a subclass installs what its forward
+        asks the engine for beyond the batch (models_pretrain.py: the ranking request)"""
+
     def _forward(self, batch, topk):
         self._raise_on_bad_ids()
         src = self._dev(batch["src_idx"])
@@ -598,6 +602,7 @@ class RealiseModule(nn.Module):
             cb.pho_idx, cb.pho_perm, cb.pho_lens_sorted = pho_idx.data_ptr(), perm_d.data_ptr(), lens_d.data_ptr()
             cb.n_alive = alive
         self._ensure_engine(B, S, cb.Tp)
+        self._install_requests()
         tdt = _DTYPES[self.compute_dtype][1]
         self._fwd_gen += 1
         # K13 (round 6): a training forward whose caller reads the loss alone (`model.train_logits = False`, what realise_amd.trainer
@@ -737,7 +742,7 @@ class RealiseModule(nn.Module):
     def _begin_gradient_pass(self):
         """detached gradients (our zero_grad(), or an optimizer's zero_grad(set_to_none=True)) mean "start from zero": the engine
         does that itself - a one-launch partial fill + overwriting weight-gradient GEMMs (realise_engine_set_grads_fresh)"""
-        sentinel = self._views["cls.predictions.bias" if self.variant.mlm_head else "classifier.bias"][3]
+        sentinel = self._views[self.variant.head_prefix + "predictions.bias" if self.variant.mlm_head else "classifier.bias"][3]
         if sentinel.grad is None or getattr(self, "_zero_pending", False):
             _capi.load().realise_engine_set_grads_fresh(self._engine, 1)
             self._zero_pending = False

@@ -33,13 +33,45 @@ def make_features(examples, max_seq_length):
     return batch
 
 
-def data_helper(items, batch_size, max_seq_length, build_batch, tokenizer=None, is_eval=False, seed=None):
-    """run.py:104-123: shuffle (train), then yield feature batches."""
+def make_pretrain_features(examples, max_seq_length, tokenizer=None, vocab=None):
+    """run_pretrain.py:51-78: truncate / pad ``src_idx`` and ``tgt_idx`` to max_seq_length; ``masks`` = 1 on the kept tokens of
+    ``tgt_idx`` (the model reads the targets, models.py:1319); ``loss_masks`` = 1 where the kept target token is exactly one CJK
+    character (run_pretrain.py:65-68) - [CLS], [SEP], punctuation, digits, word pieces carry no loss, so the mask has holes and a
+    sentence may have no loss position at all.  The tokens come from ``tokenizer.convert_ids_to_tokens`` or from ``vocab`` (a list:
+    id -> token)."""
+    from .glyph import is_cjk
+    if tokenizer is None and vocab is None:
+        raise ValueError("make_pretrain_features needs a tokenizer or a vocabulary list to tell the Chinese characters")
+    batch = {k: [] for k in ("id", "src", "tgt", "tokens_size", "lengths", "src_idx", "tgt_idx", "masks", "loss_masks")}
+    for e in examples:
+        for k in ("id", "src", "tgt", "tokens_size", "lengths"):
+            batch[k].append(e.get(k))
+        for k in ("src_idx", "tgt_idx"):
+            seq = list(e[k])[:max_seq_length]
+            pad = max_seq_length - len(seq)
+            batch[k].append(seq + [0] * pad)
+            if k == "tgt_idx":
+                batch["masks"].append([1] * len(seq) + [0] * pad)
+                tokens = tokenizer.convert_ids_to_tokens(seq) if tokenizer is not None else [vocab[i] for i in seq]
+                loss_mask = [0] * max_seq_length
+                for i, token in enumerate(tokens):
+                    if len(token) == 1 and is_cjk(ord(token)):
+                        loss_mask[i] = 1
+                batch["loss_masks"].append(loss_mask)
+    for k in ("src_idx", "tgt_idx", "masks", "loss_masks"):
+        batch[k] = torch.tensor(batch[k], dtype=torch.long)
+    return batch
+
+
+def data_helper(items, batch_size, max_seq_length, build_batch, tokenizer=None, is_eval=False, seed=None, features=None):
+    """run.py:104-123: shuffle (train), then yield feature batches.  ``features(examples, max_seq_length)``: the feature builder
+    (default ``make_features``; the pretraining loop passes one made from ``make_pretrain_features``)."""
     items = list(items)
+    features = features or make_features
     if not is_eval:
         (random.Random(seed) if seed is not None else random).shuffle(items)
     for i in range(0, len(items), batch_size):
-        yield build_batch(make_features(items[i:i + batch_size], max_seq_length), tokenizer)
+        yield build_batch(features(items[i:i + batch_size], max_seq_length), tokenizer)
 
 
 def shard(items, rank, world):
@@ -51,7 +83,7 @@ def shard(items, rank, world):
 def train(model, items, *, batch_size=64, max_seq_length=128, epochs=1, lr=5e-5, adam_epsilon=1e-8, weight_decay=0.0,
           warmup_steps=0, max_grad_norm=1.0, device="cuda", distributed=False, build_batch=None, tokenizer=None,
           gradient_accumulation_steps=1, max_steps=-1, logging_steps=0, save_steps=0, output_dir=None, training_args=None,
-          log_every=0, log_fn=None, seed=17, return_global_step=False):
+          log_every=0, log_fn=None, seed=17, return_global_step=False, features=None):
     """the hot loop of run.py:125-237 with the fused optimizer.  Returns the mean loss per optimizer step (``tr_loss / global_step``,
     run.py:237); with ``return_global_step=True`` the reference's pair ``(global_step, tr_loss / global_step)``.
 
@@ -68,7 +100,9 @@ def train(model, items, *, batch_size=64, max_seq_length=128, epochs=1, lr=5e-5,
       ``save_pretrained`` and ``training_args.bin`` (``torch.save(training_args, ...)``: whatever object the caller hands over,
       the reference saves its argparse namespace).
     The per-step ``loss.item()`` of run.py:202 is a device-side accumulation here (no host synchronisation in the loop); the
-    windowed log line reads it back once per ``logging_steps``."""
+    windowed log line reads it back once per ``logging_steps``.
+    ``features`` (default ``make_features``): the feature builder ``features(examples, max_seq_length)``; run_pretrain.py's loop is this
+    loop with ``functools.partial(make_pretrain_features, tokenizer=tokenizer)``."""
     import os
     build_batch = build_batch or type(model).build_batch
     gas = max(1, int(gradient_accumulation_steps))
@@ -112,7 +146,7 @@ def train(model, items, *, batch_size=64, max_seq_length=128, epochs=1, lr=5e-5,
         model.zero_grad()
         stop = False
         for ep in range(epochs):
-            for step, batch in enumerate(data_helper(items, batch_size, max_seq_length, build_batch, tokenizer, seed=seed + ep)):
+            for step, batch in enumerate(data_helper(items, batch_size, max_seq_length, build_batch, tokenizer, seed=seed + ep, features=features)):
                 model.train()
                 for k, v in batch.items():
                     if torch.is_tensor(v):
@@ -215,3 +249,34 @@ def evaluate(model, items, *, batch_size=64, max_seq_length=128, device="cuda", 
     results = Metric(vocab_path).metric(batches, os.path.join(output_dir, prefix, "preds.txt"),
                                         os.path.join(output_dir, prefix, "labels.txt"), label_path)
     return mean_loss, torch.cat(preds), results
+
+
+@torch.no_grad()
+def evaluate_pretrain(model, items, *, batch_size=64, max_seq_length=128, device="cuda", build_batch=None, tokenizer=None, features=None):
+    """run_pretrain.py:216-255: ``{'avg_loss': mean of the batch losses, 'accuracy': share of the active positions whose arg-max is the
+    target}``.  The model's evaluation forward decodes inside the classifier kernel; only the ids and labels of the active rows reach
+    the host, once, at the end."""
+    import functools
+    build_batch = build_batch or type(model).build_batch
+    features = features or functools.partial(make_pretrain_features, tokenizer=tokenizer)
+    model.to(device)
+    model.eval()
+    losses, preds, labels = [], [], []
+    was_static = getattr(model, "static_weights", None)
+    if was_static is not None:
+        model.mark_parameters_updated()
+        model.static_weights = True
+    try:
+        for batch in data_helper(items, batch_size, max_seq_length, build_batch, tokenizer, is_eval=True, features=features):
+            loss, pred_ids, input_ids = model(batch)[:3]
+            losses.append(loss.detach())
+            preds.append(pred_ids)
+            labels.append(input_ids)
+    finally:
+        if was_static is not None:
+            model.static_weights = was_static
+    if hasattr(model, "check_ids"):
+        model.check_ids()
+    preds, labels = torch.cat(preds), torch.cat(labels)
+    assert preds.numel() == labels.numel()
+    return {"avg_loss": torch.stack(losses).mean().item(), "accuracy": (preds == labels).double().mean().item()}

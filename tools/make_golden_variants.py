@@ -4,7 +4,7 @@ image_model_type 1 (arch3_img1_*, abla_img1_*, resnet1_*).
 
 TEST INFRASTRUCTURE; run only where the reference tree exists (oracle/_ref_import.py):
 
-    PYTHONDONTWRITEBYTECODE=1 python tools/make_golden_variants.py [abla] [arch4] [mlm] [resnet1] [--out DIR]
+    PYTHONDONTWRITEBYTECODE=1 python tools/make_golden_variants.py [abla] [arch4] [mlm] [resnet1] [pretrain] [--out DIR]
 
 Without a group name every group is generated.  Inputs are regenerated from seeds (realise_amd.init.init_state_dict_numpy(...,
 scheme="perturbed"), realise_amd.data.synthetic_batch, realise_amd.data.glyph_upstream_grad); the fixtures hold summaries in the
@@ -24,6 +24,13 @@ possible and the tests hold that block and the blocks upstream of it to a looser
 * resnet1: CharResNet1 takes ONE input channel, so every case is a one-font model.  The glyph-only case stores its ids (8 x 32 int64
   with two rows repeated, so that the deduplication has work to do), a strided sample of the tower output and - because a strided
   sample alone can alias the period-4 `c * 4 + p` permutation - its first two rows in full.
+
+* pretrain: Pho2Pretrain (models.py:1286-1347), the pinyin encoder's pretraining model, on realise_amd.data.synthetic_pretrain_batch
+  (holes in loss_masks; PRETRAIN_CASES: in the b3s40 case sentence 1 has no loss position at all).  Next to the loss, the logits
+  summary and the gradients a fixture holds what the reference's forward returns - `pred_ids` and `active_labels` of the active rows in
+  ascending row order, `hits` -, the active rows' top-1 / top-2 margins (`active_margin`), a strided sample of their logits
+  (`active_logits`) and the taps `head_z`, `head_y`, `pho_out` (the pho stack's output).  EVERY active position must have a margin
+  above 1e-4 or the generator stops: the tests compare the ids at all of them.  Losses of the committed fixtures are printed by the run.
 
 The tests compare arg-max ids above a top-1 / top-2 margin of 1e-4.  The arch4 and mlm tests expect that to be every position, the
 resnet1 tests at least 95 % of them: a case with more positions under the margin than its group allows stops the generator (pick
@@ -252,6 +259,85 @@ def case_glyph(mods, BertConfig, out, name="resnet1_glyph_b8s32", B=8, S=32, see
           % (name, len(set(ids.tolist())), ids.numel(), near0, len(list(m.resnet.parameters())), time.time() - t0))
 
 
+# ---- pretrain: Pho2Pretrain.  name, seed, train, (B, S), the sentence without a loss position (or None)
+PretrainCase = collections.namedtuple("PretrainCase", "name seed train B S empty_sentence")
+PRETRAIN_CASES = [
+    PretrainCase("pho2pre_b2s16_train", 51, True, 2, 16, None),
+    PretrainCase("pho2pre_b2s16_eval", 52, False, 2, 16, None),
+    PretrainCase("pho2pre_b3s40_train", 53, True, 3, 40, 1),
+]
+
+
+def case_pretrain(mods, BertConfig, out, c, n_layers=2):
+    from realise_amd.data import synthetic_pretrain_batch
+    t0 = time.time()
+    cfg = RealiseConfig(num_hidden_layers=n_layers, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0)
+    sd_np = init_state_dict_numpy(cfg, "pho2-pretrain", seed=c.seed, scheme="perturbed")
+    batch = synthetic_pretrain_batch(c.B, c.S, seed=c.seed, empty_sentence=c.empty_sentence)
+    m, _ = reference_model(mods, BertConfig, cfg, "pho2-pretrain")
+    m.load_state_dict({k: torch.from_numpy(np.ascontiguousarray(v)) for k, v in sd_np.items()}, strict=True)
+    m.train(c.train)
+    taken, hooks = {}, []
+    tr = m.cls2.predictions.transform
+    hooks.append(tr.dense.register_forward_hook(lambda mod, i, o: taken.__setitem__("z", o.detach().clone())))
+    hooks.append(tr.register_forward_hook(lambda mod, i, o: taken.__setitem__("y", o.detach().clone())))
+    def head_hook(mod, i, o):      # (returns None: a hook's return value would replace the output)
+        taken["x"], taken["logits"] = i[0].detach().clone(), o.detach().clone()
+    hooks.append(m.cls2.register_forward_hook(head_hook))
+    if c.train:
+        loss, pred_ids, active_labels = m(batch)
+        loss.backward()
+    else:
+        with torch.no_grad():
+            loss, pred_ids, active_labels = m(batch)
+    for h in hooks:
+        h.remove()
+    logits = taken["logits"]
+    store = {"meta/B": np.int64(c.B), "meta/S": np.int64(c.S), "meta/seed": np.int64(c.seed), "meta/n_layers": np.int64(n_layers),
+             "meta/train": np.int64(c.train), "meta/empty_sentence": np.int64(-1 if c.empty_sentence is None else c.empty_sentence)}
+    store["loss"] = np.float64(loss.item())
+    put(store, "logits", logits)
+    store["argmax"] = logits.argmax(-1).to(torch.int32).numpy()
+    top2 = logits.topk(2, dim=-1).values
+    store["margin"] = (top2[..., 0] - top2[..., 1]).to(torch.float32).numpy()
+    active = batch["loss_masks"].reshape(-1) == 1
+    store["pred_ids"] = pred_ids.numpy().astype(np.int64)
+    store["active_labels"] = active_labels.numpy().astype(np.int64)
+    store["hits"] = np.int64((pred_ids == active_labels).sum().item())
+    store["active_margin"] = store["margin"].reshape(-1)[active.numpy()]
+    put(store, "active_logits", logits.reshape(-1, logits.shape[-1])[active])
+    put(store, "head_z", taken["z"])
+    put(store, "head_y", taken["y"])
+    put(store, "pho_out", taken["x"])
+    n_none = 0
+    if c.train:
+        for k, p in m.named_parameters():
+            if p.grad is None:
+                store["gradnone/" + k] = np.int64(1)
+                n_none += 1
+            else:
+                put(store, "grad/" + k, p.grad)
+    per_sentence = batch["loss_masks"].sum(1).tolist()
+    print("[%s] loss %.6f | %d active rows %s, %d hits | smallest active margin %.2e | head |z| max %.2f | no grad: %d | %.1fs"
+          % (c.name, loss.item(), int(active.sum()), per_sentence, int(store["hits"]), float(store["active_margin"].min()),
+             float(taken["z"].abs().max()), n_none, time.time() - t0))
+    if c.empty_sentence is not None and per_sentence[c.empty_sentence] != 0:
+        raise SystemExit("%s: sentence %d was to have no loss position" % (c.name, c.empty_sentence))
+    if not (store["active_margin"] > MARGIN).all():
+        raise SystemExit("%s (seed %d): %d active positions at or under the arg-max margin %g; pick another seed"
+                         % (c.name, c.seed, int((store["active_margin"] <= MARGIN).sum()), MARGIN))
+    np.savez_compressed(os.path.join(out, c.name + ".npz"), **store)
+
+
+def state_dict_pretrain(mods, BertConfig, out):
+    m, _ = reference_model(mods, BertConfig, RealiseConfig(num_hidden_layers=12, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0),
+                           "pho2-pretrain")
+    keys = [[k, list(t.shape)] for k, t in m.state_dict().items()]
+    with open(os.path.join(out, "pho2_pretrain_state_dict.json"), "w") as f:
+        json.dump({"model_type": "pho2-pretrain", "state_dict": keys}, f, indent=0)
+    print("[pho2_pretrain_state_dict.json] %d" % len(keys))
+
+
 # ---- the reference's state_dict names and shapes at the default size (12 layers): file -> [(entry name, model type, switches)]
 STATE_DICTS = {
     "abla": ("abla_state_dicts.json", 0, [("pho%s_res%s_%s" % v, "arch3-abla", v) for v in
@@ -283,17 +369,22 @@ def state_dicts(mods, BertConfig, out, group):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("groups", nargs="*", help="which groups of fixtures to generate: %s (default: all)" % ", ".join(GROUPS))
+    ap.add_argument("groups", nargs="*", help="which groups of fixtures to generate: %s (default: all)" % ", ".join(list(GROUPS) + ["pretrain"]))
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden"), help="directory the fixtures are written to")
     args = ap.parse_args()
-    if set(args.groups) - set(GROUPS):
-        ap.error("unknown group %s" % sorted(set(args.groups) - set(GROUPS)))
+    if set(args.groups) - set(GROUPS) - {"pretrain"}:
+        ap.error("unknown group %s" % sorted(set(args.groups) - set(GROUPS) - {"pretrain"}))
     torch.manual_seed(0)
     torch.set_num_threads(8)
     models, BertConfig = import_reference()
     import models_abla                                  # src/ is on the path after import_reference()
     mods = {"models": models, "abla": models_abla}
-    for group in args.groups or list(GROUPS):
+    for group in args.groups or list(GROUPS) + ["pretrain"]:
+        if group == "pretrain":
+            state_dict_pretrain(mods, BertConfig, args.out)
+            for c in PRETRAIN_CASES:
+                case_pretrain(mods, BertConfig, args.out, c)
+            continue
         state_dicts(mods, BertConfig, args.out, group)
         for c in CASES:
             if c.group == group:
