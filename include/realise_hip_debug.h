@@ -272,6 +272,23 @@ int64_t realise_engine_plan_installs(const realise_engine* e);
 typedef struct realise_cast_desc_info { int64_t src_off, dst_off, dstT_off; int32_t R, C, ldT, group; } realise_cast_desc_info;
 int realise_debug_engine_cast_desc(const realise_engine* e, int i, realise_cast_desc_info* out);
 
+/* The pinyin GRU as the engine launches it (engine.hip gru_forward / gru_backward): thin wrappers over the functions it calls, no
+ * arithmetic of their own.  Pinned element by element by tests/test_gru_edges_gpu.py.
+ * table_fwd: table[v][j] = b_ih[j] + emb[v, :] . w_ih[j, :], fp32, [V][3H]; H > 1024 or V < 1 is refused.
+ * table_bwd: dtable [V][ld >= 3H] -> d_emb [V][H] (row 0, the padding symbol, is not touched), d_w_ih [3H][H], d_b_ih [3H], all
+ *   ACCUMULATED onto what the buffers hold; V > 64 is refused.
+ * step_*_rows: realise_gru_step_fwd / _bwd with the device-side row bound: a->n_alive is the launch bound, rows at or behind
+ *   *n_alive_dev are skipped.
+ * step_fused (bf16): one time step t > 0 as ONE launch - gh = h_prev . w_hh^T + b_hh with the gate math in the GEMM's epilogue; a->gh
+ *   is an OUTPUT here (only its n third is written), a->h_prev the GEMM's A operand [n_alive][H], w_hh_bf16 the plain [3H][ldb]
+ *   weight; H % 64 != 0 (and whatever else gemm_nt8_gru refuses) returns its REALISE_ERR_ARG. */
+int realise_gru_table_fwd(void* stream, const float* emb, const float* w_ih, const float* b_ih, int V, int H, float* table);
+int realise_gru_table_bwd(void* stream, const float* dtable, int ld, const float* emb, const float* w_ih, int V, int H, float* d_emb,
+                          float* d_w_ih, float* d_b_ih);
+int realise_gru_step_fwd_rows(void* stream, int dtype, const realise_gru_step* a, const int32_t* n_alive_dev);
+int realise_gru_step_bwd_rows(void* stream, int dtype, const realise_gru_step* a, const int32_t* n_alive_dev);
+int realise_gru_step_fused(void* stream, const realise_gru_step* a, const void* w_hh_bf16, int64_t ldb, const int32_t* n_alive_dev);
+
 
 #ifdef __cplusplus
 }

@@ -150,6 +150,11 @@ SYMBOLS = {
     "realise_masked_ce": (_I, [_P, _I, _P, _L, _P, _P, _I, _I, _P, _P, _P]),
     "realise_gru_step_fwd": (_I, [_P, _I, C.POINTER(GruStep)]),
     "realise_gru_step_bwd": (_I, [_P, _I, C.POINTER(GruStep)]),
+    "realise_gru_table_fwd": (_I, [_P, _P, _P, _P, _I, _I, _P]),
+    "realise_gru_table_bwd": (_I, [_P, _P, _I, _P, _P, _I, _I, _P, _P, _P]),
+    "realise_gru_step_fwd_rows": (_I, [_P, _I, C.POINTER(GruStep), _P]),
+    "realise_gru_step_bwd_rows": (_I, [_P, _I, C.POINTER(GruStep), _P]),
+    "realise_gru_step_fused": (_I, [_P, C.POINTER(GruStep), _P, _L, _P]),
     "realise_gate_fwd": (_I, [_P, _I, C.POINTER(Gate)]),
     "realise_gate_bwd": (_I, [_P, _I, C.POINTER(Gate)]),
     "realise_gate_softmax_fwd": (_I, [_P, _I, C.POINTER(Gate)]),

@@ -76,8 +76,9 @@ LnGeluBwdArgs<T> to_ln_gelu_bwd(const void* dy, const void* xhat, const float* r
   a.dgamma = dgamma; a.dbeta = dbeta;
   return a;
 }
-template <typename T> GruStepArgs<T> to_gru(const realise_gru_step* g) {
+template <typename T> GruStepArgs<T> to_gru(const realise_gru_step* g, const int32_t* n_alive_dev = nullptr) {
   GruStepArgs<T> a;
+  a.n_alive_dev = (const int*)n_alive_dev;
   a.n_alive = g->n_alive; a.H = g->H; a.Tp = g->Tp; a.t = g->t; a.table = g->table; a.pho_idx = g->pho_idx; a.perm = g->perm; a.lens = g->lens;
   a.gh = (const T*)g->gh; a.b_hh = g->b_hh; a.h_prev = (const T*)g->h_prev; a.h_new = (T*)g->h_new; a.rzn = (T*)g->rzn; a.out = (T*)g->out;
   a.dout = (const T*)g->dout; a.dh = (T*)g->dh; a.dgi = (T*)g->dgi; a.dgh = (T*)g->dgh; a.onehot = (T*)g->onehot;
@@ -281,6 +282,34 @@ int realise_gru_step_fwd(void* stream, int dtype, const realise_gru_step* a) {
 int realise_gru_step_bwd(void* stream, int dtype, const realise_gru_step* a) {
   if (!a) return RL_ERR_ARG;
   RL_BY_DTYPE(0, gru_step_bwd<E>((hipStream_t)stream, to_gru<E>(a)));
+}
+// the pinyin GRU as engine.hip gru_forward / gru_backward launch it (include/realise_hip_debug.h)
+int realise_gru_table_fwd(void* stream, const float* emb, const float* w_ih, const float* b_ih, int V, int H, float* table) {
+  if (!emb || !w_ih || !b_ih || !table) return RL_ERR_ARG;
+  return gru_table_fwd((hipStream_t)stream, emb, w_ih, b_ih, V, H, table);
+}
+int realise_gru_table_bwd(void* stream, const float* dtable, int ld, const float* emb, const float* w_ih, int V, int H, float* d_emb,
+                          float* d_w_ih, float* d_b_ih) {
+  if (!dtable || !emb || !w_ih || !d_emb || !d_w_ih || !d_b_ih || V < 1 || H < 1 || ld < 3 * H) return RL_ERR_ARG;
+  return gru_table_bwd((hipStream_t)stream, dtable, ld, emb, w_ih, V, H, d_emb, d_w_ih, d_b_ih);
+}
+int realise_gru_step_fwd_rows(void* stream, int dtype, const realise_gru_step* a, const int32_t* n_alive_dev) {
+  if (!a || !n_alive_dev) return RL_ERR_ARG;
+  RL_BY_DTYPE(0, gru_step_fwd<E>((hipStream_t)stream, to_gru<E>(a, n_alive_dev)));
+}
+int realise_gru_step_bwd_rows(void* stream, int dtype, const realise_gru_step* a, const int32_t* n_alive_dev) {
+  if (!a || !n_alive_dev) return RL_ERR_ARG;
+  RL_BY_DTYPE(0, gru_step_bwd<E>((hipStream_t)stream, to_gru<E>(a, n_alive_dev)));
+}
+int realise_gru_step_fused(void* stream, const realise_gru_step* a, const void* w_hh_bf16, int64_t ldb, const int32_t* n_alive_dev) {
+  if (!a || !w_hh_bf16) return RL_ERR_ARG;
+  typedef bf16_t T;
+  const int H = a->H;
+  EpiParams<T> ep; ep.mode = EPI_STORE; ep.out = (T*)a->h_new; ep.ldo = H; ep.bias = a->b_hh; ep.m_dev = (const int*)n_alive_dev;
+  ep.gru_table = a->table; ep.gru_pho_idx = a->pho_idx; ep.gru_perm = a->perm; ep.gru_lens = a->lens;
+  ep.gru_hprev = (const T*)a->h_prev; ep.gru_rzn = (T*)a->rzn; ep.gru_gh = (T*)a->gh; ep.gru_out = (T*)a->out;
+  ep.gru_Tp = a->Tp; ep.gru_t = a->t;
+  return gemm_nt8_gru((hipStream_t)stream, (const T*)a->h_prev, H, (const T*)w_hh_bf16, ldb, a->n_alive, 3 * H, H, ep);
 }
 int realise_gate_fwd(void* stream, int dtype, const realise_gate* a) {
   if (!a) return RL_ERR_ARG;
