@@ -66,6 +66,31 @@ typedef struct {
  * models.py:859), and its data gradient when B is the transposed weight. */
 int realise_gemm_nt(void* stream, int dtype, const void* A, int64_t lda, const void* B, int64_t ldb,
                     int M, int N, int K, const realise_epilogue* ep);
+/* The same product with a K-SEGMENTED A operand: out[M, N] = [A_0 | A_1 | .. | A_{nsrc-1}] . W^T + bias - the concatenation fusion
+ * `integrate(torch.cat((bert, pho, res), -1))` of SpellBertPho2ResArch2 (src/models.py:628-629; :490-491, :228-229 and :140-141 are
+ * the same line of its siblings) without the [M, nsrc * Ks] tensor, which is neither written nor read.  W is [N, nsrc * Ks] with row
+ * pitch ldw, K-contiguous; segment s is [M, Ks] with its own base a[s] and row pitch lda[s]; nsrc is 2 or 3.  ONE launch and ONE fp32
+ * accumulation over K = nsrc * Ks in the order s = 0 .. nsrc - 1 (the reference's arithmetic; no partial sum is rounded to the compute
+ * dtype).  The 4-wave kernels of realise_gemm_nt: wherever realise_gemm_nt on the materialised concatenation runs those too (every bf16
+ * shape below M = 1024 or N = 256; every fp32 / bf16x3 shape), the two outputs are equal bit for bit.  Not read: the columns of a
+ * segment row from Ks to lda[s].  bias nullable.
+ * live_list / live_count (both NULL: every row; device pointers): the M dimension is a list of rows (live_unit 1: *live_count row ids)
+ * or of 16-row blocks (live_unit 16: block ids) - listed rows are read from and written at their ORIGINAL positions and hold the bits
+ * of the dense launch, every other output row is left untouched, *live_count == 0 writes nothing.
+ * Refused with the argument error, nothing launched: nsrc outside 2..3, a NULL a[s] below nsrc, NULL w or out, Ks not a positive
+ * multiple of the K tile (64 elements for REALISE_BF16, 32 for REALISE_F32 and REALISE_F32_BF16X3: no staged tile straddles two
+ * segments), N % 4 != 0, a pitch that is no multiple of 8 (bf16) / 4 (fp32) elements, one of live_list / live_count without the
+ * other, a live_unit other than 1 and 16 with a list, a dtype outside 0..2.  M <= 0 or N <= 0 is an empty problem (0, nothing launched). */
+typedef struct {
+  int32_t M, N, Ks, nsrc;
+  const void* a[3];
+  int64_t lda[3];
+  const void* w; int64_t ldw;
+  const float* bias;
+  void* out; int64_t ldo;
+  const int32_t* live_list; const int32_t* live_count; int32_t live_unit;
+} realise_gemm_cat;
+int realise_gemm_nt_cat(void* stream, int dtype, const realise_gemm_cat* g);
 /* Same with A gathered on the fly: nn.Conv2d forward / input gradient (src/char_cnn.py:15-28). */
 int realise_conv_nt(void* stream, int dtype, const realise_conv_geom* a, const void* B, int64_t ldb,
                     int M, int N, int K, const realise_epilogue* ep);
@@ -304,7 +329,16 @@ typedef struct {
                               * pho_embeddings, pho_gru, pho_model (pho_layers deep; bert_layers is carried and ignored) - under a
                               * BertOnlyMLMHead named cls2.  No bert stack, fusion, glyph tower or output block; src_idx is the batch's
                               * tgt_idx (models.py:1319); tie_classifier == 0, with_pho == 1 and with_res == 0 (the branches it has: a
-                              * type-5 config that claims a glyph branch is refused); gradient buckets: 0 = cls2, 1 = the pinyin branch */
+                              * type-5 config that claims a glyph branch is refused); gradient buckets: 0 = cls2, 1 = the pinyin branch,
+                              * 6 = SpellBertPho2ResArch2 (models.py:513-649): Arch3's branches - bert, pinyin GRU + pho_model, glyph tower +
+                              * resnet_layernorm - fused by CONCATENATION: integrate = nn.Linear(3H, H) over torch.cat((bert, pho, res), -1)
+                              * (models.py:628-629, one realise_gemm_nt_cat launch) in front of a TWO-layer output_block; no gate_net.  The
+                              * config says what the model is: with_pho == 1, with_res == 1, fusion == 2, num_fonts == 1, glyph_size == 32
+                              * (char_images.weight [V, 1024], models.py:533), out_layers == 2; image_model_type 0 or 1; tied or untied,
+                              * 7 = SpellBertPho2 (models.py:163-249): the same without the glyph branch - integrate = nn.Linear(2H, H) over
+                              * torch.cat((bert, pho), -1): with_pho == 1, with_res == 0, fusion == 2, out_layers == 2.
+                              * Gradient buckets of 6 / 7: 0 = classifier + output_block, 1 = integrate (+ resnet_layernorm and the glyph
+                              * tower), 2 = the pinyin branch, then the bert layer groups and the bert embeddings */
   int32_t dtype;
   int32_t hidden, heads, intermediate, vocab, max_pos, type_vocab;
   int32_t bert_layers, pho_layers, out_layers;
@@ -312,7 +346,8 @@ typedef struct {
   float hidden_dropout, attn_dropout, ln_eps;
   int32_t tie_classifier;    /* classifier.weight aliases bert word embeddings (models.py:700-701) */
   /* model_type 2, and model_type 5 as (1, 0, 0) (ignored otherwise; run.py:373-375): 1 = the pinyin branch / the glyph branch is present; fusion 0 = gate over
-   * the G = 1 + with_pho + with_res sources (gate_net [G, (G+1)H]), 1 = sum (needs both branches) */
+   * the G = 1 + with_pho + with_res sources (gate_net [G, (G+1)H]), 1 = sum (needs both branches), 2 = concatenation through
+   * `integrate` (model_type 6 / 7 only, which require it) */
   int32_t with_pho, with_res, fusion;
   /* the glyph encoder (run.py:292,419-421 --image_model_type; models.py:681-686): 0 = CharResNet (char_cnn.py:36-55: five blocks,
    * num_fonts input channels, a [768, 1, 1] top), exactly what a zero-initialised field gave before it existed; 1 = CharResNet1

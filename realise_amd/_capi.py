@@ -7,7 +7,7 @@ is no CPU or PyTorch fallback.
 import ctypes as C
 import os
 
-from .config import MODEL_TYPES, model_type_number  # noqa: F401
+from .config import CONCAT_OUT_LAYERS, MODEL_TYPES, model_type_number  # noqa: F401
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "librealise_hip.so")
@@ -47,6 +47,13 @@ class Epilogue(C.Structure):
     _fields_ = [("mode", C.c_int32), ("accumulate", C.c_int32), ("out", C.c_void_p), ("ldo", C.c_int64),
                 ("out2", C.c_void_p), ("bias", C.c_void_p), ("aux", C.c_void_p), ("ldaux", C.c_int64),
                 ("alpha", C.c_float), ("drop_seed", C.c_uint32), ("drop_thresh", C.c_uint32), ("drop_scale", C.c_float)]
+
+
+class GemmCat(C.Structure):
+    """realise_gemm_cat (include/realise_hip.h)"""
+    _fields_ = [("M", C.c_int32), ("N", C.c_int32), ("Ks", C.c_int32), ("nsrc", C.c_int32),
+                ("a", C.c_void_p * 3), ("lda", C.c_int64 * 3), ("w", C.c_void_p), ("ldw", C.c_int64), ("bias", C.c_void_p),
+                ("out", C.c_void_p), ("ldo", C.c_int64), ("live_list", C.c_void_p), ("live_count", C.c_void_p), ("live_unit", C.c_int32)]
 
 
 class ConvGeom(C.Structure):
@@ -104,6 +111,7 @@ _P, _I, _L, _F, _U = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint32
 SYMBOLS = {
     "realise_version": (C.c_char_p, []),
     "realise_gemm_nt": (_I, [_P, _I, _P, _L, _P, _L, _I, _I, _I, C.POINTER(Epilogue)]),
+    "realise_gemm_nt_cat": (_I, [_P, _I, C.POINTER(GemmCat)]),
     "realise_conv_nt": (_I, [_P, _I, C.POINTER(ConvGeom), _P, _L, _I, _I, _I, C.POINTER(Epilogue)]),
     "realise_conv_dgrad_s2": (_I, [_P, _I, C.POINTER(ConvGeom), _P, _L, _I, C.POINTER(Epilogue)]),
     "realise_gemm_tn": (_I, [_P, _I, _P, _L, _P, _L, _I, _I, _I, _P, _L, _P, _L, _P]),
@@ -273,6 +281,8 @@ def make_config(cfg, model_type, dtype, tie=True):
     c.hidden, c.heads, c.intermediate = cfg["hidden_size"], cfg["num_attention_heads"], cfg["intermediate_size"]
     c.vocab, c.max_pos, c.type_vocab = cfg["vocab_size"], cfg["max_position_embeddings"], cfg["type_vocab_size"]
     c.bert_layers, c.pho_layers, c.out_layers = cfg["num_hidden_layers"], cfg["pho_layers"], cfg["out_layers"]
+    if c.model_type in (6, 7):      # the concatenation models hard-wire a two-layer output_block (models.py:546, :185)
+        c.out_layers = CONCAT_OUT_LAYERS
     c.num_fonts, c.glyph_size, c.pho_vocab = cfg["num_fonts"], cfg["glyph_size"], cfg["pho_vocab_size"]
     c.hidden_dropout, c.attn_dropout = cfg["hidden_dropout_prob"], cfg["attention_probs_dropout_prob"]
     c.ln_eps = cfg["layer_norm_eps"]
@@ -283,6 +293,8 @@ def make_config(cfg, model_type, dtype, tie=True):
     c.fusion = 1 if cfg.get("fusion", "gate") == "sum" else 0
     if c.model_type == 5:      # Pho2Pretrain is the pinyin branch without the glyph branch, whatever the config's ablation switches say
         c.with_pho, c.with_res, c.fusion = 1, 0, 0
+    if c.model_type in (6, 7):  # the concatenation models: what they are, whatever the config's ablation switches say; fusion 2 = integrate
+        c.with_pho, c.with_res, c.fusion = 1, (1 if c.model_type == 6 else 0), 2
     # the glyph encoder (run.py:419-421): 0 = CharResNet, 1 = CharResNet1; read where the model has a glyph branch
     c.image_model_type = int(cfg.get("image_model_type", 0))
     return c

@@ -139,14 +139,36 @@ _PRETRAIN_NOT_BUILT = {
     "res-pretrain": "ResPretrain (models.py:1349-1420) is not implemented: about a thousand steps over 256 glyphs that finish in a minute "
                     "on any device; only 'pho2-pretrain' runs here",
 }
+# The concatenation models of run.py:40-51 ('bert-pho2-res-arch2', 'bert-pho2'): the branches are fused by integrate =
+# nn.Linear(n * H, H) over torch.cat (models.py:628-629, :228-229) in front of a two-layer output_block.  A third table of the same row
+# format; the ABI numbers go on.  SpellBertPho2ResArch2 hard-wires the one-font glyph table at models.py:533.
+_CONCAT_MODELS = {
+    "arch2": (6, "SpellBertPho2ResArch2", 533),
+    "pho2": (7, "SpellBertPho2", None),
+}
+CONCAT_MODEL_TYPES = {k: row[0] for k, row in _CONCAT_MODELS.items()}
+CONCAT_OUT_LAYERS = 2       # models.py:546, :185
+# run.py's remaining MODEL_CLASSES entries, refused by name with their reason and never mapped to another model
+_RUN_NOT_BUILT = {
+    "bert-pho1": "SpellBertPho1 (models.py:76-160) is not implemented: it reads three pinyin id planes (initial, final, tone) from "
+                 "another converter (Pinyin.convert) and has no GRU; of the concatenation models 'bert-pho2' and "
+                 "'bert-pho2-res-arch2' run here",
+    "bert-pho1-res": "SpellBertPho1Res (models.py:251-376) is not implemented: it reads three pinyin id planes from another converter "
+                     "(Pinyin.convert) and has no GRU; of the concatenation models 'bert-pho2' and 'bert-pho2-res-arch2' run here",
+    "bert-pho2-res": "SpellBertPho2Res (models.py:379-510) is not implemented: it adds the GRU output and an un-normalised glyph "
+                     "vector into one shared pho_res_model instead of keeping a branch each; of the concatenation models 'bert-pho2' "
+                     "and 'bert-pho2-res-arch2' run here",
+}
 
 
 def model_type_number(model_type):
-    """the C ABI's realise_config.model_type of a name from MODEL_TYPES or PRETRAIN_MODEL_TYPES"""
+    """the C ABI's realise_config.model_type of a name from MODEL_TYPES, PRETRAIN_MODEL_TYPES or CONCAT_MODEL_TYPES"""
     if model_type in MODEL_TYPES:
         return MODEL_TYPES[model_type]
     if model_type in PRETRAIN_MODEL_TYPES:
         return PRETRAIN_MODEL_TYPES[model_type]
+    if model_type in CONCAT_MODEL_TYPES:
+        return CONCAT_MODEL_TYPES[model_type]
     variant_of({}, model_type)      # raises with the reason
 
 # What a model computes: csrc/layout.h's ``Variant`` field for field (``gates`` is G: 0 without a gate_net, otherwise its ``nsrc``),
@@ -154,18 +176,28 @@ def model_type_number(model_type):
 # reference class name for messages, ``head_prefix`` (the state_dict prefix of an MLM head: "cls." or Pho2Pretrain's "cls2.", else None).
 # ``bert``: the model has the bert stack (false: Pho2Pretrain, the pinyin branch alone).  Every Python-side decision reads this, not
 # ``model_type``.
-Variant = collections.namedtuple("Variant", "arch pho res gate gates gate_softmax mlm_head one_font one_font_line reference_class bert head_prefix")
+# ``concat``: the fusion is `integrate` over the concatenation (CONCAT_MODEL_TYPES): arch is true, gate false, gates 0.
+Variant = collections.namedtuple("Variant", "arch pho res gate gates gate_softmax mlm_head one_font one_font_line reference_class bert head_prefix concat",
+                                 defaults=(False,))
 
 
 def variant_of(cfg, model_type):
     if model_type in _PRETRAIN_NOT_BUILT:
         raise ValueError("model_type %r: %s" % (model_type, _PRETRAIN_NOT_BUILT[model_type]))
+    if model_type in _RUN_NOT_BUILT:
+        raise ValueError("model_type %r: %s" % (model_type, _RUN_NOT_BUILT[model_type]))
+    if model_type in _CONCAT_MODELS:        # SpellBertPho2ResArch2 (models.py:513-649) / SpellBertPho2 (models.py:163-249)
+        _, reference_class, one_font_line = _CONCAT_MODELS[model_type]
+        return Variant(arch=True, pho=True, res=model_type == "arch2", gate=False, gates=0, gate_softmax=False, mlm_head=False,
+                       one_font=one_font_line is not None, one_font_line=one_font_line, reference_class=reference_class, bert=True,
+                       head_prefix=None, concat=True)
     if model_type in _PRETRAIN_MODELS:      # Pho2Pretrain (models.py:1286-1347): pho_embeddings, pho_gru, pho_model and the MLM head cls2
         _, reference_class, _ = _PRETRAIN_MODELS[model_type]
         return Variant(arch=False, pho=True, res=False, gate=False, gates=0, gate_softmax=False, mlm_head=True, one_font=False,
                        one_font_line=None, reference_class=reference_class, bert=False, head_prefix="cls2.")
     if model_type not in _MODELS:
-        raise ValueError("model_type must be 'bert', 'arch3', 'arch3-abla', 'arch4' or 'arch3-mlm' (or 'pho2-pretrain' of PRETRAIN_MODEL_TYPES)")
+        raise ValueError("model_type must be 'bert', 'arch3', 'arch3-abla', 'arch4' or 'arch3-mlm' (or 'pho2-pretrain' of PRETRAIN_MODEL_TYPES, "
+                         "'arch2' / 'pho2' of CONCAT_MODEL_TYPES)")
     _, reference_class, one_font_line = _MODELS[model_type]
     arch = model_type != "bert"
     abla = model_type == "arch3-abla"      # src/models_abla.py:37-45: the switches drop whole branches; (yes, yes, gate) is arch3

@@ -42,6 +42,14 @@ template <typename T> ConvLoader<T> to_geom(const realise_conv_geom* g, const in
   c.finalize();
   return c;
 }
+template <typename T> int cat_launch(hipStream_t st, const realise_gemm_cat* g, int x3) {      // (nsrc is in range: the caller checked)
+  const T* a[SEG_MAX];
+  for (int s = 0; s < g->nsrc; ++s) a[s] = (const T*)g->a[s];
+  EpiParams<T> ep;
+  ep.x3 = x3; ep.out = (T*)g->out; ep.ldo = g->ldo; ep.bias = g->bias;
+  ep.live_list = g->live_list; ep.live_count = g->live_count; ep.live_unit = g->live_unit;
+  return gemm_nt_cat<T>(st, g->nsrc, a, g->lda, g->Ks, (const T*)g->w, g->ldw, g->M, g->N, ep);
+}
 TnEpi with_x3(TnEpi te, int x3) { te.x3 = x3; return te; }
 template <typename T>
 int tn_grouped(hipStream_t st, int n, const realise_tn_problem* pr, int P, int x3, const int* live = nullptr, const int* n_live = nullptr,
@@ -130,6 +138,10 @@ int realise_gemm_nt(void* stream, int dtype, const void* A, int64_t lda, const v
                     const realise_epilogue* ep) {
   if (!ep || !ep->out) return RL_ERR_ARG;
   RL_BY_DTYPE(1, gemm_nt<E>((hipStream_t)stream, (const E*)A, lda, (const E*)B, ldb, M, N, K, to_epi<E>(ep, x3)));
+}
+int realise_gemm_nt_cat(void* stream, int dtype, const realise_gemm_cat* g) {
+  if (!g || !g->out || !g->w || g->nsrc < 2 || g->nsrc > SEG_MAX) return RL_ERR_ARG;
+  RL_BY_DTYPE(1, cat_launch<E>((hipStream_t)stream, g, x3));
 }
 int realise_conv_nt(void* stream, int dtype, const realise_conv_geom* a, const void* B, int64_t ldb, int M, int N, int K,
                     const realise_epilogue* ep) {

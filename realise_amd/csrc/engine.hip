@@ -137,6 +137,7 @@ template <typename T> struct Engine : EngineBase {
   BlockSh sh_blk[TOWER_MAX_BLOCKS];      // the first L.tower.nblocks are in use
   int64_t sh_cls_w = 0, sh_cls_wT = 0, sh_gru_hh = 0, sh_gru_hhT = 0, sh_glyph = 0;
   int64_t sh_head_w = 0, sh_head_wT = 0;      // transform.dense of the MLM head (vr.mlm_head)
+  int64_t sh_int_w = 0, sh_int_wT = 0;        // integrate of a concatenation model (vr.concat)
   int64_t shadow_total = 0;
   bool glyph_built = false, descs_built = false;
   int64_t sh_descs = 0, sh_fill = 0, sh_skip = 0;
@@ -356,6 +357,7 @@ template <typename T> struct Engine : EngineBase {
     sh_fill = b.take(FILL_MAX * (int64_t)sizeof(FillChunk));  // chunk table of the fresh-gradient zero fill
     sh_skip = b.take(ACHUNK_MAX * (int64_t)sizeof(FillChunk));   // chunk list of the parameters the tiled AdamW does NOT own (adamw_step)
     if (vr.mlm_head) { sh_head_w = b.take((int64_t)H * H * e); sh_head_wT = b.take((int64_t)H * H * e); }      // (last: every other offset stays put)
+    if (vr.concat) { sh_int_w = b.take((int64_t)vr.nsrc * H * H * e); sh_int_wT = b.take((int64_t)vr.nsrc * H * H * e); }      // integrate [H][nH] and its transpose [nH][H]
     shadow_total = b.off;
   }
 
@@ -392,6 +394,7 @@ template <typename T> struct Engine : EngineBase {
     if (vr.pho) add_stack(L.pho, sh_pho);
     if (vr.arch) add_stack(L.outb, sh_out);
     if (vr.pho) add(L.gru_w_hh, 3 * H, H, sh_gru_hh, sh_gru_hhT);
+    if (vr.concat) add(L.int_w, H, vr.nsrc * H, sh_int_w, sh_int_wT);      // (in the piece of the pinyin / output stacks: the forward meets it at the fusion)
     if (d.size() > 256) return RL_ERR_ARG;
     if (hipMemcpyAsync(sh + sh_descs, d.data(), d.size() * sizeof(CastDesc), hipMemcpyHostToDevice, st) != hipSuccess) return RL_ERR_LAUNCH;
     n_descs = (int)d.size(); desc_tiles = tiles; descs_built = true;
@@ -1494,6 +1497,7 @@ template <typename T> struct Engine : EngineBase {
       if (ovl) RL_TRY(join(st));
       RL_TRY(sync_optimizer(st));                                   // every piece of a pipelined sweep is now in front of this stream
       if (vr.gate) RL_TRY(gate_fwd<T>(st, gate_args()));
+      else if (vr.concat) RL_TRY(concat_fwd(st, bert_h));
       else RL_TRY(sum_fuse_fwd<T>(st, bert_h, wp<T>(pl.pho.layers.back().y2), wp<T>(pl.res_h), wp<T>(pl.fused), Tk, H));
       RL_TRY(stack_forward(st, 2, L.outb, sh_out, pl.outb, nullptr, wp<T>(pl.fused), 1, &top));
     }
@@ -1660,7 +1664,41 @@ template <typename T> struct Engine : EngineBase {
     RL_TRY(emb_backward(la, 2, L.outb, pl.outb, nullptr, 1, gA, wp<T>(pl.sc[0].gB)));
     return RL_OK;
   }
-  int stage_fuse(hipStream_t st) {           // d fused -> X1 (d bert), X2 (d pho), X3 (d res) [+ gate_net gradients]
+  // Concatenation fusion (models.py:628-629, :228-229): fused = integrate([bert | pho | res]) as ONE GEMM over the K-segmented operand
+  // (gemm_nt_cat: no [T, nH] tensor), over the live rows of a live-row step like every layer GEMM.
+  int concat_fwd(hipStream_t st, const T* bert_h) {
+    const T* a[SEG_MAX] = {bert_h, wp<T>(pl.pho.layers.back().y2), vr.res ? wp<T>(pl.res_h) : nullptr};
+    const int64_t lda[SEG_MAX] = {H, H, H};
+    EpiParams<T> ep; ep.mode = EPI_STORE; ep.out = wp<T>(pl.fused); ep.ldo = H; ep.bias = pp(L.int_b);
+    if constexpr (sizeof(T) == 4) ep.x3 = x3();
+    if constexpr (sizeof(T) == 2) {
+      if (rows_live && g_live_rows == 2) { ep.live_list = wp<int>(pl.live_rows); ep.live_count = wp<int>(pl.live_n) + 3; ep.live_unit = 1; }
+      else if (rows_live) { ep.live_list = wp<int>(pl.live_t16); ep.live_count = wp<int>(pl.live_n) + 2; ep.live_unit = 16; }
+    }
+    return gemm_nt_cat<T>(st, vr.nsrc, a, lda, H, sp<T>(sh_int_w), (int64_t)vr.nsrc * H, pl.B * pl.S, H, ep);
+  }
+  // Its backward needs no kernel of its own.  d A_s = d fused . W[:, sH:(s+1)H] is a plain NT GEMM against rows sH.. of the transposed
+  // copy, written straight into X1 / X2 / X3.  The launches are DENSE in a live-row step too: d fused (the output block's embedding
+  // LayerNorm backward) holds exact zeros in every padding row, so the product leaves exact zeros there - what the gate backward
+  // guarantees - without a pass of its own.  All of them run here, in front of the fork: they read gB of set 0, which the bert lane's
+  // layers re-use as soon as they start.  The weight gradient is one grouped TN launch - problem s = column slice s of dW (pitch nH) -
+  // over the live reduction tiles, the bias gradient its column sum; it accumulates (integrate is not among the tensors a fresh pass stores).
+  int concat_bwd(hipStream_t st) {
+    const int Tk = pl.B * pl.S, n = vr.nsrc;
+    const T* df = wp<T>(pl.sc[0].gB);
+    T* dx[SEG_MAX] = {wp<T>(pl.X1), wp<T>(pl.X2), vr.res ? wp<T>(pl.X3) : nullptr};
+    const T* x[SEG_MAX] = {wp<T>(pl.bert.layers.back().y2), wp<T>(pl.pho.layers.back().y2), vr.res ? wp<T>(pl.res_h) : nullptr};
+    TnGroupProblem<T> gp3[SEG_MAX];
+    for (int s = 0; s < n; ++s) {
+      EpiParams<T> ep; ep.mode = EPI_STORE; ep.out = dx[s]; ep.ldo = H;
+      RL_TRY(gemm_nt<T>(st, df, H, sp<T>(sh_int_wT) + (int64_t)s * H * H, H, Tk, H, H, ep));
+      gp3[s].A = df; gp3[s].lda = H; gp3[s].B = x[s]; gp3[s].ldb = H; gp3[s].I = H; gp3[s].J = H;
+      gp3[s].out = gp(L.int_w) + (int64_t)s * H; gp3[s].ldo = (int64_t)n * H; gp3[s].colsum = s == 0 ? gp(L.int_b) : nullptr;
+    }
+    return gemm_tn_group<T>(st, n, gp3, Tk, 1.0f, 0, live_tiles(), live_tile_count(), live_list_rows());
+  }
+  int stage_fuse(hipStream_t st) {           // d fused -> X1 (d bert), X2 (d pho), X3 (d res) [+ gate_net / integrate gradients]
+    if (vr.concat) return concat_bwd(st);
     if (!vr.gate) return sum_fuse_bwd<T>(st, wp<T>(pl.sc[0].gB), wp<T>(pl.X1), wp<T>(pl.X2), wp<T>(pl.X3), pl.B * pl.S, H, live_rows());
     GateArgs<T> g = gate_args();
     g.dfused = wp<T>(pl.sc[0].gB); g.dbert = wp<T>(pl.X1); g.dz = wp<float>(pl.dz);

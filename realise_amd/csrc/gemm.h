@@ -126,6 +126,51 @@ template <typename T> struct DenseLoader {
   }
 };
 
+// A K-segmented dense operand: logical row r is [A_0[r] | A_1[r] | ... | A_{nseg-1}[r]], every segment Ks wide with its own base and row
+// pitch (the input of `integrate`, models.py:628-629: torch.cat((bert, pho, res), -1) without the concatenated tensor).  The DenseLoader
+// interface (kDense), so the X3 policy and the 4-wave kernels take it as they are; what differs is the per-column state - KPos is
+// (segment, k inside the segment), stepped by compare-and-subtract, one division in kpos() - and that Ctx keeps the ROW, since the
+// row's address depends on the segment.  Ks is a multiple of the kernels' K tile (Geo<T>::BK): no staged tile straddles two segments,
+// so all lanes of a tile are in the same segment and the kernel re-derives its stepping pointers once per segment boundary.
+constexpr int SEG_MAX = 3;
+template <typename T> struct SegLoader {
+  static constexpr bool kDense = true;
+  // Segment 0's base and pitch, then per further segment the DIFFERENCE to its predecessor (base in bytes, pitch in elements): addr()
+  // adds them under a compare.  (Three bases picked by the segment number - an array, or scalars behind a select chain - made hipcc
+  // index the kernel's private copy of the loader: 80 B of scratch per lane.  Sums of differences keep it in SGPRs.)
+  const T* base0 = nullptr;
+  int64_t ld0 = 0, dbase1 = 0, dbase2 = 0, dld1 = 0, dld2 = 0;
+  int nseg, Ks;
+  int rows, K;                     // K = nseg * Ks
+  const int* rows_dev = nullptr;   // optional device-side row bound, as DenseLoader's
+  struct Ctx { int row; };         // -1: out of range
+  struct KPos { int seg, k; };
+  __device__ __forceinline__ void clamp_rows() { if (rows_dev != nullptr) rows = min(rows, *rows_dev); }
+  __device__ __forceinline__ Ctx prepare(int row) const { Ctx c; c.row = (row >= 0 && row < rows) ? row : -1; return c; }
+  // the same bound without writing to the loader (the kernel keeps its copy read-only: it stays in SGPRs, nothing goes to scratch)
+  __device__ __forceinline__ int bounded_rows() const { return rows_dev != nullptr ? min(rows, *rows_dev) : rows; }
+  __device__ __forceinline__ Ctx prepare(int row, int bound) const { Ctx c; c.row = (row >= 0 && row < bound) ? row : -1; return c; }
+  __device__ __forceinline__ KPos kpos(int k) const { KPos q; q.seg = k / Ks; q.k = k - q.seg * Ks; return q; }
+  __device__ __forceinline__ void advance(KPos& q, int dk) const {
+    q.k += dk;
+    while (q.k >= Ks) { q.k -= Ks; ++q.seg; }
+  }
+  __device__ __forceinline__ const void* addr(const Ctx& c, const KPos& q, const void* zero) const {
+    if (c.row < 0 || q.seg >= nseg) return zero;
+    int64_t off = ((int64_t)c.row * ld0 + q.k) * (int64_t)sizeof(T);
+    if (q.seg >= 1) off += dbase1 + (int64_t)c.row * dld1 * (int64_t)sizeof(T);
+    if (q.seg >= 2) off += dbase2 + (int64_t)c.row * dld2 * (int64_t)sizeof(T);
+    return (const void*)((const char*)base0 + off);
+  }
+  void set(int n, const T* const* b, const int64_t* p) {      // host: n = 2 or 3 segments
+    base0 = b[0]; ld0 = p[0];
+    dbase1 = (int64_t)((intptr_t)b[1] - (intptr_t)b[0]); dld1 = p[1] - p[0];
+    if (n > 2) { dbase2 = (int64_t)((intptr_t)b[2] - (intptr_t)b[1]); dld2 = p[2] - p[1]; }
+  }
+};
+template <typename L> struct LoaderIsSeg { static constexpr bool value = false; };
+template <typename T> struct LoaderIsSeg<SegLoader<T>> { static constexpr bool value = true; };
+
 // Implicit im2col over an NHWC tensor (K7/K8).  Row space = pixels (n, y, x) of an Hr x Wr map,
 // K = (kh, kw, c).  mode 0: forward conv gather, source pixel (y*stride + kh - pad, ...);
 // mode 1: data-gradient gather, source pixel ((y + pad - kh)/stride, ...) when divisible.
@@ -371,6 +416,11 @@ int gemm_nt(hipStream_t st, const T* A, int64_t lda, const T* B, int64_t ldb, in
 template <typename T>
 int gemm_nt_conv(hipStream_t st, const ConvLoader<T>& la, const T* B, int64_t ldb, int M, int N, int K,
                  const EpiParams<T>& ep);
+// C[M,N] = [A_0 | .. | A_{nseg-1}] . B[N, nseg*Ks]^T (+ bias): SegLoader, nseg 2..3, Ks % Geo<T>::BK == 0, plain store; ep.live_list /
+// live_count / live_unit (1 or 16) run it over a device-side list of rows / 16-row blocks, addressed at their original positions
+template <typename T>
+int gemm_nt_cat(hipStream_t st, int nseg, const T* const* A, const int64_t* lda, int Ks, const T* B, int64_t ldb, int M, int N,
+                const EpiParams<T>& ep);
 // Stride-2 data gradient by input-pixel parity classes (ConvLoader::par): `full` is the mode-1 geometry over ALL input pixels (Hr = Wr
 // a power of two >= 2, no img_index; rows_dev counts input-pixel rows), B the class-ordered weight copy (conv_s2_class()), ep.out the
 // [rows, Cin] input gradient.  One gemm_nt_conv per class over a quarter of the rows, K = the class's taps; a class no tap reaches

@@ -51,6 +51,10 @@ template <typename T, int NA> struct ConvRows<ConvLoader<T>, NA> {
   }
 };
 
+// the Ctx / KPos types of a dense A operand: SegLoader's own, DenseLoader's for everything else (a gathered operand does not use them)
+template <typename L, typename T> struct DenseCtxOf { typedef DenseLoader<T> type; };
+template <typename T> struct DenseCtxOf<SegLoader<T>, T> { typedef SegLoader<T> type; };
+
 // DEC = 1 / 4: the decode form (DecodeParams, gemm.h) - same main loop, same accumulators, nothing of C stored
 template <typename T, typename ALoader, int WM, int WN, int NSTAGE, int NF, bool SPREAD, bool X3 = false, int DEC = 0>
 __global__ void __launch_bounds__(64 * WM * WN, (WM * WN == 4 && NSTAGE == 2) ? 2 : 1)
@@ -68,8 +72,10 @@ gemm_nt_kernel(ALoader la, DenseLoader<T> lb, int M, int N, int K, int tiles_n, 
   const int wm = wave / WN, wn = wave - wm * WN;
   // A device-side row bound (glyph dedup) shrinks the tile grid: the XCD remap is applied to the LIVE tiles only, so the
   // surplus workgroups exit at once and the live ones still spread over all 8 XCDs.
-  la.clamp_rows();
-  const int live = ((la.rows + BM_ - 1) / BM_) * tiles_n;
+  int arows;                                         // rows of A under the device-side bound
+  if constexpr (LoaderIsSeg<ALoader>::value) arows = la.bounded_rows();      // (a segmented loader is never written to)
+  else { la.clamp_rows(); arows = la.rows; }
+  const int live = ((arows + BM_ - 1) / BM_) * tiles_n;
   if ((int)blockIdx.x >= live) return;
   // A parity-class launch scatters its rows over the input map: the rows at or behind the device-side bound are not written (a storing
   // class launch left zeros in the pixels of dead images that fell into its last live tile; the accumulating one already left them alone).
@@ -82,12 +88,38 @@ gemm_nt_kernel(ALoader la, DenseLoader<T> lb, int M, int N, int K, int tiles_n, 
   const int kchunk = ((lane & 7) ^ lrow) * G::VEC;   // logical K offset of the chunk this lane fetches
 
   constexpr bool kDenseA = ALoader::kDense;
-  // dense A operand (ALoader = DenseLoader<T>): the same per-row / per-column state as B
-  typename DenseLoader<T>::Ctx actx[kDenseA ? NA : 1], bctx[NB];
-  typename DenseLoader<T>::KPos aq = {}, bq = lb.kpos(kchunk);
+  // K-segmented A operand (SegLoader<T>): the dense interface; the stepping pointers below are re-derived at every segment boundary,
+  // and the M dimension may be a device-side list of live rows / 16-row blocks (EpiParams::live_list, as gemm_nt8_live's: tile position
+  // j is row live_list[j] or row live_list[j / 16] * 16 + j % 16 of A and of the output; positions behind the list are nobody's).
+  constexpr bool kSegA = LoaderIsSeg<ALoader>::value;
+  typedef typename DenseCtxOf<ALoader, T>::type ADense;
+  int nlisted = -1;                                  // kSegA with a list: positions the list covers
+  if constexpr (kSegA) {
+    if (ep.live_list != nullptr) {
+      nlisted = min(*ep.live_count * ep.live_unit, M);
+      if (m0 >= nlisted) return;
+    }
+  }
+  auto orow = [&](int j) -> int {                    // tile position -> row of A / of the output (M: none)
+    if constexpr (kSegA) {
+      if (nlisted >= 0) {
+        if (j >= nlisted) return M;
+        return ep.live_unit == 1 ? ep.live_list[j] : ep.live_list[j >> 4] * 16 + (j & 15);
+      }
+    }
+    return j;
+  };
+  // dense A operand (ALoader = DenseLoader<T> / SegLoader<T>): the same per-row / per-column state as B
+  typename ADense::Ctx actx[kDenseA ? NA : 1];
+  typename DenseLoader<T>::Ctx bctx[NB];
+  typename ADense::KPos aq = {};
+  typename DenseLoader<T>::KPos bq = lb.kpos(kchunk);
   if constexpr (kDenseA) {
 #pragma unroll
-    for (int j = 0; j < NA; ++j) actx[j] = la.prepare(m0 + (wave * NA + j) * 8 + lrow);
+    for (int j = 0; j < NA; ++j) {
+      if constexpr (kSegA) actx[j] = la.prepare(orow(m0 + (wave * NA + j) * 8 + lrow), arows);
+      else actx[j] = la.prepare(orow(m0 + (wave * NA + j) * 8 + lrow));
+    }
     aq = la.kpos(kchunk);
   }
 #pragma unroll
@@ -102,6 +134,8 @@ gemm_nt_kernel(ALoader la, DenseLoader<T> lb, int M, int N, int K, int tiles_n, 
   const int nfast = K / G::BK;
   const bool fast = nfast > 0, fast_all = (K % G::BK) == 0;
   int kt_issue = 0;
+  int seg_tile = 0, seg_tiles = 0;                   // kSegA: K-tiles issued inside the current segment, K-tiles per segment
+  if constexpr (kSegA) seg_tiles = la.Ks / G::BK;
   const char* pa[NA];
   const char* pb[NB];
   int inca[NA], incb[NB];
@@ -134,6 +168,17 @@ gemm_nt_kernel(ALoader la, DenseLoader<T> lb, int M, int N, int K, int tiles_n, 
     } else if (f) {
 #pragma unroll
       for (int j = 0; j < NA; ++j) { glds16(pa[j], base + (wave * NA + j) * 1024); pa[j] += inca[j]; }
+      if constexpr (kSegA) {
+        if (++seg_tile == seg_tiles) {               // (uniform over the workgroup) the next K-tile starts the next segment
+          seg_tile = 0;
+          la.advance(aq, la.Ks);
+#pragma unroll
+          for (int j = 0; j < NA; ++j) {
+            const void* p0 = la.addr(actx[j], aq, zero);
+            pa[j] = (const char*)p0; inca[j] = (p0 != zero) ? G::BK * (int)sizeof(T) : 0;
+          }
+        }
+      }
     } else {
       if (fast && kt_issue == nfast) aq = la.kpos(kchunk + nfast * G::BK);
 #pragma unroll
@@ -229,7 +274,7 @@ gemm_nt_kernel(ALoader la, DenseLoader<T> lb, int M, int N, int K, int tiles_n, 
     uint4* rec = (uint4*)ep.dec.rec;
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
-      const int row = m0 + wm * 64 + i * 16 + l15;
+      const int row = orow(m0 + wm * 64 + i * 16 + l15);
       auto val = [&](int j) { return dec_round<T>(acc[i][j] + b4[j]); };
       int label = -1;
       if (ep.dec.labels != nullptr && row < M) {
@@ -262,7 +307,7 @@ gemm_nt_kernel(ALoader la, DenseLoader<T> lb, int M, int N, int K, int tiles_n, 
     for (int t = 0; t < ITEMS; ++t) {
       const int e = lane + 64 * t, r = e / ITEMS, c8 = e - r * ITEMS;
       const floatx4 v0 = *(const floatx4*)(et + r * RS + c8 * 8), v1 = *(const floatx4*)(et + r * RS + c8 * 8 + 4);
-      epilogue8<T>(ep, M, N, m0 + wm * 64 + r, n0 + wn * 16 * NF + c8 * 8, v0, v1);
+      epilogue8<T>(ep, M, N, orow(m0 + wm * 64 + r), n0 + wn * 16 * NF + c8 * 8, v0, v1);
     }
     return;
   }
@@ -270,7 +315,7 @@ gemm_nt_kernel(ALoader la, DenseLoader<T> lb, int M, int N, int K, int tiles_n, 
   for (int i = 0; i < 4; ++i)
 #pragma unroll
     for (int j = 0; j < NF; ++j)
-      epilogue4<T>(ep, M, N, m0 + wm * 64 + i * 16 + l15, n0 + wn * 16 * NF + j * 16 + 4 * g, acc[i][j]);
+      epilogue4<T>(ep, M, N, orow(m0 + wm * 64 + i * 16 + l15), n0 + wn * 16 * NF + j * 16 + 4 * g, acc[i][j]);
 }
 
 static int g_nt_n96 = 1;             // allow 128x96 tiles (tuning / A-B knob)
@@ -332,7 +377,7 @@ static int launch_nt_4w_mma(hipStream_t st, int path, const ALoader& la, const D
       if constexpr (DEC == 0) return launch_nt_tile<T, ALoader, NT_PATH_4W_256x64, X3, DEC>(st, la, lb, M, N, K, ep);
       break;
     case NT_PATH_4W_256x128:
-      if constexpr (DEC == 0 && !X3 && ALoader::kDense && sizeof(T) == 2) return launch_nt_tile<T, ALoader, NT_PATH_4W_256x128, X3, DEC>(st, la, lb, M, N, K, ep);
+      if constexpr (DEC == 0 && !X3 && ALoader::kDense && !LoaderIsSeg<ALoader>::value && sizeof(T) == 2) return launch_nt_tile<T, ALoader, NT_PATH_4W_256x128, X3, DEC>(st, la, lb, M, N, K, ep);
       break;
     default: break;
   }
@@ -460,6 +505,34 @@ int gemm_nt(hipStream_t st, const T* A, int64_t lda, const T* B, int64_t ldb, in
   la.rows_dev = rows_dev;
   return launch_nt<T, DenseLoader<T>>(st, la, B, ldb, M, N, K, ep);
 }
+// ---- K-segmented A operand (models.py:628-629, `integrate` over torch.cat): out = [A_0 | .. | A_{n-1}] . B^T + bias in one launch and
+// one fp32 accumulation over K = n * Ks in segment order; the 4-wave tiles of the cost rule (the choice a gathered launch gets: a
+// function of M and N alone, so the materialised concatenation takes the same tile wherever it stays on the 4-wave kernels, and the
+// two results are then the same bits).  Plain store (+ bias) only; optionally over a device-side list of live rows / 16-row blocks.
+template <typename T>
+int gemm_nt_cat(hipStream_t st, int nseg, const T* const* A, const int64_t* lda, int Ks, const T* B, int64_t ldb, int M, int N,
+                const EpiParams<T>& ep) {
+  if (nseg < 2 || nseg > SEG_MAX || A == nullptr || lda == nullptr || B == nullptr || ep.out == nullptr) return RL_ERR_ARG;
+  if (Ks <= 0 || (Ks % Geo<T>::BK) != 0 || Ks > 0x7FFFFFFF / SEG_MAX) return RL_ERR_ARG;      // no staged K-tile straddles two segments
+  if (ep.mode != EPI_STORE || ep.accumulate || ep.out2 != nullptr || ep.aux != nullptr || ep.dec.kc != 0 || ep.out_f32 != nullptr ||
+      ep.m_dev != nullptr || ep.slab != nullptr || ep.rm_hw_shift >= 0 || ep.col_scale != nullptr || ep.gru_table != nullptr) return RL_ERR_ARG;
+  if ((ep.live_list == nullptr) != (ep.live_count == nullptr)) return RL_ERR_ARG;
+  if (ep.live_list != nullptr && ep.live_unit != 1 && ep.live_unit != 16) return RL_ERR_ARG;
+  SegLoader<T> la;
+  for (int s = 0; s < nseg; ++s) {
+    if (A[s] == nullptr || !gemm_nt_args_ok<T>(lda[s], ep)) return RL_ERR_ARG;
+  }
+  la.set(nseg, A, lda);
+  const int K = nseg * Ks;
+  la.nseg = nseg; la.Ks = Ks; la.rows = M; la.K = K;
+  const int path = nt_path<T>(false, false, M, N, K, ep, 0, ldb);
+  if (path == NT_PATH_NONE) return RL_OK;
+  if (path == NT_PATH_REFUSED) return RL_ERR_ARG;
+  DenseLoader<T> lb{B, ldb, N, K};
+  return launch_nt_4w<T, SegLoader<T>, 0>(st, path, la, lb, M, N, K, ep);
+}
+template int gemm_nt_cat<bf16_t>(hipStream_t, int, const bf16_t* const*, const int64_t*, int, const bf16_t*, int64_t, int, int, const EpiParams<bf16_t>&);
+template int gemm_nt_cat<float>(hipStream_t, int, const float* const*, const int64_t*, int, const float*, int64_t, int, int, const EpiParams<float>&);
 // ---- decode launch: C = A . B^T + bias reduced per row to its best k entries and its log-sum-exp; no C anywhere ----
 // Route: NT_PATH_8P exactly where the plain store of the same shape (out pitch N) takes it - same body, same tile, same k-order, so the
 // accumulators are those of the storing launch bit for bit -; likewise on the 4-wave 128 x 128 / 128 x 96 tiles.  Where the storing

@@ -61,6 +61,7 @@ struct Layout {
   int64_t head_w = -1, head_b = -1, head_ln_g = -1, head_ln_b = -1;   // BertPredictionHeadTransform (Variant::mlm_head); cls_w / cls_b are then its decoder
   int64_t pho_emb = -1, gru_w_ih = -1, gru_w_hh = -1, gru_b_ih = -1, gru_b_hh = -1;
   int64_t res_ln_g = -1, res_ln_b = -1, gate_w = -1, gate_b = -1;
+  int64_t int_w = -1, int_b = -1;                      // integrate [H, nsrc * H] + bias (Variant::concat), where gate_net sits on a gate model
   int64_t glyph = -1;                                  // AR_FROZEN
   Tower tower;                                         // nblocks == 0 without the glyph branch
   BlockOff blocks[TOWER_MAX_BLOCKS];
@@ -82,12 +83,18 @@ struct Variant {
   bool gate = false;     // gate fusion (gate_net); false on an arch model: sum fusion
   int nsrc = 1;          // fusion sources: bert + the present branches
   bool gate_softmax = false;   // the gates are one softmax over the gate_net outputs (model_type 3, models.py:1143-1144), not sigmoids
+  bool concat = false;         // concatenation fusion (model_type 6 / 7, models.py:628-629 / :228-229): integrate = nn.Linear(nsrc * H, H) over
+                               // torch.cat of the branches; arch is true, gate is false, and the fusion is `integrate`, not the sum
   bool mlm_head = false;       // the classifier is BertOnlyMLMHead (model_type 4, modeling_bert.py:419-462): dense -> erf GELU -> LayerNorm in
                                // front of an untied decoder [V, H] + bias; keys cls.predictions.*, no classifier.*
 };
 inline Variant variant_of(const realise_config& c) {
   Variant v;
   if (c.model_type == 5) { v.bert = false; v.pho = true; v.mlm_head = true; return v; }
+  if (c.model_type == 6 || c.model_type == 7) {      // SpellBertPho2ResArch2 (models.py:513-649) / SpellBertPho2 (models.py:163-249)
+    v.arch = true; v.concat = true; v.pho = true; v.res = c.model_type == 6; v.nsrc = v.res ? 3 : 2;
+    return v;
+  }
   v.arch = c.model_type == 1 || c.model_type == 2 || c.model_type == 3 || c.model_type == 4;
   if (!v.arch) return v;
   const bool abla = c.model_type == 2;
@@ -105,8 +112,13 @@ inline Variant variant_of(const realise_config& c) {
 // model_type 5 has no word table to tie its decoder to: untied only.  It is the pinyin branch without the glyph branch, and its config
 // says so in the branch switches (with_pho == 1, with_res == 0): a type-5 config that claims a glyph branch, such as another model's
 // config with the number changed, describes no model and is refused.
+// model_type 6 / 7 (the concatenation models) follow that precedent: the config says what the model is - both branches and fusion 2
+// for SpellBertPho2ResArch2, whose glyph table is nn.Embedding(vocab, 1024) (models.py:533: one font, 32x32), the pinyin branch alone
+// and fusion 2 for SpellBertPho2 - and their output_block is two layers deep (models.py:546, :185).  The tie rules are Arch3's: either.
 inline bool variant_valid(const realise_config& c) {
-  if (c.model_type < 0 || c.model_type > 5) return false;
+  if (c.model_type < 0 || c.model_type > 7) return false;
+  if (c.model_type == 6) return c.with_pho == 1 && c.with_res == 1 && c.fusion == 2 && c.num_fonts == 1 && c.glyph_size == 32 && c.out_layers == 2;
+  if (c.model_type == 7) return c.with_pho == 1 && c.with_res == 0 && c.fusion == 2 && c.out_layers == 2;
   if (c.model_type == 5) return c.tie_classifier == 0 && c.with_pho == 1 && c.with_res == 0;
   if (c.model_type == 3) return c.num_fonts == 1 && c.glyph_size == 32;
   if (c.model_type == 4) return c.num_fonts == 1 && c.glyph_size == 32 && c.tie_classifier == 0;
@@ -244,6 +256,10 @@ inline Layout build_layout(const realise_config& c) {
     if (vr.gate) {
       L.gate_w = add(AR_TRAIN, "gate_net.weight", {vr.nsrc, (vr.nsrc + 1) * H});
       L.gate_b = add(AR_TRAIN, "gate_net.bias", {vr.nsrc});
+    }
+    if (vr.concat) {      // models.py:544, :183 - where gate_net sits; alone in this bucket without the glyph branch
+      L.int_w = add(AR_TRAIN, "integrate.weight", {H, vr.nsrc * H});
+      L.int_b = add(AR_TRAIN, "integrate.bias", {H});
     }
     if (vr.res) {
       L.res_ln_g = add(AR_TRAIN, "resnet_layernorm.weight", {H});

@@ -1,10 +1,12 @@
 """Training-step time of the full model and the four ablations of SpellBertPho2ResArch3Abla (src/models_abla.py:33-299), and of
 SpellBertPho2ResArch4 (src/models.py:1023-1170) against SpellBertPho2ResArch3 with one font - the same tensors and schedule, softmax
-gates instead of sigmoids - and of SpellBertPho2ResArch3MLM (src/models.py:874-1020: the BERT MLM head as the classifier):
+gates instead of sigmoids - and of SpellBertPho2ResArch3MLM (src/models.py:874-1020: the BERT MLM head as the classifier), and of the
+concatenation models SpellBertPho2ResArch2 (src/models.py:513-649) and SpellBertPho2 (src/models.py:163-249):
 
     python tools/abla_step_time.py [--batch 64] [--seq 128] [--warmup 5] [--steps 12] [--rounds 2] [--variants full,sum,...]
     python tools/abla_step_time.py --variants arch3_1font,arch4 --baseline arch3_1font --rounds 4
     python tools/abla_step_time.py --variants arch3_1font,arch3_mlm --baseline arch3_1font --rounds 4
+    python tools/abla_step_time.py --variants arch3_1font,arch2,pho2 --baseline arch3_1font --rounds 4
 
 One process; per variant and round a fresh model (bf16, train_logits = False, FusedAdamW with the trainer's trusted operand copies,
 the pinyin table on the device) timed the way bench.py's loop is: warm-up steps, then `--steps` steps between two device events.
@@ -28,12 +30,13 @@ from realise_amd.models_abla import SpellBertPho2ResArch3Abla               # no
 from realise_amd.modeling import SpellBertPho2ResArch3                      # noqa: E402
 from realise_amd.models_arch4 import SpellBertPho2ResArch4                  # noqa: E402
 from realise_amd.models_mlm import SpellBertPho2ResArch3MLM                 # noqa: E402
+from realise_amd.models_concat import SpellBertPho2, SpellBertPho2ResArch2  # noqa: E402
 from realise_amd.optim import FusedAdamW, get_linear_schedule_with_warmup   # noqa: E402
 
 VARIANTS = [("full", None), ("no_pho", ("no", "yes", "gate")), ("no_res", ("yes", "no", "gate")),
             ("no_pho_no_res", ("no", "no", "gate")), ("sum", ("yes", "yes", "sum")),
             ("arch3_1font", SpellBertPho2ResArch3), ("arch4", SpellBertPho2ResArch4),      # a class: that model with num_fonts = 1
-            ("arch3_mlm", SpellBertPho2ResArch3MLM)]
+            ("arch3_mlm", SpellBertPho2ResArch3MLM), ("arch2", SpellBertPho2ResArch2), ("pho2", SpellBertPho2)]
 
 
 def make(v, B, S, dev):

@@ -4,7 +4,7 @@ image_model_type 1 (arch3_img1_*, abla_img1_*, resnet1_*).
 
 TEST INFRASTRUCTURE; run only where the reference tree exists (oracle/_ref_import.py):
 
-    PYTHONDONTWRITEBYTECODE=1 python tools/make_golden_variants.py [abla] [arch4] [mlm] [resnet1] [pretrain] [--out DIR]
+    PYTHONDONTWRITEBYTECODE=1 python tools/make_golden_variants.py [abla] [arch4] [mlm] [resnet1] [concat] [pretrain] [--out DIR]
 
 Without a group name every group is generated.  Inputs are regenerated from seeds (realise_amd.init.init_state_dict_numpy(...,
 scheme="perturbed"), realise_amd.data.synthetic_batch, realise_amd.data.glyph_upstream_grad); the fixtures hold summaries in the
@@ -25,6 +25,16 @@ possible and the tests hold that block and the blocks upstream of it to a looser
   with two rows repeated, so that the deduplication has work to do), a strided sample of the tower output and - because a strided
   sample alone can alias the period-4 `c * 4 + p` permutation - its first two rows in full.
 
+* concat: SpellBertPho2ResArch2 (models.py:513-649) and SpellBertPho2 (models.py:163-249), the concatenation models; every fixture
+  also stores a strided sample of the `integrate` output (`fused`, taken with a forward hook).  The arch4 group's recipe.
+  Losses of the committed fixtures, as printed (B = 2, S = 16, 2 layers, dropout 0, perturbed init; every position above the margin
+  in all five): arch2_b2s16_train 10.175839 (seed 66, smallest margin 1.43e-02, 9 parameters without a gradient), arch2_b2s16_eval
+  10.334391 (seed 62, 1.90e-03), arch2_img1_b2s16_train 9.831989 (seed 63, 8.02e-03, 9), pho2_b2s16_train 9.963987 (seed 64, 1.82e-03,
+  8), pho2_b2s16_eval 10.227773 (seed 65, 4.77e-03).  Seed 61 of the CharResNet train case left one pre-ReLU input of block 5 within
+  2e-5 of zero: the looser bar a near-flip gives that block is a cosine over the strided sample, and the sample of block 5's 3x3 weight
+  gradients on its 1x1 map holds off-centre taps only - exact zeros on both sides, no cosine.  A CharResNet train case of this group
+  with relu_near0/5 != 0 stops the generator; seed 66 has none.
+
 * pretrain: Pho2Pretrain (models.py:1286-1347), the pinyin encoder's pretraining model, on realise_amd.data.synthetic_pretrain_batch
   (holes in loss_masks; PRETRAIN_CASES: in the b3s40 case sentence 1 has no loss position at all).  Next to the loss, the logits
   summary and the gradients a fixture holds what the reference's forward returns - `pred_ids` and `active_labels` of the active rows in
@@ -32,7 +42,7 @@ possible and the tests hold that block and the blocks upstream of it to a looser
   (`active_logits`) and the taps `head_z`, `head_y`, `pho_out` (the pho stack's output).  EVERY active position must have a margin
   above 1e-4 or the generator stops: the tests compare the ids at all of them.  Losses of the committed fixtures are printed by the run.
 
-The tests compare arg-max ids above a top-1 / top-2 margin of 1e-4.  The arch4 and mlm tests expect that to be every position, the
+The tests compare arg-max ids above a top-1 / top-2 margin of 1e-4.  The arch4, mlm and concat tests expect that to be every position, the
 resnet1 tests at least 95 % of them: a case with more positions under the margin than its group allows stops the generator (pick
 another seed).
 """
@@ -60,6 +70,7 @@ from make_golden import put                                        # noqa: E402
 NEAR0 = 2e-5
 MARGIN = 1e-4
 FULL = ("yes", "yes", "gate")
+PHO_ONLY = ("yes", "no", "gate")      # (the concatenation models do not read the switches: what a config of theirs carries)
 
 # name: the fixture's file name (None: run as a check, store nothing); switches: (with_pho, with_res, fusion); expect: the loss
 # measured when the model was scoped, or None
@@ -80,12 +91,17 @@ CASES = [
     Case("resnet1", "arch3_img1_b2s16_train", "arch3", FULL, 1, 31, True, None),
     Case("resnet1", "arch3_img1_b2s16_eval", "arch3", FULL, 1, 32, False, None),
     Case("resnet1", "abla_img1_phono_resyes_gate_b2s16_train", "arch3-abla", ("no", "yes", "gate"), 1, 33, True, None),
+    Case("concat", "arch2_b2s16_train", "arch2", FULL, 0, 66, True, None),
+    Case("concat", "arch2_b2s16_eval", "arch2", FULL, 0, 62, False, None),
+    Case("concat", "arch2_img1_b2s16_train", "arch2", FULL, 1, 63, True, None),
+    Case("concat", "pho2_b2s16_train", "pho2", PHO_ONLY, 0, 64, True, None),
+    Case("concat", "pho2_b2s16_eval", "pho2", PHO_ONLY, 0, 65, False, None),
 ]
 # per group: the font count of its configs, which inputs its fixtures record under meta/, the share of positions that may lie under
 # the arg-max margin (None: no stop)
 Group = collections.namedtuple("Group", "num_fonts meta_switches meta_image_model_type max_under")
 GROUPS = {"abla": Group(3, True, False, None), "arch4": Group(1, False, True, 0.0), "mlm": Group(1, False, True, 0.0),
-          "resnet1": Group(1, True, True, 0.05)}
+          "resnet1": Group(1, True, True, 0.05), "concat": Group(1, False, True, 0.0)}
 
 
 def config(group, switches, image_model_type, n_layers):
@@ -164,7 +180,16 @@ def mlm_store(store, taken, train):
     return "head |z| max %.2f" % float(taken["z"].abs().max())
 
 
-EXTRAS = {"arch4": (arch4_hook, arch4_store), "mlm": (mlm_hook, mlm_store)}
+def concat_hook(m, hooks, taken):
+    hooks.append(m.integrate.register_forward_hook(lambda mod, i, o: taken.__setitem__("fused", o.detach().clone())))
+
+
+def concat_store(store, taken, train):
+    put(store, "fused", taken["fused"])
+    return "|fused| max %.2f" % float(taken["fused"].abs().max())
+
+
+EXTRAS = {"arch4": (arch4_hook, arch4_store), "mlm": (mlm_hook, mlm_store), "concat": (concat_hook, concat_store)}
 
 
 def case(mods, BertConfig, out, c, B=2, S=16, n_layers=2):
@@ -223,6 +248,8 @@ def case(mods, BertConfig, out, c, B=2, S=16, n_layers=2):
     if group.max_under is not None and under > group.max_under * B * S:
         raise SystemExit("seed %d: %d of %d positions under the arg-max margin (the %s tests allow %g %%); pick another seed"
                          % (c.seed, under, B * S, c.group, 100 * group.max_under))
+    if c.group == "concat" and c.train and near0.get("relu_near0/5", 0):
+        raise SystemExit("seed %d: a pre-ReLU input of block 5 lies within %g of zero (see the docstring); pick another seed" % (c.seed, NEAR0))
     if c.name is not None:
         np.savez_compressed(os.path.join(out, c.name + ".npz"), **store)
 
@@ -346,6 +373,7 @@ STATE_DICTS = {
     "mlm": ("mlm_state_dict.json", 0, [(None, "arch3-mlm", FULL)]),
     "resnet1": ("resnet1_state_dicts.json", 1, [("arch3", "arch3", FULL), ("abla_phoyes_resyes_gate", "arch3-abla", FULL),
                                                 ("abla_phono_resyes_gate", "arch3-abla", ("no", "yes", "gate"))]),
+    "concat": ("concat_state_dicts.json", 0, [("arch2", "arch2", FULL), ("pho2", "pho2", PHO_ONLY)]),
 }
 
 
