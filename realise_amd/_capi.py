@@ -7,7 +7,7 @@ is no CPU or PyTorch fallback.
 import ctypes as C
 import os
 
-from .config import CONCAT_OUT_LAYERS, MODEL_TYPES, model_type_number  # noqa: F401
+from .config import MODEL_TYPES, model_row, out_layers_of  # noqa: F401
 
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "librealise_hip.so")
@@ -275,26 +275,21 @@ def check(rc, what):
 
 
 def make_config(cfg, model_type, dtype, tie=True):
+    row = model_row(model_type)      # (refuses a name that is not built)
     c = Config()
-    c.model_type = model_type_number(model_type)
+    c.model_type = row.number
     c.dtype = dtype
     c.hidden, c.heads, c.intermediate = cfg["hidden_size"], cfg["num_attention_heads"], cfg["intermediate_size"]
     c.vocab, c.max_pos, c.type_vocab = cfg["vocab_size"], cfg["max_position_embeddings"], cfg["type_vocab_size"]
-    c.bert_layers, c.pho_layers, c.out_layers = cfg["num_hidden_layers"], cfg["pho_layers"], cfg["out_layers"]
-    if c.model_type in (6, 7):      # the concatenation models hard-wire a two-layer output_block (models.py:546, :185)
-        c.out_layers = CONCAT_OUT_LAYERS
+    c.bert_layers, c.pho_layers, c.out_layers = cfg["num_hidden_layers"], cfg["pho_layers"], out_layers_of(cfg, model_type)
     c.num_fonts, c.glyph_size, c.pho_vocab = cfg["num_fonts"], cfg["glyph_size"], cfg["pho_vocab_size"]
     c.hidden_dropout, c.attn_dropout = cfg["hidden_dropout_prob"], cfg["attention_probs_dropout_prob"]
     c.ln_eps = cfg["layer_norm_eps"]
     c.tie_classifier = 1 if tie else 0
-    # the ablation switches (model_type 2 only; src/models_abla.py:37-39)
-    c.with_pho = 1 if cfg.get("with_pho", "yes") == "yes" else 0
-    c.with_res = 1 if cfg.get("with_res", "yes") == "yes" else 0
-    c.fusion = 1 if cfg.get("fusion", "gate") == "sum" else 0
-    if c.model_type == 5:      # Pho2Pretrain is the pinyin branch without the glyph branch, whatever the config's ablation switches say
-        c.with_pho, c.with_res, c.fusion = 1, 0, 0
-    if c.model_type in (6, 7):  # the concatenation models: what they are, whatever the config's ablation switches say; fusion 2 = integrate
-        c.with_pho, c.with_res, c.fusion = 1, (1 if c.model_type == 6 else 0), 2
+    # the ablation switches (src/models_abla.py:37-39), or what the model is where its row says so, whatever the config's switches say
+    c.with_pho, c.with_res, c.fusion = row.forced or (1 if cfg.get("with_pho", "yes") == "yes" else 0,
+                                                      1 if cfg.get("with_res", "yes") == "yes" else 0,
+                                                      1 if cfg.get("fusion", "gate") == "sum" else 0)
     # the glyph encoder (run.py:419-421): 0 = CharResNet, 1 = CharResNet1; read where the model has a glyph branch
     c.image_model_type = int(cfg.get("image_model_type", 0))
     return c

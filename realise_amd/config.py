@@ -117,39 +117,41 @@ class RealiseConfig(dict):
         return c
 
 
-# model_type -> (number in the C ABI, reference class, line of src/models.py where that class hard-wires the one-font glyph table
-# nn.Embedding(vocab_size, 1024), or None).  A new model is a row here and a case in variant_of.
-_MODELS = {
-    "bert": (0, "SpellBert", None),
-    "arch3": (1, "SpellBertPho2ResArch3", None),
-    "arch3-abla": (2, "SpellBertPho2ResArch3Abla", None),
-    "arch4": (3, "SpellBertPho2ResArch4", 1043),
-    "arch3-mlm": (4, "SpellBertPho2ResArch3MLM", 894),
-}
-MODEL_TYPES = {k: row[0] for k, row in _MODELS.items()}
-# run_pretrain.py:33-36 keeps a MODEL_CLASSES table of its own, and so do the pretraining models here: same row format, the ABI numbers
-# go on where MODEL_TYPES' stop.  variant_of / tensor_specs / validate / _capi.make_config take a name from either table.
-_PRETRAIN_MODELS = {
-    "pho2-pretrain": (5, "Pho2Pretrain", None),
-}
-PRETRAIN_MODEL_TYPES = {k: row[0] for k, row in _PRETRAIN_MODELS.items()}
-# run_pretrain.py's other entries, named so that they are refused with their reason instead of as an unknown string
-_PRETRAIN_NOT_BUILT = {
+# The models, one row each; csrc/layout.h's MODEL_ROWS is the library's table of the same models, row for row by ``number``.  A new
+# model is a row here and one there, its module class, and engine code for whatever it computes that no model before it did.
+#   number          realise_config.model_type in the C ABI
+#   one_font_line   line of src/models.py where the class hard-wires the one-font glyph table nn.Embedding(vocab_size, 1024), or None
+#   head_prefix     state_dict prefix of its BertOnlyMLMHead ("cls.", Pho2Pretrain's "cls2."), or None: a plain classifier
+#   family          the public table that lists it: "run" (run.py:40-51), "pretrain" (run_pretrain.py:33-36), "concat" (run.py's models
+#                   with integrate = nn.Linear(n * H, H) over torch.cat, models.py:628-629, :228-229)
+#   bert .. gate_softmax   the Variant's fields; fusion is "gate", "concat" or None
+#   switches        the ablation switches are read (src/models_abla.py:37-45): they drop branches and turn the gate into the sum
+#   out_layers      hard-wired depth of output_block (models.py:546, :185), or None: the config's
+#   forced          (with_pho, with_res, fusion) that _capi.make_config writes whatever the config says - the library wants such a
+#                   model's config to state what the model is - or None: the config's switches
+Model =collections.namedtuple("Model", "name number reference_class one_font_line head_prefix family bert arch pho res fusion gate_softmax "
+                                        "switches out_layers forced")
+_T, _F = True, False
+MODELS = {r.name: r for r in (
+    #     name             number  reference class           font  head     family      bert arch pho res fusion    softmax switches out  forced
+    Model("bert",          0, "SpellBert",                   None, None,    "run",      _T, _F, _F, _F, None,     _F, _F, None, None),
+    Model("arch3",         1, "SpellBertPho2ResArch3",       None, None,    "run",      _T, _T, _T, _T, "gate",   _F, _F, None, None),
+    Model("arch3-abla",    2, "SpellBertPho2ResArch3Abla",   None, None,    "run",      _T, _T, _T, _T, "gate",   _F, _T, None, None),
+    Model("arch4",         3, "SpellBertPho2ResArch4",       1043, None,    "run",      _T, _T, _T, _T, "gate",   _T, _F, None, None),
+    Model("arch3-mlm",     4, "SpellBertPho2ResArch3MLM",    894,  "cls.",  "run",      _T, _T, _T, _T, "gate",   _F, _F, None, None),
+    Model("pho2-pretrain", 5, "Pho2Pretrain",                None, "cls2.", "pretrain", _F, _F, _T, _F, None,     _F, _F, None, (1, 0, 0)),
+    Model("arch2",         6, "SpellBertPho2ResArch2",       533,  None,    "concat",   _T, _T, _T, _T, "concat", _F, _F, 2,    (1, 1, 2)),
+    Model("pho2",          7, "SpellBertPho2",               None, None,    "concat",   _T, _T, _T, _F, "concat", _F, _F, 2,    (1, 0, 2)),
+)}
+MODEL_TYPES = {r.name: r.number for r in MODELS.values() if r.family == "run"}
+PRETRAIN_MODEL_TYPES = {r.name: r.number for r in MODELS.values() if r.family == "pretrain"}
+CONCAT_MODEL_TYPES = {r.name: r.number for r in MODELS.values() if r.family == "concat"}
+CONCAT_OUT_LAYERS = MODELS["arch2"].out_layers       # models.py:546, :185
+# the other entries of run_pretrain.py's and run.py's MODEL_CLASSES: refused by name with their reason, never mapped to another model
+NOT_BUILT = {
     "pho2res-pretrain": "Pho2ResPretrain (models.py:1216-1284) is not implemented: only 'pho2-pretrain' runs here",
     "res-pretrain": "ResPretrain (models.py:1349-1420) is not implemented: about a thousand steps over 256 glyphs that finish in a minute "
                     "on any device; only 'pho2-pretrain' runs here",
-}
-# The concatenation models of run.py:40-51 ('bert-pho2-res-arch2', 'bert-pho2'): the branches are fused by integrate =
-# nn.Linear(n * H, H) over torch.cat (models.py:628-629, :228-229) in front of a two-layer output_block.  A third table of the same row
-# format; the ABI numbers go on.  SpellBertPho2ResArch2 hard-wires the one-font glyph table at models.py:533.
-_CONCAT_MODELS = {
-    "arch2": (6, "SpellBertPho2ResArch2", 533),
-    "pho2": (7, "SpellBertPho2", None),
-}
-CONCAT_MODEL_TYPES = {k: row[0] for k, row in _CONCAT_MODELS.items()}
-CONCAT_OUT_LAYERS = 2       # models.py:546, :185
-# run.py's remaining MODEL_CLASSES entries, refused by name with their reason and never mapped to another model
-_RUN_NOT_BUILT = {
     "bert-pho1": "SpellBertPho1 (models.py:76-160) is not implemented: it reads three pinyin id planes (initial, final, tone) from "
                  "another converter (Pinyin.convert) and has no GRU; of the concatenation models 'bert-pho2' and "
                  "'bert-pho2-res-arch2' run here",
@@ -161,50 +163,42 @@ _RUN_NOT_BUILT = {
 }
 
 
+def model_row(model_type):
+    """the row of a name in MODELS; a name of NOT_BUILT or an unknown one raises with its reason"""
+    if model_type in NOT_BUILT:
+        raise ValueError("model_type %r: %s" % (model_type, NOT_BUILT[model_type]))
+    if model_type not in MODELS:
+        raise ValueError("model_type must be 'bert', 'arch3', 'arch3-abla', 'arch4' or 'arch3-mlm' (or 'pho2-pretrain' of PRETRAIN_MODEL_TYPES, "
+                         "'arch2' / 'pho2' of CONCAT_MODEL_TYPES)")
+    return MODELS[model_type]
+
+
 def model_type_number(model_type):
     """the C ABI's realise_config.model_type of a name from MODEL_TYPES, PRETRAIN_MODEL_TYPES or CONCAT_MODEL_TYPES"""
-    if model_type in MODEL_TYPES:
-        return MODEL_TYPES[model_type]
-    if model_type in PRETRAIN_MODEL_TYPES:
-        return PRETRAIN_MODEL_TYPES[model_type]
-    if model_type in CONCAT_MODEL_TYPES:
-        return CONCAT_MODEL_TYPES[model_type]
-    variant_of({}, model_type)      # raises with the reason
+    return model_row(model_type).number
 
-# What a model computes: csrc/layout.h's ``Variant`` field for field (``gates`` is G: 0 without a gate_net, otherwise its ``nsrc``),
-# then what only Python needs: ``one_font`` (the hard-wired [V, 1024] glyph table, at src/models.py:``one_font_line``) and the
-# reference class name for messages, ``head_prefix`` (the state_dict prefix of an MLM head: "cls." or Pho2Pretrain's "cls2.", else None).
-# ``bert``: the model has the bert stack (false: Pho2Pretrain, the pinyin branch alone).  Every Python-side decision reads this, not
-# ``model_type``.
-# ``concat``: the fusion is `integrate` over the concatenation (CONCAT_MODEL_TYPES): arch is true, gate false, gates 0.
+
+# What a model computes: csrc/layout.h's ``Variant`` field for field (``gates`` is G: 0 without a gate_net, otherwise ``nsrc``), then
+# what only Python needs: ``one_font`` (the hard-wired [V, 1024] glyph table, at src/models.py:``one_font_line``), the reference class
+# name for messages and ``head_prefix``.  Every Python-side decision reads this, not ``model_type``.
+# ``bert``: the model has the bert stack (false: Pho2Pretrain).  ``concat``: the fusion is `integrate` over the concatenation, gates 0.
+# ``nsrc`` (a property: the tuple is the thirteen fields): the fusion sources, bert and the present branches.
 Variant = collections.namedtuple("Variant", "arch pho res gate gates gate_softmax mlm_head one_font one_font_line reference_class bert head_prefix concat",
                                  defaults=(False,))
+Variant.nsrc = property(lambda v: 1 + v.pho + v.res if v.arch else 1)
 
 
 def variant_of(cfg, model_type):
-    if model_type in _PRETRAIN_NOT_BUILT:
-        raise ValueError("model_type %r: %s" % (model_type, _PRETRAIN_NOT_BUILT[model_type]))
-    if model_type in _RUN_NOT_BUILT:
-        raise ValueError("model_type %r: %s" % (model_type, _RUN_NOT_BUILT[model_type]))
-    if model_type in _CONCAT_MODELS:        # SpellBertPho2ResArch2 (models.py:513-649) / SpellBertPho2 (models.py:163-249)
-        _, reference_class, one_font_line = _CONCAT_MODELS[model_type]
-        return Variant(arch=True, pho=True, res=model_type == "arch2", gate=False, gates=0, gate_softmax=False, mlm_head=False,
-                       one_font=one_font_line is not None, one_font_line=one_font_line, reference_class=reference_class, bert=True,
-                       head_prefix=None, concat=True)
-    if model_type in _PRETRAIN_MODELS:      # Pho2Pretrain (models.py:1286-1347): pho_embeddings, pho_gru, pho_model and the MLM head cls2
-        _, reference_class, _ = _PRETRAIN_MODELS[model_type]
-        return Variant(arch=False, pho=True, res=False, gate=False, gates=0, gate_softmax=False, mlm_head=True, one_font=False,
-                       one_font_line=None, reference_class=reference_class, bert=False, head_prefix="cls2.")
-    if model_type not in _MODELS:
-        raise ValueError("model_type must be 'bert', 'arch3', 'arch3-abla', 'arch4' or 'arch3-mlm' (or 'pho2-pretrain' of PRETRAIN_MODEL_TYPES, "
-                         "'arch2' / 'pho2' of CONCAT_MODEL_TYPES)")
-    _, reference_class, one_font_line = _MODELS[model_type]
-    arch = model_type != "bert"
-    abla = model_type == "arch3-abla"      # src/models_abla.py:37-45: the switches drop whole branches; (yes, yes, gate) is arch3
-    pho = arch and (not abla or cfg.get("with_pho", "yes") == "yes")
-    res = arch and (not abla or cfg.get("with_res", "yes") == "yes")
-    gate = arch and (not abla or cfg.get("fusion", "gate") == "gate")
-    return Variant(arch=arch, pho=pho, res=res, gate=gate, gates=(1 + pho + res) if gate else 0,
-                   gate_softmax=model_type == "arch4", mlm_head=model_type == "arch3-mlm",
-                   one_font=one_font_line is not None, one_font_line=one_font_line, reference_class=reference_class, bert=True,
-                   head_prefix="cls." if model_type == "arch3-mlm" else None)
+    r = model_row(model_type)
+    pho = r.pho and (not r.switches or cfg.get("with_pho", "yes") == "yes")
+    res = r.res and (not r.switches or cfg.get("with_res", "yes") == "yes")
+    fusion = "sum" if r.switches and cfg.get("fusion", "gate") != "gate" else r.fusion
+    v = Variant(arch=r.arch, pho=pho, res=res, gate=fusion == "gate", gates=0, gate_softmax=r.gate_softmax,
+                mlm_head=r.head_prefix is not None, one_font=r.one_font_line is not None, one_font_line=r.one_font_line,
+                reference_class=r.reference_class, bert=r.bert, head_prefix=r.head_prefix, concat=fusion == "concat")
+    return v._replace(gates=v.nsrc) if v.gate else v
+
+
+def out_layers_of(cfg, model_type):
+    """depth of output_block: the row's where the reference hard-wires it, else the config's"""
+    return model_row(model_type).out_layers or cfg["out_layers"]

@@ -70,59 +70,66 @@ struct Layout {
 
 inline int64_t align64(int64_t x) { return (x + 63) & ~(int64_t)63; }
 
-// What a configuration computes: SpellBert is the bert stack alone, SpellBertPho2ResArch3 has every branch, the ablation model
-// (model_type 2, src/models_abla.py:33-96) what its switches keep, SpellBertPho2ResArch4 (model_type 3, models.py:1023-1170) every
-// branch with a softmax over the gates, SpellBertPho2ResArch3MLM (model_type 4, models.py:874-1020) Arch3 with BertOnlyMLMHead as
-// its classifier, Pho2Pretrain (model_type 5, models.py:1286-1347) the pinyin branch alone under a BertOnlyMLMHead named cls2: no
-// bert stack, no fusion, no output block.  Every layout / engine decision reads this, not model_type.
+// What a configuration computes.  Every layout / engine decision reads this, not model_type.
 struct Variant {
-  bool bert = true;      // the bert stack under a (tied or untied) classifier; false: the model starts at the pinyin branch (model_type 5)
-  bool arch = false;     // output_block behind a fusion of the branches (model_type 1, 2, 3, 4)
+  bool bert = true;      // the bert stack under a (tied or untied) classifier; false: the model starts at the pinyin branch
+  bool arch = false;     // output_block behind a fusion of the branches
   bool pho = false;      // pinyin branch: pho_embeddings, pho_gru, pho_model
   bool res = false;      // glyph branch: glyph table, resnet, resnet_layernorm
-  bool gate = false;     // gate fusion (gate_net); false on an arch model: sum fusion
+  bool gate = false;     // gate fusion (gate_net); false on an arch model without concat: sum fusion
   int nsrc = 1;          // fusion sources: bert + the present branches
-  bool gate_softmax = false;   // the gates are one softmax over the gate_net outputs (model_type 3, models.py:1143-1144), not sigmoids
-  bool concat = false;         // concatenation fusion (model_type 6 / 7, models.py:628-629 / :228-229): integrate = nn.Linear(nsrc * H, H) over
-                               // torch.cat of the branches; arch is true, gate is false, and the fusion is `integrate`, not the sum
-  bool mlm_head = false;       // the classifier is BertOnlyMLMHead (model_type 4, modeling_bert.py:419-462): dense -> erf GELU -> LayerNorm in
-                               // front of an untied decoder [V, H] + bias; keys cls.predictions.*, no classifier.*
+  bool gate_softmax = false;   // the gates are one softmax over the gate_net outputs (models.py:1143-1144), not sigmoids
+  bool concat = false;         // the fusion is integrate = nn.Linear(nsrc * H, H) over torch.cat of the branches (models.py:628-629, :228-229)
+  bool mlm_head = false;       // the classifier is BertOnlyMLMHead (modeling_bert.py:419-462): cls.predictions.* (cls2. without bert), no classifier.*
 };
+// The models, one row per realise_config.model_type; variant_of and variant_valid below only read the row.  A new model is a row here
+// (and one in realise_amd/config.py) plus engine code for whatever it computes that no row before it did.
+enum Fuse { FUSE_NONE = -1, FUSE_GATE = 0, FUSE_SUM = 1, FUSE_CONCAT = 2 };      // the values of realise_config.fusion
+enum States { STATES_NOTHING, STATES_BRANCHES, STATES_BRANCHES_FUSION };           // what the config must say about the model itself
+struct ModelRow {
+  bool bert, arch, pho, res; Fuse fuse;
+  bool switches;         // with_pho / with_res / fusion are read (src/models_abla.py:37-45): they drop branches, turn the gate into the sum
+  bool gate_softmax, mlm_head;
+  bool one_font;         // the glyph table is nn.Embedding(vocab, 1024) viewed as [N, 1, 32, 32]: num_fonts == 1, glyph_size == 32
+  bool untied_only;      // the decoder is the model's own (tie_cls_weight is a `pass`, models.py:915-917) or there is no word table to tie to
+  States states;         // with_pho / with_res (and fusion) must equal the row's: another model's config with the number changed is refused
+  int out_layers;        // hard-wired depth of output_block (models.py:546, :185); 0: the config's
+};
+static constexpr ModelRow MODEL_ROWS[] = {
+  // bert  arch   pho    res    fuse         switch softmax mlm   1font  untied states                  out
+  {true,  false, false, false, FUSE_NONE,   false, false, false, false, false, STATES_NOTHING,         0},   // 0 SpellBert
+  {true,  true,  true,  true,  FUSE_GATE,   false, false, false, false, false, STATES_NOTHING,         0},   // 1 SpellBertPho2ResArch3
+  {true,  true,  true,  true,  FUSE_GATE,   true,  false, false, false, false, STATES_NOTHING,         0},   // 2 ...Arch3Abla (models_abla.py:33-96)
+  {true,  true,  true,  true,  FUSE_GATE,   false, true,  false, true,  false, STATES_NOTHING,         0},   // 3 ...Arch4 (models.py:1023-1170)
+  {true,  true,  true,  true,  FUSE_GATE,   false, false, true,  true,  true,  STATES_NOTHING,         0},   // 4 ...Arch3MLM (models.py:874-1020)
+  {false, false, true,  false, FUSE_NONE,   false, false, true,  false, true,  STATES_BRANCHES,        0},   // 5 Pho2Pretrain (models.py:1286-1347)
+  {true,  true,  true,  true,  FUSE_CONCAT, false, false, false, true,  false, STATES_BRANCHES_FUSION, 2},   // 6 ...Arch2 (models.py:513-649)
+  {true,  true,  true,  false, FUSE_CONCAT, false, false, false, false, false, STATES_BRANCHES_FUSION, 2},   // 7 SpellBertPho2 (models.py:163-249)
+};
+inline const ModelRow* model_row(const realise_config& c) {
+  return c.model_type >= 0 && c.model_type < (int)(sizeof(MODEL_ROWS) / sizeof(MODEL_ROWS[0])) ? &MODEL_ROWS[c.model_type] : nullptr;
+}
 inline Variant variant_of(const realise_config& c) {
   Variant v;
-  if (c.model_type == 5) { v.bert = false; v.pho = true; v.mlm_head = true; return v; }
-  if (c.model_type == 6 || c.model_type == 7) {      // SpellBertPho2ResArch2 (models.py:513-649) / SpellBertPho2 (models.py:163-249)
-    v.arch = true; v.concat = true; v.pho = true; v.res = c.model_type == 6; v.nsrc = v.res ? 3 : 2;
-    return v;
-  }
-  v.arch = c.model_type == 1 || c.model_type == 2 || c.model_type == 3 || c.model_type == 4;
-  if (!v.arch) return v;
-  const bool abla = c.model_type == 2;
-  v.pho = !abla || c.with_pho != 0;
-  v.res = !abla || c.with_res != 0;
-  v.gate = !abla || c.fusion == 0;
-  v.nsrc = 1 + (v.pho ? 1 : 0) + (v.res ? 1 : 0);
-  v.gate_softmax = c.model_type == 3;
-  v.mlm_head = c.model_type == 4;
+  const ModelRow* r = model_row(c); if (!r) return v;
+  v.bert = r->bert; v.arch = r->arch; v.gate_softmax = r->gate_softmax; v.mlm_head = r->mlm_head;
+  v.pho = r->pho && (!r->switches || c.with_pho != 0);
+  v.res = r->res && (!r->switches || c.with_res != 0);
+  const Fuse f = r->switches && c.fusion != 0 ? FUSE_SUM : r->fuse;
+  v.gate = f == FUSE_GATE; v.concat = f == FUSE_CONCAT;
+  if (v.arch) v.nsrc = 1 + (v.pho ? 1 : 0) + (v.res ? 1 : 0);
   return v;
 }
-// model_type 2 fields in range, sum fusion only with both branches (the reference's sum path adds None otherwise).  model_type 3 keeps
-// its glyph table as nn.Embedding(vocab, 1024) viewed as [N, 1, 32, 32] (models.py:1043,1134): one font, 32x32 glyphs, nothing else.
-// model_type 4 has the same table (models.py:894,985) and a decoder of its own (tie_cls_weight is a `pass`, models.py:915-917): untied only.
-// model_type 5 has no word table to tie its decoder to: untied only.  It is the pinyin branch without the glyph branch, and its config
-// says so in the branch switches (with_pho == 1, with_res == 0): a type-5 config that claims a glyph branch, such as another model's
-// config with the number changed, describes no model and is refused.
-// model_type 6 / 7 (the concatenation models) follow that precedent: the config says what the model is - both branches and fusion 2
-// for SpellBertPho2ResArch2, whose glyph table is nn.Embedding(vocab, 1024) (models.py:533: one font, 32x32), the pinyin branch alone
-// and fusion 2 for SpellBertPho2 - and their output_block is two layers deep (models.py:546, :185).  The tie rules are Arch3's: either.
+// The rules of the row, each applied only where the row states it: what it does not state is carried unchecked.  Where the switches
+// are read they are in range, and the sum fusion has both branches (the reference's sum path adds None otherwise).
 inline bool variant_valid(const realise_config& c) {
-  if (c.model_type < 0 || c.model_type > 7) return false;
-  if (c.model_type == 6) return c.with_pho == 1 && c.with_res == 1 && c.fusion == 2 && c.num_fonts == 1 && c.glyph_size == 32 && c.out_layers == 2;
-  if (c.model_type == 7) return c.with_pho == 1 && c.with_res == 0 && c.fusion == 2 && c.out_layers == 2;
-  if (c.model_type == 5) return c.tie_classifier == 0 && c.with_pho == 1 && c.with_res == 0;
-  if (c.model_type == 3) return c.num_fonts == 1 && c.glyph_size == 32;
-  if (c.model_type == 4) return c.num_fonts == 1 && c.glyph_size == 32 && c.tie_classifier == 0;
-  if (c.model_type != 2) return true;
+  const ModelRow* r = model_row(c); if (!r) return false;
+  if (r->one_font && (c.num_fonts != 1 || c.glyph_size != 32)) return false;
+  if (r->untied_only && c.tie_classifier != 0) return false;
+  if (r->states != STATES_NOTHING && (c.with_pho != (int)r->pho || c.with_res != (int)r->res)) return false;
+  if (r->states == STATES_BRANCHES_FUSION && c.fusion != (int)r->fuse) return false;
+  if (r->out_layers != 0 && c.out_layers != r->out_layers) return false;
+  if (!r->switches) return true;
   if ((c.with_pho != 0 && c.with_pho != 1) || (c.with_res != 0 && c.with_res != 1) || (c.fusion != 0 && c.fusion != 1)) return false;
   return c.fusion == 0 || (c.with_pho == 1 && c.with_res == 1);
 }
@@ -221,29 +228,26 @@ inline Layout build_layout(const realise_config& c) {
     L.pho_emb = add(AR_TRAIN, "pho_embeddings.weight", {c.pho_vocab, H});
     close_bucket(begin);
   };
+  // BertOnlyMLMHead (modeling_bert.py:419-462) in backward completion order: decoder bias and weight, the transform's LayerNorm, its dense
+  auto add_mlm_head = [&](const std::string& p) {
+    L.cls_b = add(AR_TRAIN, p + "predictions.bias", {V});
+    L.cls_w = add(AR_TRAIN, p + "predictions.decoder.weight", {V, H});
+    L.head_ln_g = add(AR_TRAIN, p + "predictions.transform.LayerNorm.weight", {H});
+    L.head_ln_b = add(AR_TRAIN, p + "predictions.transform.LayerNorm.bias", {H});
+    L.head_w = add(AR_TRAIN, p + "predictions.transform.dense.weight", {H, H});
+    L.head_b = add(AR_TRAIN, p + "predictions.transform.dense.bias", {H});
+  };
   if (!vr.bert) {
-    // Pho2Pretrain (models.py:1286-1347): bucket 0 = BertOnlyMLMHead `cls2` in backward completion order, bucket 1 = the pinyin branch.
-    // num_hidden_layers is carried and ignored (models.py:1302 hard-wires the 4 pho layers); no bert.*, classifier.* or cls.* keys.
-    L.cls_b = add(AR_TRAIN, "cls2.predictions.bias", {V});
-    L.cls_w = add(AR_TRAIN, "cls2.predictions.decoder.weight", {V, H});
-    L.head_ln_g = add(AR_TRAIN, "cls2.predictions.transform.LayerNorm.weight", {H});
-    L.head_ln_b = add(AR_TRAIN, "cls2.predictions.transform.LayerNorm.bias", {H});
-    L.head_w = add(AR_TRAIN, "cls2.predictions.transform.dense.weight", {H, H});
-    L.head_b = add(AR_TRAIN, "cls2.predictions.transform.dense.bias", {H});
+    // Pho2Pretrain (models.py:1286-1347): bucket 0 = the head `cls2`, bucket 1 = the pinyin branch.  num_hidden_layers is carried and
+    // ignored (models.py:1302 hard-wires the 4 pho layers); no bert.*, classifier.* or cls.* keys.
+    add_mlm_head("cls2.");
     close_bucket(begin);
     add_pho();
     return L;
   }
   // ---- bucket 0: classifier bias (+ untied weight), output_block
-  if (vr.mlm_head) {
-    // BertOnlyMLMHead (modeling_bert.py:419-462) in backward completion order: decoder bias and weight, the transform's LayerNorm, its dense
-    L.cls_b = add(AR_TRAIN, "cls.predictions.bias", {V});
-    L.cls_w = add(AR_TRAIN, "cls.predictions.decoder.weight", {V, H});
-    L.head_ln_g = add(AR_TRAIN, "cls.predictions.transform.LayerNorm.weight", {H});
-    L.head_ln_b = add(AR_TRAIN, "cls.predictions.transform.LayerNorm.bias", {H});
-    L.head_w = add(AR_TRAIN, "cls.predictions.transform.dense.weight", {H, H});
-    L.head_b = add(AR_TRAIN, "cls.predictions.transform.dense.bias", {H});
-  } else {
+  if (vr.mlm_head) add_mlm_head("cls.");
+  else {
     L.cls_b = add(AR_TRAIN, "classifier.bias", {V});
     if (!c.tie_classifier) L.cls_w = add(AR_TRAIN, "classifier.weight", {V, H});
   }

@@ -15,7 +15,7 @@ import zlib
 
 import numpy as np
 
-from .config import CONCAT_OUT_LAYERS, variant_of
+from .config import out_layers_of, variant_of
 
 
 def _rng(name, seed):
@@ -177,10 +177,9 @@ def tensor_specs(cfg, model_type="arch3"):
             specs.append(("gate_net.weight", (G, (G + 1) * H), "normal"))
             specs.append(("gate_net.bias", (G,), "zeros"))
         if v.concat:      # models.py:544, :183: integrate = nn.Linear(n * H, H); init_weights: weight normal, bias zero
-            n = 1 + int(with_pho) + int(with_res)
-            specs.append(("integrate.weight", (H, n * H), "normal"))
+            specs.append(("integrate.weight", (H, v.nsrc * H), "normal"))
             specs.append(("integrate.bias", (H,), "zeros"))
-        bert("output_block.", CONCAT_OUT_LAYERS if v.concat else cfg["out_layers"])      # (models.py:546, :185 hard-wire two layers)
+        bert("output_block.", out_layers_of(cfg, model_type))      # (models.py:546, :185 hard-wire two layers)
     if v.mlm_head:
         mlm_head(v.head_prefix)
         return specs
