@@ -13,7 +13,7 @@ HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 OBJ = os.path.join(HERE, "_obj")
 LIB = os.path.join(HERE, "librealise_hip.so")
-SOURCES = ["gemm.hip", "gemm_nt8.hip", "gemm_nt8p.hip", "conv_wgrad_c64.hip", "conv_c64_nt.hip", "attention.hip", "ops.hip", "ops2.hip", "engine.hip", "capi.hip", "prof.hip"]
+SOURCES = sorted(f for f in os.listdir(CSRC) if f.endswith(".hip"))       # every translation unit: a new file cannot be forgotten
 FLAGS = ["--offload-arch=gfx950", "-O3", "-std=c++17", "-munsafe-fp-atomics", "-fPIC", "-fno-gpu-rdc"]
 
 

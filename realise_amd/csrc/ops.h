@@ -143,6 +143,7 @@ template <typename T>
 int ce_loss(hipStream_t st, const T* logits, int64_t ld, const int64_t* labels, const int64_t* loss_mask, int rows, int V,
             float* loss_out, float* count_buf, T* dlogits, float* row_loss = nullptr, int64_t ld_dl = 0, const CeCompact& cc = CeCompact(),
             const CePred* pr = nullptr);
+void set_ce_fast(int on);           // bf16 masked cross-entropy with the logits row held in registers (default 1)
 // out[j] = in[idx[j]], j < *n_dev (rows of H elements); out[row] = inv[row] >= 0 ? in[inv[row]] * dropout mask : 0
 template <typename T> int gather_rows(hipStream_t st, const T* in, const int* idx, const int* n_dev, int max_rows, int H, T* out);
 // scale_dev (nullable): a device scalar multiplied into every stored value - the incoming loss gradient, never read on the host
@@ -225,8 +226,6 @@ int gru_table_bwd(hipStream_t st, const float* dtable, int ld_dtable, const floa
 // a BasicBlock's bn2 + shortcut BN (shared dy and ReLU mask read once).  *2 functions return RL_ERR_ARG when the fast path does not apply.
 void set_bn_fast(int on);
 void set_bn_chunks(int n);
-void set_adamw_reg(int on);         // realise_set_ln key 6: AdamW + operand-copy tiles with the in-register transpose (1) or through LDS (0, default)
-void set_ce_fast(int on);           // bf16 masked cross-entropy with the logits row held in registers (default 1)
 // What the BatchNorm launches decide on the host (realise_debug_bn_plan): the choices col_sum / col_sumsq_centered / bn_bwd_reduce(2) /
 // bn_stats_train16 / bn_apply / bn_bwd_apply(2) themselves act on, as pure host functions under the knobs as they stand.
 enum BnKernel { BN_GENERIC = 0, BN_16B = 1, BN_ONEPASS = 2, BN_PAIRED = 3 };
@@ -366,6 +365,7 @@ int adamw_grouped(hipStream_t st, float* p, const float* g, float* m, float* v, 
 template <typename T>
 int adamw_cast_multi(hipStream_t st, const CastDesc* descs, int n, int total_tiles, float* P0, const float* G0, float* M0, float* V0,
                      const uint8_t* group_of_block, const AdamwGroups& gs, const float* norm_sq, float max_norm, int tile_base = 0);
+void set_adamw_reg(int on);         // realise_set_ln key 6: AdamW + operand-copy tiles with the in-register transpose (1) or through LDS (0, default)
 int clip_scale(hipStream_t st, float* g, int64_t n, const float* norm_sq, float max_norm);
 int fill_f32(hipStream_t st, float* p, float v, int64_t n);
 struct FillChunk { int64_t off; int32_t len, pad; };     // off: 4-element aligned

@@ -1,14 +1,12 @@
-// HBM-bound kernels, part 1: masks, embeddings + LayerNorm (K1/K4/K10), bias gradients, dropout,
-// masked cross-entropy (K13), gate fusion (K11).  All row-wise kernels use one 64-lane wave per
+// HBM-bound row kernels that are not yet files of their own: masks, embeddings + LayerNorm (K1/K4/K10), the classifier dropout,
+// masked cross-entropy (K13), arg-max and the decode merge / loss, gate and sum fusion (K11), glyph dedup.  One 64-lane wave per
 // row with 8-16 byte per-lane accesses (a 768-wide row = 3 coalesced 4-element vectors per lane);
 // statistics are always fp32.
 #include "ops.h"
+#include "launch.h"
 
 namespace rl {
-__global__ void col_fold_kernel(float* __restrict__ slots, int slot_stride, int nrec, int n, float* out0, float* out1, int C, int overwrite, int clean, float alpha);
 
-#define RL_LAUNCH_CHECK() (hipGetLastError() == hipSuccess ? RL_OK : RL_ERR_LAUNCH)
-#define RL_TRY(expr) do { const int _rc = (expr); if (_rc != RL_OK) return _rc; } while (0)
 static constexpr int LN_MAXV = 4;   // up to 4 x (64 lanes x 4 elems) = 1024 columns per row
 
 __global__ void mask_to_additive_kernel(const int64_t* __restrict__ m, float* __restrict__ out, int n) {
@@ -167,87 +165,11 @@ __global__ void __launch_bounds__(256) ln_fwd16_kernel(LnFwdArgs<bf16_t> a) {
   }
 }
 
-static int g_ce_fast = 1;                            // bf16 cross-entropy with the row in registers (realise_set_ln key 4)
-void set_ce_fast(int on) { g_ce_fast = on; }
 static int g_ln_fast = 1, g_ln_bwd_blocks = 512;
 // round 5 (realise_set_ln key 5): 1 = the row reductions of the bf16 LayerNorm kernels through DPP (wave_sum_dpp) and the backward on
 // ln_bwd16v2_kernel (no barrier before the first row, four rows of a wave in flight, one-barrier epilogue); 0 = the round-4 kernels
 static int g_ln_v2 = 1, g_ln_bwd_blocks_v2 = 256;
 void set_ln_v2(int on) { g_ln_v2 = on; }
-static int g_bn_fast = 1, g_bn_chunks = 1024;       // bf16 16-byte BatchNorm / column-reduction kernels; row chunks (= workgroups) of the reductions
-static int g_bn_onepass = 1;                        // bf16 training statistics in one pass about the running mean (bn_stats_train16)
-void set_bn_fast(int on) { g_bn_fast = on & 1; g_bn_onepass = (on & 1) && !(on & 2); }
-void set_bn_chunks(int n) { if (n >= 1 && n <= 4096) g_bn_chunks = n; }
-// ---- the host plan of the BatchNorm launches (ops.h; realise_debug_bn_plan): every kernel choice below is made here and nowhere else ----
-static inline int pow2_shift(int C) { int s = 0; while (s < 31 && (1 << s) < C) ++s; return (1 << s) == C ? s : -1; }
-// the 16-byte kernels apply: bf16, C a power of two in [8, 2048], hw a power of two
-static inline bool bn_fast_shape(int elem_bytes, int C, int hw) {
-  const int cs = pow2_shift(C);
-  return elem_bytes == 2 && g_bn_fast && cs >= 3 && cs <= 11 && pow2_shift(hw) >= 0;
-}
-// row chunks of a 16-byte reduction: the knob, at least four row passes per workgroup, the records inside the scratch
-static inline int reduce16_chunks(int rows, int C, int stride) {
-  const int rpp = 2048 / C;
-  int g = g_bn_chunks;
-  const int max_g = (rows + 4 * rpp - 1) / (4 * rpp);
-  if (g > max_g) g = max_g;
-  if ((int64_t)g * stride > COL_SLOT_FLOATS) g = COL_SLOT_FLOATS / stride;
-  return g < 1 ? 1 : g;
-}
-BnPass col_reduce_plan(int elem_bytes, int rows, int C, int hw, bool slots_given, int nout, bool fast) {
-  BnPass p;
-  if (fast && slots_given && bn_fast_shape(elem_bytes, C, hw)) {       // (the 16-byte kernels write records only: they need the scratch)
-    p.kernel = BN_16B; p.stride = nout * C; p.g = reduce16_chunks(rows, C, p.stride); p.fold_wgs = (p.stride + 31) / 32; p.overwrite = 1;
-    return p;
-  }
-  p.tpr_shift = 5;
-  while (p.tpr_shift > 2 && (1 << p.tpr_shift) * 4 > C) --p.tpr_shift;      // 32 threads x 4 columns unless the row is narrower
-  const int tpr = 1 << p.tpr_shift;
-  p.gx = (C + tpr * 4 - 1) / (tpr * 4);
-  int gy = 1024 / p.gx;
-  if (gy < 1) gy = 1;
-  const int rpp = 256 / tpr;
-  const int max_gy = (rows + 4 * rpp - 1) / (4 * rpp);                      // at least 4 passes per workgroup
-  if (gy > max_gy) gy = max_gy;
-  if (gy < 1) gy = 1;
-  if (slots_given) {           // per-chunk partial records [C | C] + ordered fold: bitwise reproducible (gy * 2C <= COL_SLOT_FLOATS)
-    p.stride = 2 * C;
-    if ((int64_t)gy * p.stride > COL_SLOT_FLOATS) gy = COL_SLOT_FLOATS / p.stride;      // (0: refused)
-    p.fold_wgs = ((nout > 1 ? 2 * C : C) + 31) / 32;
-    p.overwrite = 1;
-  }
-  p.g = gy;
-  return p;
-}
-BnPass bn_stats_plan(int elem_bytes, int P, int C, int hw, bool slots_given) {
-  if (slots_given && g_bn_onepass && P > 0 && bn_fast_shape(elem_bytes, C, hw)) {
-    BnPass p;
-    p.kernel = BN_ONEPASS; p.stride = 2 * C; p.g = reduce16_chunks(P, C, p.stride); p.fold_wgs = (C + 31) / 32; p.overwrite = 1;
-    return p;
-  }
-  return col_reduce_plan(elem_bytes, P, C, hw, slots_given, 1, true);
-}
-BnPass bn_map_plan(int elem_bytes, int P, int C, int hw) {
-  BnPass p;
-  p.overwrite = 1;
-  if (bn_fast_shape(elem_bytes, C, hw) && (((int64_t)P * C) & 7) == 0) p.kernel = BN_16B;
-  return p;
-}
-bool bn_pair_ok(int elem_bytes, int P, int C, int hw, bool slots_given) {
-  return col_reduce_plan(elem_bytes, P, C, hw, slots_given, 4, true).kernel == BN_16B && bn_map_plan(elem_bytes, P, C, hw).kernel == BN_16B &&
-         4 * C <= BN_PAIR_SUMS;
-}
-int bn_plan(int elem_bytes, int P, int C, int hw, bool slots_given, int branches, BnPlan& pl) {
-  pl = BnPlan();
-  if ((elem_bytes != 2 && elem_bytes != 4) || P < 1 || C < 4 || (C & 3) || hw < 1 || branches < 1 || branches > 2) return RL_ERR_ARG;
-  pl.stats = bn_stats_plan(elem_bytes, P, C, hw, slots_given);
-  pl.apply = bn_map_plan(elem_bytes, P, C, hw);
-  const bool pair = branches == 2 && bn_pair_ok(elem_bytes, P, C, hw, slots_given);
-  pl.bwd_reduce = col_reduce_plan(elem_bytes, P, C, hw, slots_given, pair ? 4 : 2, true);
-  pl.bwd_apply = bn_map_plan(elem_bytes, P, C, hw);
-  if (pair) pl.bwd_reduce.kernel = pl.bwd_apply.kernel = BN_PAIRED;
-  return (pl.stats.g < 1 || pl.bwd_reduce.g < 1) ? RL_ERR_ARG : RL_OK;
-}
 void set_ln_fast(int on) { g_ln_fast = on; }
 void set_ln_bwd_blocks(int n) { if (g_ln_v2) g_ln_bwd_blocks_v2 = n > 0 ? n : 256; else g_ln_bwd_blocks = n > 0 ? n : 512; }      // (of the active variant)
 
@@ -1109,434 +1031,6 @@ template int embed_bwd<bf16_t>(hipStream_t, const bf16_t*, const int64_t*, int, 
 template int embed_bwd<float>(hipStream_t, const float*, const int64_t*, int, int, int, float*, float*, int, float*);
 
 // ---------------------------------------------------------------------------------------------
-// Column reductions over a row-major [rows][C] matrix: 32 threads x 4 columns wide, 8 row lanes.
-// ---------------------------------------------------------------------------------------------
-template <typename F>
-__global__ void __launch_bounds__(256) col_reduce_kernel(F f, int rows_max, int C, int tpr_shift, float* out0, float* out1, RowBound rb,
-                                                          float* slots, int slot_stride) {
-  // tpr = threads per row (each owns 4 consecutive columns); 256 / tpr rows are read per pass, so a wave always touches
-  // whole contiguous rows (C = 64: 16 threads x 4 cols = one 128-byte bf16 row, 4 rows per wave-instruction).
-  __shared__ floatx4 red[2][256];
-  const int tpr = 1 << tpr_shift, rpp = 256 >> tpr_shift;
-  const int cx = threadIdx.x & (tpr - 1), ry = threadIdx.x >> tpr_shift;
-  const int col = (blockIdx.x * tpr + cx) * 4;
-  const int rows = rb_rows(rb, rows_max);
-  const int chunk = (rows + gridDim.y - 1) / gridDim.y;          // live rows are re-split evenly over the grid
-  const int r0 = blockIdx.y * chunk;
-  const int r1 = min(rows, r0 + chunk);
-  floatx4 a0 = floatx4{0.f, 0.f, 0.f, 0.f}, a1 = floatx4{0.f, 0.f, 0.f, 0.f};
-  if (col < C) {
-    // four independent accumulator pairs: the loads of four row passes are in flight together (one pass at a time left a
-    // 64-column reduction over 957k rows at 1.2 TB/s: a thread's 8-byte load, then its dependent add, then the next load)
-    floatx4 b0 = a0, b1 = a0, c0 = a0, c1 = a0, d0 = a0, d1 = a0;
-    int r = r0 + ry;
-    for (; r + 3 * rpp < r1; r += 4 * rpp) {
-      f(r, col, a0, a1);
-      f(r + rpp, col, b0, b1);
-      f(r + 2 * rpp, col, c0, c1);
-      f(r + 3 * rpp, col, d0, d1);
-    }
-    for (; r < r1; r += rpp) f(r, col, a0, a1);
-    a0 = (a0 + b0) + (c0 + d0);
-    a1 = (a1 + b1) + (c1 + d1);
-  }
-  red[0][threadIdx.x] = a0;
-  red[1][threadIdx.x] = a1;
-  __syncthreads();
-  if (ry == 0 && col < C) {
-    for (int k = 1; k < rpp; ++k) { a0 += red[0][k * tpr + cx]; a1 += red[1][k * tpr + cx]; }
-    if (slot_stride) {     // deterministic path: this row chunk's partial sums go to their own [C | C] record
-      float* rec = slots + (int64_t)blockIdx.y * slot_stride;      // col_fold_kernel adds the records up in a fixed order
-      *(floatx4*)(rec + col) = a0;
-      if (out1 != nullptr) *(floatx4*)(rec + C + col) = a1;
-    } else {
-#pragma unroll
-      for (int j = 0; j < 4; ++j) {
-        atomicAdd(out0 + col + j, a0[j]);
-        if (out1 != nullptr) atomicAdd(out1 + col + j, a1[j]);
-      }
-    }
-  }
-}
-// out[i] (+)= sum over the nrec partial records, in a fixed order: 32 record lanes per column quad (each adds records
-// k, k + 32, ... in order), then a fixed pairwise tree over the 32 lane sums.  One workgroup per 32 columns.
-// overwrite: out = sum (no zero-fill needed before the reduction); clean: the records are left zeroed (accumulator records that the
-// next launch adds into with atomics need no memset).
-__global__ void __launch_bounds__(256) col_fold_kernel(float* __restrict__ slots, int slot_stride, int nrec, int n, float* out0,
-                                                        float* out1, int C, int overwrite, int clean, float alpha) {
-  __shared__ floatx4 red[32][8];
-  const int cq = threadIdx.x & 7, kl = threadIdx.x >> 3;
-  const int i = (blockIdx.x * 8 + cq) * 4;                 // i in [0, n): n = C or 2C laid out [C | C], C % 4 == 0
-  floatx4 s = floatx4{0.f, 0.f, 0.f, 0.f};
-  if (i < n)
-    for (int k = kl; k < nrec; k += 32) {
-      floatx4* p = (floatx4*)(slots + (int64_t)k * slot_stride + i);
-      s += *p;
-      if (clean) *p = floatx4{0.f, 0.f, 0.f, 0.f};
-    }
-  red[kl][cq] = s;
-  __syncthreads();
-#pragma unroll
-  for (int w = 16; w > 0; w >>= 1) {
-    if (kl < w) red[kl][cq] += red[kl + w][cq];
-    __syncthreads();
-  }
-  if (kl == 0 && i < n) {
-    float* o = i < C ? out0 + i : out1 + (i - C);
-    if (overwrite) *(floatx4*)o = red[0][cq] * alpha;
-    else *(floatx4*)o += red[0][cq] * alpha;
-  }
-}
-template <typename F>
-static int launch_col_reduce(hipStream_t st, const F& f, int rows, int C, float* out0, float* out1, const BnPass& pl, RowBound rb = RowBound(),
-                             float* slots = nullptr, float alpha = 1.0f) {
-  if (rows <= 0 || C <= 0) return RL_OK;
-  if (C & 3) return RL_ERR_ARG;
-  if (pl.g < 1) return RL_ERR_ARG;
-  if (slots != nullptr) {      // per-chunk partial records + ordered fold: bitwise reproducible (col_reduce_plan keeps g * 2C <= COL_SLOT_FLOATS)
-    hipLaunchKernelGGL((col_reduce_kernel<F>), dim3(pl.gx, pl.g), dim3(256), 0, st, f, rows, C, pl.tpr_shift, out0, out1, rb, slots, pl.stride);
-    const int n = out1 ? 2 * C : C;
-    hipLaunchKernelGGL(col_fold_kernel, dim3(pl.fold_wgs), dim3(256), 0, st, slots, pl.stride, pl.g, n, out0, out1, C, 1, 0, alpha);     // OVERWRITES out0 / out1
-  } else {
-    if (alpha != 1.0f) return RL_ERR_ARG;        // the scaled form exists on the record + fold path only
-    hipLaunchKernelGGL((col_reduce_kernel<F>), dim3(pl.gx, pl.g), dim3(256), 0, st, f, rows, C, pl.tpr_shift, out0, out1, rb, (float*)nullptr, 0);
-  }
-  return RL_LAUNCH_CHECK();
-}
-
-// ---- bf16 fast path of the column reductions: 16-byte loads, C a power of two in [8, 2048] ----------------------------------
-// One workgroup spans all C columns (C / 8 threads per row, 2048 / C rows per pass) over a contiguous chunk of rows.  The four row
-// passes of an iteration are LOADED before the first is added (4 x 16 B per input tensor in flight per thread, against 4 x 8 B and
-// a 64-bit row * ld multiply per load in the generic kernel), row weights come from a shift, and the per-column constants (mean,
-// rstd) sit in registers for the whole loop.  Partial sums go to the chunk's record and the same ordered fold as above: bitwise
-// reproducible.  The 64-channel reductions over the 957k rows of block 1 went from 1.1-1.6 TB/s to the figures in
-// profiles/round3_bn_probe.log.
-struct RowW16 {                       // multiplicity of a row's glyph (dedup), hw a power of two
-  const float* counts; int hw_shift;
-  __device__ __forceinline__ float operator()(int r) const { return counts ? counts[r >> hw_shift] : 1.0f; }
-};
-template <int N> struct Acc16 { floatx4 lo[N], hi[N]; };
-
-struct WSum16F {                      // sum_r w_r x[r][c]
-  static constexpr int NACC = 1;
-  const bf16_t* x; RowW16 w;
-  struct Item { uint4 x; };
-  struct Ctx {};
-  __device__ __forceinline__ Ctx prep(int, int) const { return Ctx{}; }
-  __device__ __forceinline__ Item load(int64_t e) const { return Item{*(const uint4*)(x + e)}; }
-  __device__ __forceinline__ void add(Acc16<1>& a, const Item& it, const Ctx&, int r) const {
-    floatx4 lo, hi; unpack8(it.x, lo, hi);
-    const float ww = w(r);
-    a.lo[0] += lo * ww; a.hi[0] += hi * ww;
-  }
-};
-struct SumSqC16F {                    // sum_r w_r (x[r][c] - mean[c])^2
-  static constexpr int NACC = 1;
-  const bf16_t* x; const float* mean; RowW16 w;
-  struct Item { uint4 x; };
-  struct Ctx { floatx4 mlo, mhi; };
-  __device__ __forceinline__ Ctx prep(int col, int) const { return Ctx{*(const floatx4*)(mean + col), *(const floatx4*)(mean + col + 4)}; }
-  __device__ __forceinline__ Item load(int64_t e) const { return Item{*(const uint4*)(x + e)}; }
-  __device__ __forceinline__ void add(Acc16<1>& a, const Item& it, const Ctx& c, int r) const {
-    floatx4 lo, hi; unpack8(it.x, lo, hi);
-    lo -= c.mlo; hi -= c.mhi;
-    const float ww = w(r);
-    a.lo[0] += lo * lo * ww; a.hi[0] += hi * hi * ww;
-  }
-};
-// BatchNorm backward sums of NB normalisations that share the incoming gradient and ReLU mask (bn2 and the shortcut's BN both feed
-// out = relu(bn2(c2) + bns(cs)), char_cnn.py:30-32): acc 0 = sum g, acc 1 + b = sum g * xhat_b, with dy and the mask read ONCE.
-template <int NB> struct BnBwd16F {
-  static constexpr int NACC = 1 + NB;
-  const bf16_t* dy; const bf16_t* relu_src; const bf16_t* x[NB]; const float* mean[NB]; const float* rstd[NB];
-  struct Item { uint4 g, o, x[NB]; };
-  struct Ctx { floatx4 mlo[NB], mhi[NB], rlo[NB], rhi[NB]; };
-  __device__ __forceinline__ Ctx prep(int col, int) const {
-    Ctx c;
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      c.mlo[b] = *(const floatx4*)(mean[b] + col); c.mhi[b] = *(const floatx4*)(mean[b] + col + 4);
-      c.rlo[b] = *(const floatx4*)(rstd[b] + col); c.rhi[b] = *(const floatx4*)(rstd[b] + col + 4);
-    }
-    return c;
-  }
-  __device__ __forceinline__ Item load(int64_t e) const {
-    Item it;
-    it.g = *(const uint4*)(dy + e);
-    it.o = relu_src ? *(const uint4*)(relu_src + e) : uint4{0x3f803f80u, 0x3f803f80u, 0x3f803f80u, 0x3f803f80u};
-#pragma unroll
-    for (int b = 0; b < NB; ++b) it.x[b] = *(const uint4*)(x[b] + e);
-    return it;
-  }
-  __device__ __forceinline__ void add(Acc16<NACC>& a, const Item& it, const Ctx& c, int) const {
-    floatx4 glo, ghi, olo, ohi;
-    unpack8(it.g, glo, ghi); unpack8(it.o, olo, ohi);
-#pragma unroll
-    for (int j = 0; j < 4; ++j) { glo[j] = olo[j] > 0.f ? glo[j] : 0.f; ghi[j] = ohi[j] > 0.f ? ghi[j] : 0.f; }
-    a.lo[0] += glo; a.hi[0] += ghi;
-#pragma unroll
-    for (int b = 0; b < NB; ++b) {
-      floatx4 xlo, xhi; unpack8(it.x[b], xlo, xhi);
-      a.lo[1 + b] += glo * ((xlo - c.mlo[b]) * c.rlo[b]);
-      a.hi[1 + b] += ghi * ((xhi - c.mhi[b]) * c.rhi[b]);
-    }
-  }
-};
-
-// One-pass BatchNorm training statistics: S1 = sum w (x - K), S2 = sum w (x - K)^2 about the per-channel pivot K = the first row of
-// the batch itself (round 3 pivoted on the running mean: fresh or foreign running statistics far from the batch mean made the
-// subtraction below cancel - ADVICE round 3).  mean = K + S1 / n, var = S2 / n - (S1 / n)^2: with fp32 sums the cancellation error
-// is ~1e-7 (1 + (mean - K)^2 / var) relative, far inside bf16 activations' own rounding; the fp32 parity mode keeps the two-pass form.
-struct Moments16F {
-  static constexpr int NACC = 2;
-  const bf16_t* x; RowW16 w;
-  struct Item { uint4 x; };
-  struct Ctx { floatx4 klo, khi; };
-  // pivot K = the batch's own first row (a sample of the distribution being measured: |mean - K| is of the order of the standard
-  // deviation whatever the running statistics hold - fresh buffers, buffers loaded from another domain)
-  // (no live row under a device-side bound of 0: row 0 is not read, the pivot is 0 - bn_fold_train_kernel adds the same back)
-  __device__ __forceinline__ Ctx prep(int col, int rows) const {
-    Ctx c;
-    if (rows > 0) unpack8(*(const uint4*)(x + col), c.klo, c.khi);
-    else c.klo = c.khi = floatx4{0.f, 0.f, 0.f, 0.f};
-    return c;
-  }
-  __device__ __forceinline__ Item load(int64_t e) const { return Item{*(const uint4*)(x + e)}; }
-  __device__ __forceinline__ void add(Acc16<2>& a, const Item& it, const Ctx& c, int r) const {
-    floatx4 lo, hi; unpack8(it.x, lo, hi);
-    lo -= c.klo; hi -= c.khi;
-    const float ww = w(r);
-    const floatx4 wlo = lo * ww, whi = hi * ww;
-    a.lo[0] += wlo; a.hi[0] += whi;
-    a.lo[1] += wlo * lo; a.hi[1] += whi * hi;
-  }
-};
-// Ordered fold of the [S1 | S2] records (same lane / tree order as col_fold_kernel) + everything bn_train_kernel does, one workgroup
-// per 32 channels: mean, rstd, scale, shift, running statistics (unbiased variance, momentum), num_batches_tracked.
-__global__ void __launch_bounds__(256) bn_fold_train_kernel(const float* __restrict__ slots, int slot_stride, int nrec, int C, float inv_n, float unbias,
-                                                             const float* __restrict__ gamma, const float* __restrict__ beta, float eps, float momentum,
-                                                             float* rmean, float* rvar, float* mean, float* rstd, float* scale, float* shift, int64_t* nbt,
-                                                             const bf16_t* __restrict__ x0, const int* __restrict__ rows_dev) {
-  __shared__ floatx4 red[2][32][8];
-  const int cq = threadIdx.x & 7, kl = threadIdx.x >> 3;
-  const int c = (blockIdx.x * 8 + cq) * 4;
-  floatx4 s1 = floatx4{0.f, 0.f, 0.f, 0.f}, s2 = s1;
-  if (c < C)
-    for (int k = kl; k < nrec; k += 32) {
-      const float* rec = slots + (int64_t)k * slot_stride;
-      s1 += *(const floatx4*)(rec + c);
-      s2 += *(const floatx4*)(rec + C + c);
-    }
-  red[0][kl][cq] = s1; red[1][kl][cq] = s2;
-  __syncthreads();
-#pragma unroll
-  for (int w = 16; w > 0; w >>= 1) {
-    if (kl < w) { red[0][kl][cq] += red[0][kl + w][cq]; red[1][kl][cq] += red[1][kl + w][cq]; }
-    __syncthreads();
-  }
-  if (blockIdx.x == 0 && threadIdx.x == 0 && nbt != nullptr) *nbt += 1;
-  if (kl == 0 && c < C) {
-    const bool pivot = rows_dev == nullptr || *rows_dev > 0;
-    s1 = red[0][0][cq]; s2 = red[1][0][cq];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-      const float d = s1[j] * inv_n, m = (pivot ? to_f<bf16_t>(x0[c + j]) : 0.f) + d;   // the pivot was the batch's first row (Moments16F::prep)
-      const float var = fmaxf(s2[j] * inv_n - d * d, 0.f);
-      const float rs = 1.0f / sqrtf(var + eps), g = gamma[c + j];
-      mean[c + j] = m; rstd[c + j] = rs; scale[c + j] = g * rs; shift[c + j] = beta[c + j] - m * g * rs;
-      rmean[c + j] = (1.0f - momentum) * rmean[c + j] + momentum * m;
-      rvar[c + j] = (1.0f - momentum) * rvar[c + j] + momentum * (var * unbias);
-    }
-  }
-}
-template <typename F>
-__global__ void __launch_bounds__(256) col_reduce16_kernel(F f, int rows_max, int c_shift, RowBound rb, float* __restrict__ slots, int slot_stride,
-                                                            int dup0_at) {
-  __shared__ floatx4 red[2][256];
-  const int tshift = c_shift - 3, tpr = 1 << tshift, rpp = 256 >> tshift;
-  const int cx = threadIdx.x & (tpr - 1), ry = threadIdx.x >> tshift, col = cx * 8;
-  const int rows = rb_rows(rb, rows_max);
-  const int chunk = (rows + gridDim.x - 1) / gridDim.x;
-  const int r0 = blockIdx.x * chunk, r1 = min(rows, r0 + chunk);
-  Acc16<F::NACC> acc;
-#pragma unroll
-  for (int k = 0; k < F::NACC; ++k) acc.lo[k] = acc.hi[k] = floatx4{0.f, 0.f, 0.f, 0.f};
-  const typename F::Ctx ctx = f.prep(col, rows);
-  int r = r0 + ry;
-  const int64_t step = (int64_t)rpp << c_shift;
-  int64_t e = ((int64_t)r << c_shift) + col;
-  for (; r + 3 * rpp < r1; r += 4 * rpp, e += 4 * step) {
-    const typename F::Item i0 = f.load(e), i1 = f.load(e + step), i2 = f.load(e + 2 * step), i3 = f.load(e + 3 * step);
-    f.add(acc, i0, ctx, r); f.add(acc, i1, ctx, r + rpp); f.add(acc, i2, ctx, r + 2 * rpp); f.add(acc, i3, ctx, r + 3 * rpp);
-  }
-  for (; r < r1; r += rpp, e += step) { const typename F::Item i0 = f.load(e); f.add(acc, i0, ctx, r); }
-  float* rec = slots + (int64_t)blockIdx.x * slot_stride;
-  const int C = 1 << c_shift;
-#pragma unroll
-  for (int k = 0; k < F::NACC; ++k) {
-    red[0][threadIdx.x] = acc.lo[k];
-    red[1][threadIdx.x] = acc.hi[k];
-    __syncthreads();
-    if (ry == 0) {
-      floatx4 lo = acc.lo[k], hi = acc.hi[k];
-      for (int j = 1; j < rpp; ++j) { lo += red[0][j * tpr + cx]; hi += red[1][j * tpr + cx]; }
-      // record layout: accumulator k at [k * C, (k + 1) * C); with dup0_at > 0 (two normalisations) accumulator 0 is stored again at
-      // dup0_at * C and accumulators >= dup0_at move up one slot, so that the folded output reads [sum g | sum g xhat_0 | sum g | sum g xhat_1]
-      const int slot = (dup0_at > 0 && k >= dup0_at) ? k + 1 : k;
-      *(floatx4*)(rec + slot * C + col) = lo; *(floatx4*)(rec + slot * C + col + 4) = hi;
-      if (k == 0 && dup0_at > 0) { *(floatx4*)(rec + dup0_at * C + col) = lo; *(floatx4*)(rec + dup0_at * C + col + 4) = hi; }
-    }
-    __syncthreads();
-  }
-}
-// nout = folded outputs of C floats each, written contiguously to `out` (overwritten); alpha scales them; pl: a BN_16B plan of col_reduce_plan
-template <typename F>
-static int launch_col_reduce16(hipStream_t st, const F& f, int rows, int C, float* out, int dup0_at, const RowBound& rb, float alpha, const BnPass& pl) {
-  if (rows <= 0) return RL_OK;
-  hipLaunchKernelGGL((col_reduce16_kernel<F>), dim3(pl.g), dim3(256), 0, st, f, rows, pow2_shift(C), rb, rb.slots, pl.stride, dup0_at);
-  hipLaunchKernelGGL(col_fold_kernel, dim3(pl.fold_wgs), dim3(256), 0, st, rb.slots, pl.stride, pl.g, pl.stride, out, out + C, C, 1, 0, alpha);
-  return RL_LAUNCH_CHECK();
-}
-
-template <typename T> struct SumF {
-  const T* x; int64_t ld;
-  __device__ __forceinline__ void operator()(int r, int c, floatx4& a0, floatx4&) const { a0 += load4<T>(x + (int64_t)r * ld + c); }
-};
-template <typename T> int bias_grad(hipStream_t st, const T* dy, int64_t ld, int rows, int N, float* out, const int* rows_dev) {
-  if (ld & 3) return RL_ERR_ARG;
-  SumF<T> f{dy, ld};
-  RowBound rb;
-  rb.rows_dev = rows_dev;
-  return launch_col_reduce(st, f, rows, N, out, nullptr, col_reduce_plan((int)sizeof(T), rows, N, 1, false, 1, false), rb);
-}
-template int bias_grad<bf16_t>(hipStream_t, const bf16_t*, int64_t, int, int, float*, const int*);
-template int bias_grad<float>(hipStream_t, const float*, int64_t, int, int, float*, const int*);
-
-template <typename T> struct WSumF {
-  const T* x; int64_t ld; RowBound rb;
-  __device__ __forceinline__ void operator()(int r, int c, floatx4& a0, floatx4&) const {
-    a0 += load4<T>(x + (int64_t)r * ld + c) * rb_weight(rb, r);
-  }
-};
-template <typename T> int col_sum(hipStream_t st, const T* x, int P, int C, float* out, RowBound rb, float scale) {
-  const BnPass pl = col_reduce_plan((int)sizeof(T), P, C, rb.hw, rb.slots != nullptr, 1, true);
-  if constexpr (sizeof(T) == 2) {
-    if (pl.kernel == BN_16B) { WSum16F f{x, RowW16{rb.counts, pow2_shift(rb.hw)}}; return launch_col_reduce16(st, f, P, C, out, 0, rb, scale, pl); }
-  }
-  WSumF<T> f{x, (int64_t)C, rb};
-  return launch_col_reduce(st, f, P, C, out, nullptr, pl, rb, rb.slots, scale);
-}
-template int col_sum<bf16_t>(hipStream_t, const bf16_t*, int, int, float*, RowBound, float);
-template int col_sum<float>(hipStream_t, const float*, int, int, float*, RowBound, float);
-
-template <typename T> struct SumSqCF {
-  const T* x; int64_t ld; const float* mean; RowBound rb;
-  __device__ __forceinline__ void operator()(int r, int c, floatx4& a0, floatx4&) const {
-    const floatx4 d = load4<T>(x + (int64_t)r * ld + c) - *(const floatx4*)(mean + c);
-    a0 += d * d * rb_weight(rb, r);
-  }
-};
-template <typename T> int col_sumsq_centered(hipStream_t st, const T* x, int P, int C, const float* mean, float* out, RowBound rb) {
-  const BnPass pl = col_reduce_plan((int)sizeof(T), P, C, rb.hw, rb.slots != nullptr, 1, true);
-  if constexpr (sizeof(T) == 2) {
-    if (pl.kernel == BN_16B) { SumSqC16F f{x, mean, RowW16{rb.counts, pow2_shift(rb.hw)}}; return launch_col_reduce16(st, f, P, C, out, 0, rb, 1.0f, pl); }
-  }
-  SumSqCF<T> f{x, (int64_t)C, mean, rb};
-  return launch_col_reduce(st, f, P, C, out, nullptr, pl, rb, rb.slots);
-}
-template int col_sumsq_centered<bf16_t>(hipStream_t, const bf16_t*, int, int, const float*, float*, RowBound);
-template int col_sumsq_centered<float>(hipStream_t, const float*, int, int, const float*, float*, RowBound);
-
-template <typename T> struct BnBwdF {
-  const T* dy; const T* relu_src; const T* x; const float* mean; const float* rstd; int64_t ld;
-  __device__ __forceinline__ void operator()(int r, int c, floatx4& a0, floatx4& a1) const {
-    floatx4 g = load4<T>(dy + (int64_t)r * ld + c);
-    if (relu_src != nullptr) {
-      const floatx4 o = load4<T>(relu_src + (int64_t)r * ld + c);
-#pragma unroll
-      for (int j = 0; j < 4; ++j) g[j] = o[j] > 0.f ? g[j] : 0.f;
-    }
-    const floatx4 xh = (load4<T>(x + (int64_t)r * ld + c) - *(const floatx4*)(mean + c)) * *(const floatx4*)(rstd + c);
-    a0 += g;
-    a1 += g * xh;
-  }
-};
-template <typename T>
-int bn_bwd_reduce(hipStream_t st, const T* dy, const T* relu_src, const T* x, const float* mean, const float* rstd, int P, int C,
-                  float* sums, RowBound rb) {
-  const BnPass pl = col_reduce_plan((int)sizeof(T), P, C, rb.hw, rb.slots != nullptr, 2, true);
-  if constexpr (sizeof(T) == 2) {
-    if (pl.kernel == BN_16B) { BnBwd16F<1> f{dy, relu_src, {x}, {mean}, {rstd}}; return launch_col_reduce16(st, f, P, C, sums, 0, rb, 1.0f, pl); }
-  }
-  BnBwdF<T> f{dy, relu_src, x, mean, rstd, (int64_t)C};
-  return launch_col_reduce(st, f, P, C, sums, sums + C, pl, rb, rb.slots);
-}
-int bn_stats_train16(hipStream_t st, const bf16_t* x, int P, int C, int n_stat, const float* gamma, const float* beta, float eps, float momentum,
-                     float* rmean, float* rvar, float* mean, float* rstd, float* scale, float* shift, int64_t* nbt, RowBound rb) {
-  const BnPass pl = bn_stats_plan(2, P, C, rb.hw, rb.slots != nullptr);
-  if (pl.kernel != BN_ONEPASS) return RL_ERR_ARG;
-  Moments16F f{x, RowW16{rb.counts, pow2_shift(rb.hw)}};
-  hipLaunchKernelGGL((col_reduce16_kernel<Moments16F>), dim3(pl.g), dim3(256), 0, st, f, P, pow2_shift(C), rb, rb.slots, pl.stride, 0);
-  const int n = n_stat > 0 ? n_stat : P;
-  hipLaunchKernelGGL(bn_fold_train_kernel, dim3(pl.fold_wgs), dim3(256), 0, st, rb.slots, pl.stride, pl.g, C, 1.0f / (float)n,
-                     (float)n / (float)(n > 1 ? n - 1 : 1), gamma, beta, eps, momentum, rmean, rvar, mean, rstd, scale, shift, nbt, x, rb.rows_dev);
-  return RL_LAUNCH_CHECK();
-}
-// Two normalisations sharing dy and the ReLU mask: sums = [sum g | sum g xhat_a | sum g | sum g xhat_b] (4C floats).  Returns
-// RL_ERR_ARG when the fast path does not apply (the caller then runs the two single reductions).
-int bn_bwd_reduce2(hipStream_t st, const bf16_t* dy, const bf16_t* relu_src, const bf16_t* xa, const float* mean_a, const float* rstd_a,
-                   const bf16_t* xb, const float* mean_b, const float* rstd_b, int P, int C, float* sums, RowBound rb) {
-  if (!bn_pair_ok(2, P, C, rb.hw, rb.slots != nullptr)) return RL_ERR_ARG;
-  BnBwd16F<2> f{dy, relu_src, {xa, xb}, {mean_a, mean_b}, {rstd_a, rstd_b}};
-  return launch_col_reduce16(st, f, P, C, sums, 2, rb, 1.0f, col_reduce_plan(2, P, C, rb.hw, true, 4, true));
-}
-template int bn_bwd_reduce<bf16_t>(hipStream_t, const bf16_t*, const bf16_t*, const bf16_t*, const float*, const float*, int, int, float*, RowBound);
-template int bn_bwd_reduce<float>(hipStream_t, const float*, const float*, const float*, const float*, const float*, int, int, float*, RowBound);
-
-// ---- the two BatchNorm launch sequences (ops.h): what the plan above decides, issued here and nowhere else ----
-template <typename T>
-int bn_stats(hipStream_t st, const T* x, int P, int C, int n_stat, int training, const float* gamma, const float* beta, float eps, float momentum,
-             float* rmean, float* rvar, int64_t* nbt, float* mean, float* rstd, float* scale, float* shift, float* scratch, RowBound rb) {
-  if (!training) return bn_finalize_eval(st, C, gamma, beta, eps, rmean, rvar, scale, shift);
-  const int n = n_stat > 0 ? n_stat : P;
-  if constexpr (sizeof(T) == 2) {
-    if (bn_stats_train16(st, x, P, C, n, gamma, beta, eps, momentum, rmean, rvar, mean, rstd, scale, shift, nbt, rb) == RL_OK) return RL_OK;
-  }
-  if (rb.slots != nullptr) {
-    RL_TRY(col_sum<T>(st, x, P, C, mean, rb, 1.0f / (float)n));          // the fold writes the mean directly
-  } else {
-    RL_TRY(fill_f32(st, scratch, 0.0f, 2 * C));
-    RL_TRY(col_sum<T>(st, x, P, C, scratch, rb));
-    RL_TRY(bn_finalize_mean(st, scratch, C, n, mean));
-  }
-  RL_TRY(col_sumsq_centered<T>(st, x, P, C, mean, scratch + C, rb));
-  return bn_finalize_train(st, mean, scratch + C, C, n, gamma, beta, eps, momentum, rmean, rvar, rstd, scale, shift, nbt);
-}
-template int bn_stats<bf16_t>(hipStream_t, const bf16_t*, int, int, int, int, const float*, const float*, float, float, float*, float*, int64_t*, float*,
-                              float*, float*, float*, float*, RowBound);
-template int bn_stats<float>(hipStream_t, const float*, int, int, int, int, const float*, const float*, float, float, float*, float*, int64_t*, float*,
-                             float*, float*, float*, float*, RowBound);
-template <typename T>
-int bn_backward(hipStream_t st, const T* dy, const T* relu_src, int P, int C, int n_stat, const BnBranch<T>& a, const BnBranch<T>& b, float* sums,
-                RowBound rb) {
-  if constexpr (sizeof(T) == 2) {
-    // (paired while bn_pair_ok says so: the 16-byte kernels apply and 4 C floats fit the sums scratch)
-    if (b.x != nullptr && bn_bwd_reduce2(st, dy, relu_src, a.x, a.mean, a.rstd, b.x, b.mean, b.rstd, P, C, sums, rb) == RL_OK)
-      return bn_bwd_apply2(st, dy, relu_src, a.x, a.mean, a.rstd, a.gamma, a.dx, a.dgamma, a.dbeta, b.x, b.mean, b.rstd, b.gamma, b.dx, b.dgamma,
-                           b.dbeta, sums, P, C, rb, n_stat);
-  }
-  for (const BnBranch<T>* br : {&a, &b}) {
-    if (br->x == nullptr) continue;
-    if (rb.slots == nullptr) RL_TRY(fill_f32(st, sums, 0.0f, 2 * C));      // (atomics; with records the reduction overwrites)
-    RL_TRY(bn_bwd_reduce<T>(st, dy, relu_src, br->x, br->mean, br->rstd, P, C, sums, rb));
-    RL_TRY(bn_bwd_apply<T>(st, dy, relu_src, br->x, br->mean, br->rstd, br->gamma, sums, P, C, br->dx, br->dgamma, br->dbeta, rb, n_stat));
-  }
-  return RL_OK;
-}
-template int bn_backward<bf16_t>(hipStream_t, const bf16_t*, const bf16_t*, int, int, int, const BnBranch<bf16_t>&, const BnBranch<bf16_t>&, float*, RowBound);
-template int bn_backward<float>(hipStream_t, const float*, const float*, int, int, int, const BnBranch<float>&, const BnBranch<float>&, float*, RowBound);
-
-// ---------------------------------------------------------------------------------------------
 // Dropout as a stand-alone map (the one before the classifier, models.py:858)
 // ---------------------------------------------------------------------------------------------
 template <typename T>
@@ -1559,6 +1053,8 @@ template int dropout_apply<float>(hipStream_t, const float*, float*, int, int, D
 // ---------------------------------------------------------------------------------------------
 // Masked cross-entropy (models.py:862-869): one 256-thread workgroup per token row.
 // ---------------------------------------------------------------------------------------------
+static int g_ce_fast = 1;                            // bf16 cross-entropy with the row in registers (realise_set_ln key 4)
+void set_ce_fast(int on) { g_ce_fast = on; }
 // rows that enter the loss: loss_mask == 1 (models.py:864) and label != -100 (CrossEntropyLoss's default ignore_index)
 #define RL_CE_IGNORE_INDEX (-100)
 __global__ void count_active_kernel(const int64_t* __restrict__ m, const int64_t* __restrict__ labels, int n, float* out) {
@@ -2750,5 +2246,95 @@ template <typename T> int argmax_rows(hipStream_t st, const T* logits, int64_t l
 }
 template int argmax_rows<bf16_t>(hipStream_t, const bf16_t*, int64_t, int, int, int64_t*);
 template int argmax_rows<float>(hipStream_t, const float*, int64_t, int, int, int64_t*);
+
+// ---- decode GEMM: merge of the per-slab records (what np.argmax(preds, -1) of src/run.py:262-263 / src/test.py:143 read the [B, S, V]
+// logits for).  One lane per row; records are [plane][slab][row] 16-byte words, so a wave reads 1 KiB lines.  Slabs are folded in
+// ascending column order with the comparator of the epilogue (DecCand, gemm_dev.h): a function of the records alone.
+template <int KC>
+__global__ void __launch_bounds__(64) decode_merge_kernel(const uint4* __restrict__ rec, int nslab, int M, int k, int64_t* __restrict__ ids,
+                                                          float* __restrict__ values, float* __restrict__ probs, float* __restrict__ lse) {
+  const int row = blockIdx.x * 64 + threadIdx.x;
+  if (row >= M) return;
+  uint32_t key[KC]; int col[KC];
+#pragma unroll
+  for (int j = 0; j < KC; ++j) { key[j] = 0u; col[j] = 0x7FFFFFFF; }
+  float m = -__builtin_huge_valf(), s = 0.f;
+  auto beats = [](uint32_t ka, int ca, uint32_t kb, int cb) { return ka > kb || (ka == kb && ca < cb); };
+  auto keyof = [](float x) {
+    const float y = x + 0.0f;
+    const uint32_t u = __float_as_uint(y);
+    return (y != y) ? 0xFFFFFFFFu : (u ^ ((uint32_t)((int32_t)u >> 31) | 0x80000000u));
+  };
+  for (int sl = 0; sl < nslab; ++sl) {
+    uint32_t v[KC]; int c[KC]; float m2, s2;
+    if constexpr (KC == 1) {
+      const uint4 r = rec[(int64_t)sl * M + row];
+      v[0] = r.x; c[0] = (int)r.y; m2 = __uint_as_float(r.z); s2 = __uint_as_float(r.w);
+    } else {
+      const uint4 r0 = rec[(int64_t)sl * M + row], r1 = rec[((int64_t)nslab + sl) * M + row], r2 = rec[((int64_t)2 * nslab + sl) * M + row];
+      v[0] = r0.x; v[1] = r0.y; v[2] = r0.z; v[3] = r0.w;
+      c[0] = (int)r1.x; c[1] = (int)r1.y; c[2] = (int)r1.z; c[3] = (int)r1.w;
+      m2 = __uint_as_float(r2.x); s2 = __uint_as_float(r2.y);
+    }
+    if (c[0] == 0x7FFFFFFF) continue;                  // a slab that lies beyond N as a whole
+#pragma unroll
+    for (int e = 0; e < KC; ++e) {
+      const int ce = c[e];
+      const uint32_t ke = ce == 0x7FFFFFFF ? 0u : keyof(__uint_as_float(v[e]));
+      bool b[KC];
+#pragma unroll
+      for (int j = 0; j < KC; ++j) b[j] = beats(ke, ce, key[j], col[j]);
+#pragma unroll
+      for (int j = KC - 1; j >= 0; --j) {
+        const int jm = j > 0 ? j - 1 : 0;
+        const bool up = j > 0 && b[jm];
+        key[j] = b[j] ? (up ? key[jm] : ke) : key[j];
+        col[j] = b[j] ? (up ? col[jm] : ce) : col[j];
+      }
+    }
+    const float mm = fmaxf(m, m2);
+    s = s * (m == mm ? 1.0f : expf(m - mm)) + s2 * (m2 == mm ? 1.0f : expf(m2 - mm));
+    m = mm;
+  }
+  const float l = m + logf(s);
+  lse[row] = l;
+#pragma unroll
+  for (int j = 0; j < KC; ++j) {
+    if (j < k) {
+      const uint32_t kj = key[j];
+      const float val = __uint_as_float(kj == 0xFFFFFFFFu ? 0x7FC00000u : ((kj & 0x80000000u) ? (kj ^ 0x80000000u) : ~kj));
+      ids[(int64_t)row * k + j] = col[j];
+      values[(int64_t)row * k + j] = val;
+      probs[(int64_t)row * k + j] = expf(val - l);
+    }
+  }
+}
+int decode_merge(hipStream_t st, const float* rec, int kc, int nslab, int M, int k, int64_t* ids, float* values, float* probs, float* lse) {
+  if (!rec || !ids || !values || !probs || !lse || M < 1 || nslab < 1 || k < 1 || k > kc || (kc != 1 && kc != 4)) return RL_ERR_ARG;
+  const dim3 grid((M + 63) / 64);
+  if (kc == 1) hipLaunchKernelGGL((decode_merge_kernel<1>), grid, dim3(64), 0, st, (const uint4*)rec, nslab, M, k, ids, values, probs, lse);
+  else hipLaunchKernelGGL((decode_merge_kernel<4>), grid, dim3(64), 0, st, (const uint4*)rec, nslab, M, k, ids, values, probs, lse);
+  return RL_LAUNCH_CHECK();
+}
+
+// the loss of models.py:862-869 from the decode outputs: mean over the active rows of lse - logit[label]
+__global__ void __launch_bounds__(256) decode_loss_kernel(const float* __restrict__ lse, const float* __restrict__ label_logit,
+                                                          const int64_t* __restrict__ labels, const int64_t* __restrict__ loss_mask, int rows,
+                                                          float* __restrict__ loss_out) {
+  __shared__ float sm[8];
+  float a = 0.f, n = 0.f;
+  for (int i = threadIdx.x; i < rows; i += 256) {
+    if (loss_mask[i] == 1 && labels[i] != -100) { a += lse[i] - label_logit[i]; n += 1.f; }
+  }
+  a = wave_sum(a); n = wave_sum(n);
+  if ((threadIdx.x & 63) == 0) { sm[threadIdx.x >> 6] = a; sm[4 + (threadIdx.x >> 6)] = n; }
+  __syncthreads();
+  if (threadIdx.x == 0) *loss_out = (sm[0] + sm[1] + sm[2] + sm[3]) / (sm[4] + sm[5] + sm[6] + sm[7]);
+}
+int decode_loss(hipStream_t st, const float* lse, const float* label_logit, const int64_t* labels, const int64_t* loss_mask, int rows, float* loss_out) {
+  if (!lse || !label_logit || !labels || !loss_mask || !loss_out || rows < 1) return RL_ERR_ARG;
+  hipLaunchKernelGGL(decode_loss_kernel, dim3(1), dim3(256), 0, st, lse, label_logit, labels, loss_mask, rows, loss_out);
+  return RL_LAUNCH_CHECK();
+}
 
 }  // namespace rl
