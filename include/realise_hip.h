@@ -146,6 +146,13 @@ int realise_conv_tn(void* stream, int dtype, const void* A, int64_t lda, const r
  * over q.k / 8 - 10000 (finite, as the reference's) - there is no -inf and no special case.  The backward recomputes the probabilities as
  * exp(score - lse); rowdot[b][h][q] = sum_d dctx . ctx is its other saved row term (written for every q < S).  In a sentence with at
  * least one live key the dk / dv rows of masked keys are exact zeros. */
+/* Dropout (drop_thresh != 0; 0 disables it and drop_scale is not applied): probability (b, h, q, key) is kept iff the 16 random bits
+ * of counter idx = ((b * nh + h) * S + q) * S + key (mod 2^32; hence B * nh * S * S < 2^32) under drop_seed are >= drop_thresh >> 16 - the
+ * counter rule of every dropout site of this library (csrc/common.h drop_mult) - and a kept probability is multiplied by drop_scale.
+ * All six kernels - forward, dK / dV and dQ, one-tile and tiled - regenerate the mask from this one rule: the index is the absolute
+ * (query, key) pair, whatever tile or lane computes it.  ctx = (p keep scale) V; the backward applies the same factor to dO V^T and to
+ * the probabilities of dV.  tests/row_cases.py att_keep restates the rule; tests/test_row_edges_gpu.py reads it off the outputs of
+ * each kernel. */
 int realise_attention_fwd(void* stream, int dtype, const void* q, const void* k, const void* v, int64_t ldq,
                           const float* mask_add, void* ctx, int64_t ldc, float* lse, int B, int nh, int S,
                           uint32_t drop_seed, uint32_t drop_thresh, float drop_scale);

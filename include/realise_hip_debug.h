@@ -290,6 +290,32 @@ int realise_gru_step_bwd_rows(void* stream, int dtype, const realise_gru_step* a
 int realise_gru_step_fused(void* stream, const realise_gru_step* a, const void* w_hh_bf16, int64_t ldb, const int32_t* n_alive_dev);
 
 
+/* Attention and the row-liveness tables as a live-row training step launches them (engine.hip: attn_fwd / attn_bwd with the table
+ * rlen, row_liveness): thin wrappers over the functions it calls, no arithmetic of their own.  Pinned element by element by
+ * tests/test_row_edges_gpu.py.
+ * attention_fwd_rows / attention_bwd_rows: realise_attention_fwd / _bwd plus rlen, a device pointer to B ints (NULL: the plain call).
+ *   Rows at or beyond rlen[b] of sentence b are padding: masked as keys, never read as queries.  Forward: the q / k / v rows there are
+ *   not read, and the ctx / lse rows of the 32-query blocks that start at or beyond rlen[b] keep what they held (the rows between
+ *   rlen[b] and the end of the block that holds it are written with finite values nobody reads).  Backward: nothing read from such a
+ *   row (q, k, v, ctx, dctx, lse) enters a result, and its dq / dk / dv rows are stored as exact zeros in every head; its rowdot rows
+ *   are not promised.  Rows below rlen[b] are bit-identical to the plain call on the same input with the padding rows zero-filled.
+ *   mask_add must mask every key at or beyond rlen[b].
+ * row_liveness: row (b, s) is live iff s < 1 + the last position of sentence b with masks == 1 or loss_masks == 1 (loss_masks
+ *   nullable).  row_live [B*S] bytes; rlen [B] (nullable) = live rows per sentence; tiles64 / tiles32 / tiles16 (nullable): ascending
+ *   indices of the 64- / 32- / 16-row blocks of the B*S token rows that hold a live row, n_tiles[0..2] their counts; rows (nullable):
+ *   the live rows themselves, ascending, n_tiles[3] of them.  Entries behind a count, and the count of a NULL list, are not written.
+ *   B < 1, S < 1, B*S % 64 != 0 or masks == NULL is refused and nothing is written. */
+int realise_attention_fwd_rows(void* stream, int dtype, const void* q, const void* k, const void* v, int64_t ldq,
+                               const float* mask_add, void* ctx, int64_t ldc, float* lse, int B, int nh, int S,
+                               uint32_t drop_seed, uint32_t drop_thresh, float drop_scale, const int32_t* rlen);
+int realise_attention_bwd_rows(void* stream, int dtype, const void* q, const void* k, const void* v, int64_t ldq,
+                               const float* mask_add, const void* ctx, const void* dctx, int64_t ldc, const float* lse,
+                               float* rowdot, void* dq, void* dk, void* dv, int64_t ldd, int B, int nh, int S,
+                               uint32_t drop_seed, uint32_t drop_thresh, float drop_scale, const int32_t* rlen);
+int realise_row_liveness(void* stream, const int64_t* masks, const int64_t* loss_masks, int B, int S, uint8_t* row_live, int32_t* tiles64,
+                         int32_t* tiles32, int32_t* tiles16, int32_t* n_tiles, int32_t* rlen, int32_t* rows);
+
+
 #ifdef __cplusplus
 }
 #endif

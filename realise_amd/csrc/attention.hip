@@ -309,9 +309,9 @@ attn_bwd_dkv_kernel(const T* __restrict__ q_, const T* __restrict__ k_, const T*
     const float ma = key < S ? mask_add[b * S + key] : 0.0f;
     typename Mma::Frag kf[G::KSTEPS], vf[G::KSTEPS];
 #pragma unroll
-    for (int ks = 0; ks < G::KSTEPS; ++ks) {
-      kf[ks] = gfrag<T>(K, ldq, key, S, ks, g);
-      vf[ks] = gfrag<T>(V, ldq, key, S, ks, g);
+    for (int ks = 0; ks < G::KSTEPS; ++ks) {     // (bound Sl: the keys in [Sl, S) of the tile that straddles Sl are padding rows - zeros, not read)
+      kf[ks] = gfrag<T>(K, ldq, key, Sl, ks, g);
+      vf[ks] = gfrag<T>(V, ldq, key, Sl, ks, g);
     }
     floatx4 dv[4], dk[4];
 #pragma unroll
@@ -662,7 +662,7 @@ attn_bwd_dkv_long_kernel(const T* __restrict__ q_, const T* __restrict__ k_, con
     const int key = k0 + 16 * n + l15;
     ma[n] = key < S ? mask_add[b * S + key] : 0.0f;
 #pragma unroll
-    for (int ks = 0; ks < G::KSTEPS; ++ks) { kf[n][ks] = gfrag<T>(K, ldq, key, S, ks, g); vf[n][ks] = gfrag<T>(V, ldq, key, S, ks, g); }
+    for (int ks = 0; ks < G::KSTEPS; ++ks) { kf[n][ks] = gfrag<T>(K, ldq, key, Sl, ks, g); vf[n][ks] = gfrag<T>(V, ldq, key, Sl, ks, g); }   // (Sl: padding keys are zeros, not read)
   }
   floatx4 dv[2][4], dk[2][4];
 #pragma unroll

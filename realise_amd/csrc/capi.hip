@@ -221,6 +221,25 @@ int realise_attention_bwd(void* stream, int dtype, const void* q, const void* k,
   RL_BY_DTYPE(0, attn_bwd<E>((hipStream_t)stream, (const E*)q, (const E*)k, (const E*)v, ldq, mask_add, (const E*)ctx, (const E*)dctx, ldc, lse, rowdot,
                              (E*)dq, (E*)dk, (E*)dv, ldd, B, nh, S, drop_seed, drop_thresh, drop_scale));
 }
+// the attention launchers and row_liveness as a live-row training step calls them (include/realise_hip_debug.h): no arithmetic of their own
+int realise_attention_fwd_rows(void* stream, int dtype, const void* q, const void* k, const void* v, int64_t ldq, const float* mask_add,
+                               void* ctx, int64_t ldc, float* lse, int B, int nh, int S, uint32_t drop_seed, uint32_t drop_thresh,
+                               float drop_scale, const int32_t* rlen) {
+  RL_BY_DTYPE(0, attn_fwd<E>((hipStream_t)stream, (const E*)q, (const E*)k, (const E*)v, ldq, mask_add, (E*)ctx, ldc, lse, B, nh, S, drop_seed,
+                             drop_thresh, drop_scale, (const int*)rlen));
+}
+int realise_attention_bwd_rows(void* stream, int dtype, const void* q, const void* k, const void* v, int64_t ldq, const float* mask_add,
+                               const void* ctx, const void* dctx, int64_t ldc, const float* lse, float* rowdot, void* dq, void* dk,
+                               void* dv, int64_t ldd, int B, int nh, int S, uint32_t drop_seed, uint32_t drop_thresh, float drop_scale,
+                               const int32_t* rlen) {
+  RL_BY_DTYPE(0, attn_bwd<E>((hipStream_t)stream, (const E*)q, (const E*)k, (const E*)v, ldq, mask_add, (const E*)ctx, (const E*)dctx, ldc, lse, rowdot,
+                             (E*)dq, (E*)dk, (E*)dv, ldd, B, nh, S, drop_seed, drop_thresh, drop_scale, (const int*)rlen));
+}
+int realise_row_liveness(void* stream, const int64_t* masks, const int64_t* loss_masks, int B, int S, uint8_t* row_live, int32_t* tiles64,
+                         int32_t* tiles32, int32_t* tiles16, int32_t* n_tiles, int32_t* rlen, int32_t* rows) {
+  return row_liveness((hipStream_t)stream, masks, loss_masks, B, S, row_live, (int*)tiles64, (int*)tiles32, (int*)tiles16, (int*)n_tiles, (int*)rlen,
+                      (int*)rows);
+}
 int realise_mask_to_additive(void* stream, const int64_t* masks, float* out, int n) {
   return mask_to_additive((hipStream_t)stream, masks, out, n);
 }

@@ -4,11 +4,14 @@ the same ops as plain torch in the kernels' storage types ("statements"), and th
 tests/test_row_edges_gpu.py runs the kernels through them; tests/test_compare_helpers_cpu.py runs the statements and subtly wrong answers
 through them without a GPU.  The bars: DESIGN section 3, "Element-wise bars of the row kernels".
 """
+import functools
 import math
 
+import numpy as np
 import torch
 import torch.nn.functional as F
 
+from gemm_cases import DROP_EDGES, SCALE_P, keep_of_index
 from helpers import TINY, U_BF16, U_FP32, close_elementwise, elem_bound, u_stored
 
 TDT = {"fp32": torch.float32, "bf16": torch.bfloat16}
@@ -107,8 +110,9 @@ def att_lengths(S):
 
 def att_case(S, dt, lengths, seed=0, boost=None):
     """qkv [B*S, 3H], dctx [B*S, H], masks [B, S].  boost = (a, first key, n keys): every query and the keys of that block get the
-    component a * e (e the unit vector (1, .., 1) / 8 of every head) - the block's scores sit a^2 / 8 above the rest."""
-    B, nh = ATT_B, ATT_NH
+    component a * e (e the unit vector (1, .., 1) / 8 of every head) - the block's scores sit a^2 / 8 above the rest.  One sentence per
+    entry of `lengths`."""
+    B, nh = len(lengths), ATT_NH
     H = nh * HD
     qkv = torch.randn((B, S, 3 * H), generator=gen(2000 + S + seed))
     dctx = torch.randn((B * S, H), generator=gen(3000 + S + seed))
@@ -122,9 +126,24 @@ def att_case(S, dt, lengths, seed=0, boost=None):
     return rounded(qkv.reshape(B * S, 3 * H), dt), rounded(dctx, dt), masks
 
 
-def att_reference(qkv, dctx, masks, ctx_stored=None):
-    """float64 softmax(Q K^T / 8 + (1 - mask) * -10000) V and its gradients, with the terms of every element's bar.  All [B, nh, S, .]."""
+def att_keep(seed, thresh, B, nh, S):
+    """bool [B, nh, S, S]: the attention kernels keep probability (b, h, q, key) - keep_of_index at idx = ((b * nh + h) * S + q) * S + key,
+    the one rule of all six kernels (include/realise_hip.h)"""
+    idx = np.arange(B * nh * S * S, dtype=np.uint64)               # the flat index of [B, nh, S, S] IS that idx
+    return torch.from_numpy(keep_of_index(seed, thresh, idx).reshape(B, nh, S, S))
+
+
+def att_mult(keep, scale):
+    """the float64 multiplier of every probability: keep * scale (the scale as the C ABI carries it: a float), 1 without a mask"""
+    return 1.0 if keep is None else keep.to(F64) * float(np.float32(scale))
+
+
+def att_reference(qkv, dctx, masks, ctx_stored=None, keep=None, scale=1.0):
+    """float64 softmax(Q K^T / 8 + (1 - mask) * -10000) -> dropout -> . V and its gradients, with the terms of every element's bar.  All
+    [B, nh, S, .].  keep (bool [B, nh, S, S], None: no dropout) and scale: pd = p keep scale takes the place of p in ctx and dv, and
+    dP = (dO V^T) keep scale; D and dS as without dropout; every _terms tensor carries the same factors."""
     B, S = masks.shape
+    mult = att_mult(keep, scale)
     nh = ATT_NH
     H = nh * HD
 
@@ -139,18 +158,27 @@ def att_reference(qkv, dctx, masks, ctx_stored=None):
     p = torch.exp(s - lse[..., None])
     s_terms = q.abs() @ k.abs().transpose(-1, -2) / 8.0 + madd.abs()[:, None, None, :]
     r = {"p": p, "lse": lse, "lse_terms": (p * s_terms).sum(-1) + (lse - smax).abs()}      # the scores' own terms, weighted as the lse weighs them
-    r["ctx"], r["ctx_terms"] = p @ v, p @ v.abs()
-    dP, dP_terms = dO @ v.transpose(-1, -2), dO.abs() @ v.abs().transpose(-1, -2)
+    pd = p * mult
+    r["pd"] = pd
+    r["ctx"], r["ctx_terms"] = pd @ v, pd @ v.abs()
+    r["dP_raw"] = dO @ v.transpose(-1, -2)
+    dP, dP_terms = r["dP_raw"] * mult, (dO.abs() @ v.abs().transpose(-1, -2)) * mult
     D, D_terms = (dO * r["ctx"]).sum(-1), (dO.abs() * r["ctx_terms"]).sum(-1)
     dS = p * (dP - D[..., None])
     W = p * (dP_terms + D_terms[..., None])
+    r["D"] = D
     r["dq"], r["dq_terms"] = dS @ k / 8.0, W @ k.abs() / 8.0
     r["dk"], r["dk_terms"] = dS.transpose(-1, -2) @ q / 8.0, W.transpose(-1, -2) @ q.abs() / 8.0
-    r["dv"], r["dv_terms"] = p.transpose(-1, -2) @ dO, p.transpose(-1, -2) @ dO.abs()
-    if ctx_stored is not None:       # rowdot is a function of the backward's OWN inputs: the stored ctx
-        cs = heads(ctx_stored)
-        r["rowdot"], r["rowdot_terms"] = (dO * cs).sum(-1), (dO * cs).abs().sum(-1)
+    r["dv"], r["dv_terms"] = pd.transpose(-1, -2) @ dO, pd.transpose(-1, -2) @ dO.abs()
+    if ctx_stored is not None:
+        r.update(rowdot_reference(dctx, ctx_stored, B, S))
     return r
+
+
+def rowdot_reference(dctx, ctx_stored, B, S):
+    """rowdot is a function of the backward's OWN inputs: the stored ctx"""
+    dO, cs = (t.to(F64).reshape(B, S, ATT_NH, HD).permute(0, 2, 1, 3) for t in (dctx, ctx_stored))
+    return {"rowdot": (dO * cs).sum(-1), "rowdot_terms": (dO * cs).abs().sum(-1)}
 
 
 def from_heads(t, B, S):
@@ -163,12 +191,14 @@ def from_heads(t, B, S):
 # the figure times 4; tests/test_compare_helpers_cpu.py re-measures them and holds each to within a factor 2 of what it measures.
 #  * bf16: the probabilities p and the score gradients ds enter their MFMAs as bf16 operands, one rounding (2^-8) more than the output's.
 #    "plain": the unit-spread scores of S = 16..301 and S = 40; "boosted": a block of keys 30 above the rest, where one rounding of a
-#    p near 1 is worth many of the small ones.
+#    p near 1 is worth many of the small ones.  "dropout": att_dropout_cases below - the dropped probabilities leave fewer terms to a sum,
+#    down to one where nearly everything is dropped, and one term carries both roundings (operand and output) undiluted.
 #  * a sentence whose every key is masked: all scores are q.k / 8 - 10000, and fp32 holds them and their lse on a grid of 2^-10 that
 #    float64 does not share.  fp32 ctx, dq, dk, dv: "all masked"; |lse error| / lse_terms (about 10000), fp32 and bf16 runs alike (the lse
 #    is an fp32 output of fp32 scores in both): "all masked lse".
 ATT_MEASURED = {"bf16": {"plain": {"ctx": 5.0e-3, "dv": 4.1e-3, "dq": 7.3e-4, "dk": 3.8e-4},
-                         "boosted": {"ctx": 6.5e-3, "dv": 5.7e-3, "dq": 1.2e-3, "dk": 1.2e-3}},
+                         "boosted": {"ctx": 6.5e-3, "dv": 5.7e-3, "dq": 1.2e-3, "dk": 1.2e-3},
+                         "dropout": {"ctx": 6.1e-3, "dv": 6.8e-3, "dq": 1.8e-3, "dk": 3.2e-3}},
                 "all masked": 5.0e-4, "all masked lse": 5.5e-8}
 
 
@@ -181,10 +211,12 @@ def att_u(dt, name, B, all_masked=(), regime="plain"):
     return u
 
 
-def att_statement(qkv, dctx, masks, dt):
+def att_statement(qkv, dctx, masks, dt, keep=None, scale=1.0, keep_dkv=None, keep_dq=None, dp_scale=None):
     """The same attention as plain torch in the kernel's storage types, on the CPU: fp32 scores + mask, lse = fp32 logsumexp, the gradients
-    recomputed from the stored lse and the stored ctx; bf16: the MFMA operands p and ds and the stored outputs rounded to bf16.  Returns
-    what run_attention returns."""
+    recomputed from the stored lse and the stored ctx; bf16: the MFMA operands pd and ds and the stored outputs rounded to bf16.  Returns
+    what run_attention returns.  keep / scale: the dropout mask (att_keep) and its scale.  What a mutant changes
+    (tests/test_compare_helpers_cpu.py): keep_dkv / keep_dq - the mask the dK / dV and the dQ kernel apply (default: keep); dp_scale - the
+    scale both put on dP (default: scale)."""
     tdt = TDT[dt]
     B, S = masks.shape
     H = ATT_NH * HD
@@ -197,30 +229,50 @@ def att_statement(qkv, dctx, masks, dt):
 
     def op(t):
         return t.to(tdt).float()
+
+    def mult(kp, sc):
+        return 1.0 if kp is None else kp.float() * float(np.float32(sc))
+    keep_dkv = keep if keep_dkv is None else keep_dkv
+    keep_dq = keep if keep_dq is None else keep_dq
+    dp_scale = scale if dp_scale is None else dp_scale
     q, k, v, dO = heads(qkv[:, :H]), heads(qkv[:, H:2 * H]), heads(qkv[:, 2 * H:]), heads(dctx)
     s = q @ k.transpose(-1, -2) * 0.125 + ((1.0 - masks.float()) * -10000.0)[:, None, None, :]
     lse = torch.logsumexp(s, -1)
     p = torch.exp(s - lse[..., None])
-    ctx = (op(p) @ v).to(tdt)
+    ctx = (op(p * mult(keep, scale)) @ v).to(tdt)
     D = (dO * ctx.float()).sum(-1)
-    dS = op(p * (dO @ v.transpose(-1, -2) - D[..., None]) * 0.125)
-    dq, dk, dv = (dS @ k).to(tdt), (dS.transpose(-1, -2) @ q).to(tdt), (op(p).transpose(-1, -2) @ dO).to(tdt)
+    dP = dO @ v.transpose(-1, -2)
+    dS_kv = op(p * (dP * mult(keep_dkv, dp_scale) - D[..., None]) * 0.125)
+    dS_q = op(p * (dP * mult(keep_dq, dp_scale) - D[..., None]) * 0.125)
+    dq, dk = (dS_q @ k).to(tdt), (dS_kv.transpose(-1, -2) @ q).to(tdt)
+    dv = (op(p * mult(keep_dkv, scale)).transpose(-1, -2) @ dO).to(tdt)
     return rows(ctx), lse, D, torch.cat([rows(dq), rows(dk), rows(dv)], 1)
 
 
-def check_attention(dt, qkv, dctx, masks, out, what, all_masked=(), regime="plain", ref=None):
+def check_attention(dt, qkv, dctx, masks, out, what, all_masked=(), regime="plain", ref=None, keep=None, scale=1.0, live=None):
+    """every output element against the float64 reference (ref: the same att_reference, computed once by the caller; its rowdot is added
+    here from the stored ctx where it has none).  live (bool [B, S], None: every row): only these rows of ctx, lse, rowdot and dq / dk /
+    dv are compared - what a live-row launch promises of the others is the caller's to assert."""
     ctx, lse, rowdot, dqkv = out
     B, S = masks.shape
     H = ATT_NH * HD
-    r = att_reference(qkv, dctx, masks, ctx_stored=ctx) if ref is None else ref       # (ref: the same, computed once by the caller)
+    r = att_reference(qkv, dctx, masks, keep=keep, scale=scale) if ref is None else dict(ref)
+    if "rowdot" not in r:
+        r.update(rowdot_reference(dctx, ctx if live is None else torch.where(live.reshape(B * S, 1), ctx, torch.zeros_like(ctx)), B, S))
+    row_sel = torch.ones((B, S), dtype=torch.bool) if live is None else live
+
+    def sel(got, want):                                    # the rows outside `live` take the reference's value: never the worst element
+        m = row_sel[:, None, :, None] if want.dim() == 4 else row_sel[:, None, :]
+        return torch.where(m.expand_as(want), got.to(F64), want)
     lse_u = torch.full((B, 1, 1), U_FP32, dtype=F64)
     for b in all_masked:
         lse_u[b] = 4 * ATT_MEASURED["all masked lse"]
     got = {"ctx": ctx, "dq": dqkv[:, :H], "dk": dqkv[:, H:2 * H], "dv": dqkv[:, 2 * H:]}
-    worst = {"lse": close_elementwise(lse, r["lse"], lse_u * r["lse_terms"] + TINY, what + " lse"),
-             "rowdot": close_elementwise(rowdot, r["rowdot"], elem_bound(U_FP32, r["rowdot_terms"]), what + " rowdot")}
+    worst = {"lse": close_elementwise(sel(lse, r["lse"]), r["lse"], lse_u * r["lse_terms"] + TINY, what + " lse"),
+             "rowdot": close_elementwise(sel(rowdot, r["rowdot"]), r["rowdot"], elem_bound(U_FP32, r["rowdot_terms"]), what + " rowdot")}
     for name in ("ctx", "dv", "dk", "dq"):
-        worst[name] = close_elementwise(from_heads(got[name], B, S), r[name], att_u(dt, name, B, all_masked, regime) * r[name + "_terms"] + TINY, "%s %s" % (what, name))
+        worst[name] = close_elementwise(sel(from_heads(got[name], B, S), r[name]), r[name],
+                                        att_u(dt, name, B, all_masked, regime) * r[name + "_terms"] + TINY, "%s %s" % (what, name))
     for b in range(B):                                     # the dk / dv rows of masked keys: the reference underflows to exact zero, so must the kernel
         if b in all_masked:
             continue
@@ -230,6 +282,7 @@ def check_attention(dt, qkv, dctx, masks, out, what, all_masked=(), regime="plai
             got = from_heads(dqkv[:, lo:lo + H], B, S)[b][:, dead]
             assert bool((got == 0).all()), "%s: %s rows of masked keys of sentence %d are not exact zeros" % (what, name, b)
     print(what, " ".join("%s %.3f" % kv for kv in worst.items()))
+    return worst
 
 
 BOOST_KEYS = 16
@@ -247,6 +300,163 @@ def boost_amplitude(S, dt, k0):
             return a
         a -= 0.25
     raise AssertionError("no amplitude leaves probability outside the block")
+
+
+# ------------------------------------------------------------------------------------------------ attention under dropout
+DROP = {name: (seed, thresh) for name, seed, thresh in DROP_EDGES}
+ATT_DROP_S = ATT_S + [64, 61]               # + one tile with S % 4 == 0 below 128 (the quad exchange of dK / dV) and S % 4 != 0 below 64
+ATT_DROP_ALL_EDGES_S = (64, 256)            # one-tile and tiled, both S % 4 == 0: every edge of DROP_EDGES
+
+
+def att_dropout_edges(S):
+    return [e[0] for e in DROP_EDGES] if S in ATT_DROP_ALL_EDGES_S else ["p0.1"]
+
+
+@functools.lru_cache(maxsize=None)
+def att_dropout_case(S, dt, edge):
+    """(qkv, dctx, masks, keep, scale, float64 reference without rowdot) of att_case(S, dt, att_lengths(S)) under DROP_EDGES[edge].  Cached:
+    the tests share one reference per case and leave it unchanged."""
+    seed, thresh = DROP[edge]
+    qkv, dctx, masks = att_case(S, dt, att_lengths(S))
+    keep = att_keep(seed, thresh, masks.shape[0], ATT_NH, S)
+    return qkv, dctx, masks, keep, SCALE_P, att_reference(qkv, dctx, masks, keep=keep, scale=SCALE_P)
+
+
+# The mask read off the outputs (test_attention_mask_read_off): per 64-wide window j of the sequence two launches.
+#  "ctx dv": v[k] = e_(k - 64j) inside the window, 0 outside -> ctx[q, d] = pd(q, 64j + d): ctx != 0 is the forward kernel's mask of every
+#    live key of the window; dO[q] = e_(q - 64j) inside the window, 0 outside -> dv[k, d] = pd(64j + d, k): dv != 0 is the dK / dV
+#    kernel's mask of every query of the window (dv does not read v, so one launch carries both).
+#  "dq": k[key] = e_(key - 64j) inside the window, 0 outside -> dq[q, d] = ds(q, 64j + d) / 8, which is p (dP scale - D) / 8 for a kept
+#    pair and p (-D) / 8 for a dropped one: the pair is readable where the two lie further apart than twice the bar of that element.
+WINDOW = 64
+READOFF_S = (64, 61, 256, 301)
+READOFF_CAP = {"fp32": 0.01, "bf16": 0.10}  # the share of live pairs the dq read-off may leave unreadable
+# u of the dq read-off: U_FP32, and in bf16 4 x 1.2e-3.  The read-off launches are p = 0.1 launches, where the statement's worst dq
+# error / cond_terms is 8.3e-4 (ATT_MEASURED's 1.8e-3 comes from the "drop nearly all" edge alone): a kernel inside 4.8e-3 of an
+# element's terms lies nearer to the right side of every readable pair, and the reference leaves 0.2 % / 7.5 % of the pairs unreadable.
+READOFF_U = {"fp32": U_FP32, "bf16": 4.8e-3}
+
+
+def readoff_windows(S):
+    return range((S + WINDOW - 1) // WINDOW)
+
+
+def readoff_case(kind, S, dt, j):
+    """att_case(S, dt, att_lengths(S)) with the unit-vector operands of read-off `kind` ("ctx dv" | "dq") for window j"""
+    qkv, dctx, masks = att_case(S, dt, att_lengths(S), seed=7)
+    B, H = masks.shape[0], ATT_NH * HD
+    qkv, dctx = qkv.clone().reshape(B, S, 3 * H), dctx.clone().reshape(B, S, H)
+    unit = torch.zeros((S, HD))
+    w = torch.arange(WINDOW * j, min(S, WINDOW * (j + 1)))
+    unit[w, w - WINDOW * j] = 1.0
+    unit = unit.repeat(1, ATT_NH).to(qkv.dtype)                    # [S, H]: the same window in every head
+    if kind == "ctx dv":
+        qkv[:, :, 2 * H:] = unit
+        dctx[:] = unit
+    else:
+        qkv[:, :, H:2 * H] = unit
+    return qkv.reshape(B * S, 3 * H), dctx.reshape(B * S, H), masks
+
+
+def read_off_masks(S, dt, edge, run, what):
+    """The three read-offs of the kernels' dropout mask under DROP_EDGES[edge], window by window.  run(qkv, dctx, masks, seed, thresh,
+    scale) -> (ctx, lse, rowdot, dqkv) is the GPU launch (tests/test_row_edges_gpu.py) or the statement (tests/test_compare_helpers_cpu.py).
+    Asserts, in this order: from the reference alone, that the dq read-off leaves no more than READOFF_CAP of the live pairs unreadable;
+    that the forward's and the dK / dV kernel's masks equal att_keep on every live (query, key) and are empty on masked keys; that the
+    dQ kernel's value lies on the side att_keep names on every readable pair; that the three agree wherever all are readable."""
+    seed, thresh = DROP[edge]
+    lengths = att_lengths(S)
+    B, nh, H = len(lengths), ATT_NH, ATT_NH * HD
+    keep = att_keep(seed, thresh, B, nh, S)
+    u = READOFF_U[dt]
+    live = None
+    sides, readable = {}, torch.zeros((B, nh, S, S), dtype=torch.bool)
+    for j in readoff_windows(S):
+        lo, hi = WINDOW * j, min(S, WINDOW * (j + 1))
+        qkv, dctx, masks = readoff_case("dq", S, dt, j)
+        live = (masks == 1)[:, None, None, :].expand(B, nh, S, S)
+        sides[j] = readoff_dq_sides(att_reference(qkv, dctx, masks, keep=keep, scale=SCALE_P), j, S, u, SCALE_P)
+        readable[..., lo:hi] = sides[j][2]
+    unreadable = 1.0 - float(readable[live].float().mean())
+    print("%s: the dq read-off leaves %.2f %% of the live pairs unreadable (cap %.0f %%)" % (what, 100 * unreadable, 100 * READOFF_CAP[dt]))
+    assert unreadable <= READOFF_CAP[dt], what
+    fwd, dkv, dqm = (torch.zeros((B, nh, S, S), dtype=torch.bool) for _ in range(3))
+    for j in readoff_windows(S):
+        lo, hi = WINDOW * j, min(S, WINDOW * (j + 1))
+        qkv, dctx, masks = readoff_case("ctx dv", S, dt, j)
+        ctx, _, _, dqkv = run(qkv, dctx, masks, seed, thresh, SCALE_P)
+        fwd[..., lo:hi] = from_heads(ctx, B, S)[..., :hi - lo] != 0
+        assert bool((from_heads(ctx, B, S)[..., hi - lo:] == 0).all()), what
+        dv = from_heads(dqkv[:, 2 * H:], B, S)                       # dv[key, d] = pd(query 64j + d, key)
+        dkv[:, :, lo:hi, :] = (dv[..., :hi - lo] != 0).transpose(-1, -2)
+        qkv, dctx, masks = readoff_case("dq", S, dt, j)
+        _, _, _, dqkv = run(qkv, dctx, masks, seed, thresh, SCALE_P)
+        got = from_heads(dqkv[:, :H], B, S).to(F64)[..., :hi - lo]
+        kept, dropped, _ = sides[j]
+        dqm[..., lo:hi] = (got - kept).abs() < (got - dropped).abs()
+    for name, m in (("forward", fwd), ("dK / dV", dkv)):
+        assert not bool(m[~live].any()), "%s: the %s kernel gives a masked key a non-zero probability" % (what, name)
+        bad = int((m[live] != keep[live]).sum())
+        assert bad == 0, "%s: the %s kernel's mask differs from att_keep in %d of %d live pairs" % (what, name, bad, int(live.sum()))
+    can = live & readable
+    bad = int((dqm[can] != keep[can]).sum())
+    assert bad == 0, "%s: the dQ kernel's mask differs from att_keep in %d of %d readable pairs" % (what, bad, int(can.sum()))
+    assert torch.equal(fwd[can], dkv[can]) and torch.equal(fwd[can], dqm[can]), what + ": the three read-offs disagree"
+    return keep, live, fwd, dkv, dqm, readable
+
+
+def readoff_dq_sides(ref, j, S, u, scale):
+    """For window j of the "dq" read-off, all [B, nh, S, w]: what the reference's dq element (q, d) = ds(q, 64j + d) / 8 is if the pair is
+    kept, what if it is dropped (ref: att_reference under the true mask - its D; dO V^T before the mask), and whether the pair is
+    readable: the two lie p |dO V^T| scale / 8 apart, more than twice the bar u x terms of that element."""
+    lo, hi = WINDOW * j, min(S, WINDOW * (j + 1))
+    p, D = ref["p"][..., lo:hi], ref["D"][..., None]
+    kept, dropped = p * (ref["dP_raw"][..., lo:hi] * float(np.float32(scale)) - D) / 8.0, p * (-D) / 8.0
+    readable = (kept - dropped).abs() > 2.0 * u * ref["dq_terms"][..., :hi - lo]
+    return kept, dropped, readable
+
+
+# ------------------------------------------------------------------------------------------------ attention over live rows
+# (S, rlen per sentence, mask length per sentence): rows at or beyond rlen are padding; the mask is a prefix no longer than rlen, and one
+# sentence's ends 3 rows before its rlen - live rows that are masked keys (a loss position behind the mask end)
+LIVE_CASES = {128: ([128, 0, 1, 31, 32, 33, 97], [128, 0, 1, 31, 32, 33, 94]),
+              301: ([301, 0, 1, 127, 128, 129, 160], [301, 0, 1, 127, 128, 129, 157])}
+
+
+# ------------------------------------------------------------------------------------------------ row_liveness
+LIVENESS_SHAPES = [(2, 96), (17, 64), (1, 64), (4, 512), (40, 512)]     # a partial second 64-lane chunk | more sentences than waves | nothing
+#                                                                         flagged | 2048 rows: a second round of the 1024-thread scan for the
+#                                                                         row list | 1280 blocks of 16: the same for tiles16
+
+
+def liveness_case(B, S, with_loss):
+    """masks, loss_masks (None without) [B, S] int64: mask prefixes of every kind of length - 0, 1, S, around the 16 / 32 / 64 edges -, and
+    with loss_masks a loss position behind the mask end in every third sentence (and one in a sentence without a mask at all)"""
+    if (B, S) == (1, 64):
+        return torch.zeros((B, S), dtype=torch.int64), (torch.zeros((B, S), dtype=torch.int64) if with_loss else None)
+    g = np.random.default_rng(100 * B + S)
+    edges = [0, 1, S, 15, 16, 17, 31, 32, 33, 63, 64, 65, S - 1, S // 2]
+    masks = torch.zeros((B, S), dtype=torch.int64)
+    loss = torch.zeros((B, S), dtype=torch.int64)
+    for b in range(B):
+        n = min(S, edges[b] if b < len(edges) else int(g.integers(0, S + 1)))
+        masks[b, :n] = 1
+        loss[b, 1:max(1, n - 1)] = torch.from_numpy(g.integers(0, 2, max(0, n - 2)))
+        if b % 3 == 0 and n + 5 < S:
+            loss[b, n + 5] = 1
+    return masks, (loss if with_loss else None)
+
+
+def liveness_reference(masks, loss_masks):
+    """plain numpy: row_live [B*S] uint8, rlen [B], the ascending live 64- / 32- / 16-row block lists and the live rows, n_tiles [4]"""
+    m = masks.numpy() == 1
+    if loss_masks is not None:
+        m = m | (loss_masks.numpy() == 1)
+    B, S = m.shape
+    rlen = np.array([(np.flatnonzero(row)[-1] + 1) if row.any() else 0 for row in m], dtype=np.int32)
+    row_live = (np.arange(S)[None, :] < rlen[:, None]).reshape(-1).astype(np.uint8)
+    lists = [np.flatnonzero(row_live.reshape(-1, bp).any(-1)).astype(np.int32) for bp in (64, 32, 16, 1)]
+    return {"row_live": row_live, "rlen": rlen, "lists": lists, "n_tiles": np.array([len(x) for x in lists], dtype=np.int32)}
 
 
 # ================================================================================================ LayerNorm family

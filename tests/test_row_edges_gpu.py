@@ -5,20 +5,25 @@ kernels span orders of magnitude, so here every element is compared with a float
 u * cond_terms + 1e-30 (tests/helpers.py close_elementwise; DESIGN section 3, "Element-wise bars of the row kernels"): cond_terms is the
 sum of the absolute values of the terms the reference adds to produce the element, u = 1e-4 for an fp32 output (of either mode) and 2^-8
 for an output stored in bf16.  bf16 inputs are rounded first and shared with the reference.  Every output buffer is `guarded`.
+Attention is also pinned in the form a training step launches: under dropout (the mask att_keep, held element-wise and read off the
+outputs of each kernel bit by bit), with the live-row table rlen and NaN in every padding row, with padded pitches, and through
+row_liveness, which writes that table.
 
 The case builders, the float64 references and the checks are plain CPU code in tests/row_cases.py: tests/test_compare_helpers_cpu.py
 runs them without a GPU.
 """
 import ctypes as C
 
+import numpy as np
 import pytest
 import torch
 
 from realise_amd import _capi
 from helpers import close_elementwise, guarded
-from row_cases import (ATT_NH, ATT_S, BOOST_KEYS, CE_ROWS, CE_V, HD, LN_EPS, LN_H, LN_ROWS, att_case, att_lengths, boost_amplitude,
-                       ce_case, ce_reference, check_attention, check_ce, gen, ln_bwd_reference, ln_fwd_reference, ln_gelu_case, ln_input,
-                       ln_params, rounded)
+from row_cases import (ATT_DROP_S, ATT_NH, ATT_S, BOOST_KEYS, CE_ROWS, CE_V, DROP, HD, LIVE_CASES, LIVENESS_SHAPES, LN_EPS, LN_H, LN_ROWS,
+                       READOFF_S, SCALE_P, att_case, att_dropout_case, att_dropout_edges, att_keep, att_lengths, boost_amplitude, ce_case,
+                       ce_reference, check_attention, check_ce, gen, liveness_case, liveness_reference, ln_bwd_reference,
+                       ln_fwd_reference, ln_gelu_case, ln_input, ln_params, read_off_masks, rounded)
 
 pytestmark = pytest.mark.gpu
 
@@ -104,25 +109,78 @@ def test_masked_ce_empty_selection(dt, V):
 
 
 # ================================================================================================ attention
-def run_attention(lib, dt, qkv, dctx, masks):
-    """forward and backward through the C ABI; returns CPU tensors ctx [B*S, H], lse, rowdot [B, nh, S], dqkv [B*S, 3H]"""
+NAN = float("nan")
+
+
+def bits(t):
+    return t.contiguous().view({2: torch.int16, 4: torch.int32}[t.element_size()])
+
+
+def run_attention(lib, dt, qkv, dctx, masks, drop=(0, 0, 1.0), rlen=None, pitched=False, poison=None, raw=False):
+    """forward and backward through the C ABI; returns CPU tensors ctx [B*S, H], lse, rowdot [B, nh, S], dqkv [B*S, 3H].  Every output
+    buffer is guarded and prefilled with NaN.
+    drop = (seed, thresh, scale).  rlen (list of B ints): the _rows entry points with that live-row table; None: the plain ones.
+    pitched: q, k, v in three buffers of pitch H + VEC, ctx / dctx of pitch H + VEC, dq / dk / dv in three buffers of pitch H + 4, the
+    input padding columns NaN (the padding columns of the outputs are returned with raw = True).
+    poison (bool [B, S]): between the two calls those rows of the ctx and lse the backward is given are overwritten with NaN (what is
+    returned is the forward's own output).  raw: also returns the dict of the padded output buffers as the kernels left them."""
     code, tdt = DT[dt]
     B, S = masks.shape
     nh, H = ATT_NH, ATT_NH * HD
-    qd, dd = qkv.cuda(), dctx.cuda()
-    esz = qd.element_size()
+    vec = 16 // torch.empty((), dtype=tdt).element_size()
+    esz = 16 // vec
+    seed, thresh, scale = drop
     madd = ((1.0 - masks.float()) * -10000.0).cuda()
-    ctx, chk_ctx = guarded((B * S, H), tdt, float("nan"))
-    lse, chk_lse = guarded((B, nh, S), torch.float32, float("nan"))
-    rowdot, chk_rd = guarded((B, nh, S), torch.float32, float("nan"))
-    dqkv, chk_dqkv = guarded((B * S, 3 * H), tdt, float("nan"))
-    _capi.check(lib.realise_attention_fwd(stream(), code, P(qd), P(qd, H * esz), P(qd, 2 * H * esz), 3 * H, P(madd), P(ctx), H, P(lse),
-                                          B, nh, S, 0, 0, 1.0), "attention fwd")
-    _capi.check(lib.realise_attention_bwd(stream(), code, P(qd), P(qd, H * esz), P(qd, 2 * H * esz), 3 * H, P(madd), P(ctx), P(dd), H, P(lse),
-                                          P(rowdot), P(dqkv), P(dqkv, H * esz), P(dqkv, 2 * H * esz), 3 * H, B, nh, S, 0, 0, 1.0), "attention bwd")
+    rl = None if rlen is None else torch.tensor(rlen, dtype=torch.int32).cuda()
+    if pitched:
+        ldq, ldc, ldd = H + vec, H + vec, H + 4
+        ins = []
+        for t in (qkv[:, :H], qkv[:, H:2 * H], qkv[:, 2 * H:], dctx):
+            buf = torch.full((B * S, H + vec), NAN, dtype=tdt)
+            buf[:, :H] = t
+            ins.append(buf.cuda())
+        qd, kd, vd, dd = ins
+        q_p, k_p, v_p = P(qd), P(kd), P(vd)
+        ctx, chk_ctx = guarded((B * S, ldc), tdt, NAN)
+        grads = [guarded((B * S, ldd), tdt, NAN) for _ in range(3)]
+        dq_p, dk_p, dv_p = (P(g[0]) for g in grads)
+    else:
+        ldq, ldc, ldd = 3 * H, H, 3 * H
+        qd, dd = qkv.cuda(), dctx.cuda()
+        q_p, k_p, v_p = P(qd), P(qd, H * esz), P(qd, 2 * H * esz)
+        ctx, chk_ctx = guarded((B * S, H), tdt, NAN)
+        dqkv, chk_dqkv = guarded((B * S, 3 * H), tdt, NAN)
+        grads = [(dqkv, chk_dqkv)]
+        dq_p, dk_p, dv_p = P(dqkv), P(dqkv, H * esz), P(dqkv, 2 * H * esz)
+    lse, chk_lse = guarded((B, nh, S), torch.float32, NAN)
+    rowdot, chk_rd = guarded((B, nh, S), torch.float32, NAN)
+    if rl is None:
+        _capi.check(lib.realise_attention_fwd(stream(), code, q_p, k_p, v_p, ldq, P(madd), P(ctx), ldc, P(lse), B, nh, S, seed, thresh, scale),
+                    "attention fwd")
+    else:
+        _capi.check(lib.realise_attention_fwd_rows(stream(), code, q_p, k_p, v_p, ldq, P(madd), P(ctx), ldc, P(lse), B, nh, S, seed, thresh, scale,
+                                                   P(rl)), "attention fwd rows")
     torch.cuda.synchronize()
-    chk_ctx("attention ctx"); chk_lse("attention lse"); chk_rd("attention rowdot"); chk_dqkv("attention dqkv")
-    return ctx.cpu(), lse.cpu(), rowdot.cpu(), dqkv.cpu()
+    ctx_fwd, lse_fwd = ctx.cpu(), lse.cpu()
+    if poison is not None:
+        rows = poison.reshape(-1).cuda()
+        ctx[rows] = NAN
+        lse.copy_(torch.where(poison.cuda()[:, None, :].expand(B, nh, S), torch.full_like(lse, NAN), lse))
+    if rl is None:
+        _capi.check(lib.realise_attention_bwd(stream(), code, q_p, k_p, v_p, ldq, P(madd), P(ctx), P(dd), ldc, P(lse), P(rowdot), dq_p, dk_p, dv_p,
+                                              ldd, B, nh, S, seed, thresh, scale), "attention bwd")
+    else:
+        _capi.check(lib.realise_attention_bwd_rows(stream(), code, q_p, k_p, v_p, ldq, P(madd), P(ctx), P(dd), ldc, P(lse), P(rowdot), dq_p, dk_p,
+                                                   dv_p, ldd, B, nh, S, seed, thresh, scale, P(rl)), "attention bwd rows")
+    torch.cuda.synchronize()
+    chk_ctx("attention ctx"); chk_lse("attention lse"); chk_rd("attention rowdot")
+    for g, chk in grads:
+        chk("attention dq / dk / dv")
+    dq_all = torch.cat([g.cpu()[:, :H] for g, _ in grads], 1) if pitched else grads[0][0].cpu()
+    out = (ctx_fwd[:, :H].contiguous(), lse_fwd, rowdot.cpu(), dq_all)
+    if raw:
+        return out, {"ctx": ctx_fwd, "grads": [g.cpu() for g, _ in grads]}
+    return out
 
 
 @pytest.mark.parametrize("dt", ["fp32", "bf16"])
@@ -159,6 +217,204 @@ def test_attention_running_maximum(dt, S, where):
     qkv, dctx, masks = att_case(S, dt, [S, S, S - 5], boost=(a, k0, BOOST_KEYS))
     check_attention(dt, qkv, dctx, masks, run_attention(lib, dt, qkv, dctx, masks), "attention %s S=%d block %s a=%.2f" % (dt, S, where, a),
                     regime="boosted")
+
+
+# ------------------------------------------------------------------------------------------------ attention as a training step runs it
+@pytest.mark.parametrize("dt", ["fp32", "bf16"])
+@pytest.mark.parametrize("S", ATT_DROP_S)
+def test_attention_dropout_rows(dt, S):
+    """ctx, lse, rowdot, dq, dk, dv under dropout, element-wise against the float64 reference with the mask att_keep: p = 0.1 at every S;
+    at S = 64 and 256 also the top 16 bits of thresh zero (nothing dropped, the scale still applies), nearly everything dropped, and a
+    second seed.  The dk / dv rows of masked keys stay exact zeros (check_attention)."""
+    lib = _capi.load()
+    for edge in att_dropout_edges(S):
+        qkv, dctx, masks, keep, scale, ref = att_dropout_case(S, dt, edge)
+        seed, thresh = DROP[edge]
+        out = run_attention(lib, dt, qkv, dctx, masks, drop=(seed, thresh, scale))
+        check_attention(dt, qkv, dctx, masks, out, "attention %s S=%d dropout %s" % (dt, S, edge), regime="dropout", ref=ref)
+
+
+@pytest.mark.parametrize("dt", ["fp32", "bf16"])
+@pytest.mark.parametrize("S,edge", [(S, "p0.1") for S in READOFF_S] + [(64, "second seed"), (256, "second seed")])
+def test_attention_mask_read_off(dt, S, edge):
+    """the dropout mask of each of the three kernels (forward, dK / dV with its quad exchange, dQ) read off the outputs bit by bit, per
+    64-wide window, and compared with att_keep (tests/row_cases.py read_off_masks)"""
+    lib = _capi.load()
+
+    def run(qkv, dctx, masks, seed, thresh, scale):
+        return run_attention(lib, dt, qkv, dctx, masks, drop=(seed, thresh, scale))
+    read_off_masks(S, dt, edge, run, "attention %s S=%d %s" % (dt, S, edge))
+
+
+@pytest.mark.parametrize("dt", ["fp32", "bf16"])
+@pytest.mark.parametrize("S", sorted(LIVE_CASES))
+def test_attention_live_rows(dt, S):
+    """realise_attention_fwd_rows / _bwd_rows with dropout on and every row at or beyond rlen[b] NaN in q, k, v, dctx and - for the
+    backward - in the ctx and lse it is given.  Forward: rows < rlen of ctx / lse equal the plain call on the same input with those rows
+    zero-filled bit for bit and are within the bars of test_attention_dropout_rows; the 32-query blocks that start at or beyond rlen keep
+    their prefill.  Backward: dq / dk / dv rows >= rlen are exact zeros in every head, rows < rlen equal the plain call's bit for bit and
+    are within the bars of the reference with zero dctx there, rowdot is held on the rows < rlen."""
+    lib = _capi.load()
+    rlen, mlen = LIVE_CASES[S]
+    B, H = len(rlen), ATT_NH * HD
+    seed, thresh = DROP["p0.1"]
+    drop = (seed, thresh, SCALE_P)
+    qkv, dctx, masks = att_case(S, dt, mlen, seed=11)
+    live = torch.arange(S)[None, :] < torch.tensor(rlen)[:, None]                # [B, S]
+    assert bool((masks.bool() & ~live).sum() == 0) and int((live & ~masks.bool()).sum()) == 3
+    lr = live.reshape(-1, 1)
+    zeroed = (torch.where(lr, qkv, torch.zeros_like(qkv)), torch.where(lr, dctx, torch.zeros_like(dctx)))
+    poisoned = (torch.where(lr, qkv, torch.full_like(qkv, NAN)), torch.where(lr, dctx, torch.full_like(dctx, NAN)))
+    what = "attention %s S=%d live rows" % (dt, S)
+    plain = run_attention(lib, dt, zeroed[0], zeroed[1], masks, drop=drop)
+    out = run_attention(lib, dt, poisoned[0], poisoned[1], masks, drop=drop, rlen=rlen, poison=~live)
+    ctx, lse, rowdot, dqkv = out
+    # forward
+    assert torch.equal(bits(ctx[lr[:, 0]]), bits(plain[0][lr[:, 0]])), what + ": ctx rows < rlen differ from the plain call"
+    lsel = live[:, None, :].expand(B, ATT_NH, S)
+    assert torch.equal(bits(lse[lsel]), bits(plain[1][lsel])), what + ": lse rows < rlen differ from the plain call"
+    skipped = torch.arange(S)[None, :] // 32 * 32 >= torch.tensor(rlen)[:, None]    # rows of 32-query blocks that start at or beyond rlen
+    assert int(skipped.sum()) > 0
+    fill_c, fill_l = bits(torch.full((1,), NAN, dtype=ctx.dtype)), bits(torch.full((1,), NAN))
+    assert bool((bits(ctx[skipped.reshape(-1)]) == fill_c).all()), what + ": ctx rows of a query block beyond rlen were written"
+    assert bool((bits(lse[skipped[:, None, :].expand(B, ATT_NH, S)]) == fill_l).all()), what + ": lse rows of a query block beyond rlen were written"
+    # backward
+    dead = ~lr[:, 0]
+    for name, lo in (("dq", 0), ("dk", H), ("dv", 2 * H)):
+        g = dqkv[:, lo:lo + H]
+        bad = g[dead] != 0                                                        # (NaN != 0 is True: a NaN row is reported too)
+        assert not bool(bad.any()), "%s: %d %s rows at or beyond rlen are not exact zeros" % (what, int(bad.any(-1).sum()), name)
+        assert torch.equal(bits(g[~dead]), bits(plain[3][:, lo:lo + H][~dead])), "%s: %s rows < rlen differ from the plain call" % (what, name)
+    keep = att_keep(seed, thresh, B, ATT_NH, S)
+    empty = tuple(b for b in range(B) if mlen[b] == 0)
+    check_attention(dt, zeroed[0], zeroed[1], masks, out, what, all_masked=empty, regime="dropout", keep=keep, scale=SCALE_P, live=live)
+
+
+@pytest.mark.parametrize("dt", ["fp32", "bf16"])
+@pytest.mark.parametrize("S", [97, 301])
+def test_attention_pitches(dt, S):
+    """q, k, v in three separate buffers with ldq = H + VEC, ctx / dctx with ldc = H + VEC, dq / dk / dv with ldd = H + 4, dropout on: the
+    input padding columns hold NaN, the output padding columns keep their prefill bits, every result equals the packed launch bit for bit"""
+    lib = _capi.load()
+    seed, thresh = DROP["p0.1"]
+    qkv, dctx, masks = att_case(S, dt, att_lengths(S))
+    H = ATT_NH * HD
+    packed = run_attention(lib, dt, qkv, dctx, masks, drop=(seed, thresh, SCALE_P))
+    pitched, rawbuf = run_attention(lib, dt, qkv, dctx, masks, drop=(seed, thresh, SCALE_P), pitched=True, raw=True)
+    for name, a, b in zip(("ctx", "lse", "rowdot", "dq | dk | dv"), pitched, packed):
+        assert bool(torch.isfinite(a.float()).all()), name
+        assert torch.equal(bits(a), bits(b)), "attention %s S=%d: %s of the pitched launch differs from the packed launch" % (dt, S, name)
+    fill = bits(torch.full((1,), NAN, dtype=packed[0].dtype))
+    for name, buf in [("ctx", rawbuf["ctx"])] + list(zip(("dq", "dk", "dv"), rawbuf["grads"])):
+        assert buf.shape[1] > H and bool((bits(buf[:, H:]) == fill).all()), "attention %s S=%d: padding columns of %s were written" % (dt, S, name)
+
+
+@pytest.mark.parametrize("dt", ["fp32", "bf16"])
+def test_attention_refusals_write_nothing(dt):
+    """S = 0, ldq / ldc off a multiple of VEC, ldd % 4 != 0, B * nh * S * S = 2^32 (B = 65536, nh = 1, S = 256): REALISE_ERR_ARG from both
+    entry points and both their _rows forms before anything is launched - every output bit unchanged (small buffers do)"""
+    lib = _capi.load()
+    code, tdt = DT[dt]
+    nh, H, S, B = ATT_NH, ATT_NH * HD, 16, 1
+    vec = 16 // torch.empty((), dtype=tdt).element_size()
+    ins = torch.zeros((B * S, 3 * H + 8), dtype=tdt).cuda()
+    dd = torch.zeros((B * S, H + 8), dtype=tdt).cuda()
+    madd = torch.zeros((B, S)).cuda()
+    rl = torch.tensor([S], dtype=torch.int32).cuda()
+    esz = ins.element_size()
+    # (B, nh, S, ldq, ldc, ldd, forward refuses too)
+    cases = {"S = 0": (B, nh, 0, 3 * H, H, 3 * H, True), "ldq % VEC": (B, nh, S, 3 * H + vec // 2, H, 3 * H, True),
+             "ldc % VEC": (B, nh, S, 3 * H, H + vec // 2, 3 * H, True), "ldd % 4": (B, nh, S, 3 * H, H, 3 * H + 2, False),
+             "B nh S S = 2^32": (65536, 1, 256, 3 * H, H, 3 * H, True)}
+    for name, (b_, nh_, s_, ldq, ldc, ldd, fwd_too) in cases.items():
+        for rows in (False, True):
+            outs = {"ctx": guarded((B * S, H + 8), tdt, 3.0), "lse": guarded((B, nh, S), torch.float32, 3.0),
+                    "rowdot": guarded((B, nh, S), torch.float32, 3.0), "dqkv": guarded((B * S, 3 * H + 8), tdt, 3.0)}
+            ctx, lse, rowdot, dqkv = (outs[k][0] for k in ("ctx", "lse", "rowdot", "dqkv"))
+            tail = (P(rl),) if rows else ()
+            fwd = lib.realise_attention_fwd_rows if rows else lib.realise_attention_fwd
+            bwd = lib.realise_attention_bwd_rows if rows else lib.realise_attention_bwd
+            if fwd_too:
+                rc = fwd(stream(), code, P(ins), P(ins, H * esz), P(ins, 2 * H * esz), ldq, P(madd), P(ctx), ldc, P(lse), b_, nh_, s_,
+                         DROP["p0.1"][0], DROP["p0.1"][1], SCALE_P, *tail)
+                assert rc == ERR_ARG, (name, rows, rc)
+            rc = bwd(stream(), code, P(ins), P(ins, H * esz), P(ins, 2 * H * esz), ldq, P(madd), P(ctx), P(dd), ldc, P(lse), P(rowdot),
+                     P(dqkv), P(dqkv, H * esz), P(dqkv, 2 * H * esz), ldd, b_, nh_, s_, DROP["p0.1"][0], DROP["p0.1"][1], SCALE_P, *tail)
+            assert rc == ERR_ARG, (name, rows, rc)
+            torch.cuda.synchronize()
+            for k, (t, chk) in outs.items():
+                chk(name + " " + k)
+                assert bool((t.float() == 3.0).all()), "%s: %s was written by a refused call" % (name, k)
+
+
+# ================================================================================================ row_liveness
+POISON_I32 = -23131
+
+
+def run_liveness(lib, masks, loss_masks, B, S, null=()):
+    """one realise_row_liveness call on guarded, prefilled buffers; `null`: names of the nullable outputs passed as NULL.  Returns
+    (return code, name -> CPU array)."""
+    T = B * S
+    # (row_live: T bytes of 77, allocated as T / 4 ints - guarded() takes no 8-bit type)
+    shapes = {"row_live": (T // 4, torch.int32, 0x4D4D4D4D), "tiles64": (max(1, T // 64), torch.int32, POISON_I32), "tiles32": (max(1, T // 32), torch.int32, POISON_I32),
+              "tiles16": (max(1, T // 16), torch.int32, POISON_I32), "n_tiles": (4, torch.int32, POISON_I32), "rlen": (B, torch.int32, POISON_I32),
+              "rows": (T, torch.int32, POISON_I32)}
+    bufs = {k: guarded((n,), t, f) for k, (n, t, f) in shapes.items()}
+    md = None if masks is None else masks.cuda()
+    ld = None if loss_masks is None else loss_masks.cuda()
+    ptr = {k: (None if k in null else P(v[0])) for k, v in bufs.items()}
+    rc = lib.realise_row_liveness(stream(), P(md), P(ld), B, S, ptr["row_live"], ptr["tiles64"], ptr["tiles32"], ptr["tiles16"], ptr["n_tiles"],
+                                  ptr["rlen"], ptr["rows"])
+    torch.cuda.synchronize()
+    for k, (t, chk) in bufs.items():
+        chk("row_liveness " + k)
+    got = {k: v[0].cpu().numpy() for k, v in bufs.items()}
+    got["row_live"] = got["row_live"].view(np.uint8)
+    return rc, got
+
+
+@pytest.mark.parametrize("with_loss", [False, True])
+@pytest.mark.parametrize("B,S", LIVENESS_SHAPES)
+def test_row_liveness(B, S, with_loss):
+    """row_live, rlen, the live 64- / 32- / 16-row block lists, the live-row list and the four counts against plain numpy, exactly; every
+    entry behind a count keeps its prefill; with some of the nullable outputs NULL the others are unchanged and the count of a NULL list
+    is not written"""
+    lib = _capi.load()
+    masks, loss = liveness_case(B, S, with_loss)
+    ref = liveness_reference(masks, loss)
+    rc, got = run_liveness(lib, masks, loss, B, S)
+    assert rc == 0
+    names = ("tiles64", "tiles32", "tiles16", "rows")
+
+    def held(got, null=()):
+        assert np.array_equal(got["row_live"], ref["row_live"]), "row_live"
+        assert bool((got["rlen"] == POISON_I32).all()) if "rlen" in null else np.array_equal(got["rlen"], ref["rlen"]), "rlen"
+        for k, name in enumerate(names):
+            n = int(ref["n_tiles"][k])
+            if name in null:
+                assert got["n_tiles"][k] == POISON_I32 and bool((got[name] == POISON_I32).all()), name
+                continue
+            assert got["n_tiles"][k] == n, (name, got["n_tiles"][k], n)
+            assert np.array_equal(got[name][:n], ref["lists"][k]), name
+            assert bool((got[name][n:] == POISON_I32).all()), name + ": an entry behind the count was written"
+    held(got)
+    print("row_liveness B=%d S=%d loss_masks=%s: rlen %s counts %s" % (B, S, with_loss, ref["rlen"].tolist()[:8], ref["n_tiles"].tolist()))
+    for null in (("tiles32", "rows", "rlen"), ("tiles64", "tiles16")):
+        rc, got = run_liveness(lib, masks, loss, B, S, null=null)
+        assert rc == 0
+        held(got, null)
+
+
+def test_row_liveness_refusals_write_nothing():
+    """B * S % 64 != 0 and masks == NULL: REALISE_ERR_ARG, every output keeps its prefill"""
+    lib = _capi.load()
+    for B, S, with_masks in ((1, 96, True), (3, 40, True), (2, 64, False)):
+        masks = torch.ones((B, S), dtype=torch.int64) if with_masks else None
+        rc, got = run_liveness(lib, masks, torch.ones((B, S), dtype=torch.int64), B, S)
+        assert rc == ERR_ARG, (B, S, with_masks, rc)
+        assert bool((got["row_live"] == 77).all())
+        for k in ("tiles64", "tiles32", "tiles16", "n_tiles", "rlen", "rows"):
+            assert bool((got[k] == POISON_I32).all()), k
 
 
 # ================================================================================================ LayerNorm family
