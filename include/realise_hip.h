@@ -288,6 +288,28 @@ int realise_layernorm_fwd_chw4(void* stream, int dtype, const void* x, const int
 int realise_gather_rows_chw4(void* stream, int dtype, const void* x, const int32_t* inv, int T, int H, void* out);
 int realise_segment_sum_chw4(void* stream, int dtype, const void* x, const int32_t* inv, int T, int H, float* acc, void* out, const int32_t* nuniq_dev);
 
+/* Token rows (evaluation; no reference counterpart: pho_gru's last hidden state, models.py:818-826, and
+ * resnet_layernorm(resnet(glyph[id])), models.py:829-838 on BatchNorm's running statistics, depend on nothing but the token id, so a
+ * table [V, H] of each, in the storage of `dtype`, replaces the computation).  At most two row-kernel launches:
+ *   pho_table != NULL:  x[t] = float(pho_table[ids[t]]) + pos[t % S] + type0,  pho_out[t] = LayerNorm(x[t]) * gamma + beta
+ *                       - BertEmbeddings of pho_model on inputs_embeds (modeling_bert.py:183-193) with the GRU rows read by id.  Statistics
+ *                       and arithmetic order are those of the embedding LayerNorm over rows given directly: the same bits.
+ *   res_table != NULL:  res_out[t] = res_table[ids[t]]   (a copy)
+ * ids [T] int64, each in [0, rows of the tables): NOT checked here (the engine passes its range-checked copy).  Both tables have the row
+ * pitch ld, the outputs their own; every access is 16 bytes, so table and output rows are 16-byte aligned.
+ * Accepts dtypes 0 and 1.  Refused with the argument error before anything is launched: H % 8 != 0, H < 8 or H > 1024; ld below H or
+ * no multiple of 8; an output pitch below H or no multiple of 8; T <= 0 or S <= 0; both tables NULL; a table without its output; NULL ids;
+ * a pho_table without pos / type0 / gamma / beta. */
+typedef struct {
+  const int64_t* ids;
+  int32_t T, S, H;
+  const void* pho_table; const void* res_table; int64_t ld;
+  const float* pos; const float* type0; const float* gamma; const float* beta; float eps;
+  void* pho_out; int64_t ld_pho_out;
+  void* res_out; int64_t ld_res_out;
+} realise_token_rows_args;
+int realise_token_rows(void* stream, int dtype, const realise_token_rows_args* a);
+
 /* Eval decode: ids[row] = argmax over the V logits of the row, first maximum wins - replaces
  * `logits.detach().cpu().numpy()` + `np.argmax(preds, axis=-1)` (src/run.py:262-263): only the ids cross PCIe. */
 int realise_argmax(void* stream, int dtype, const void* logits, int64_t ld, int rows, int V, int64_t* ids);
@@ -472,6 +494,27 @@ typedef struct {
 int realise_build_pho(void* stream, const int64_t* src_idx, int T, const int64_t* table, const int32_t* vlens, int V, int Tw,
                       int64_t* pho_idx, int32_t* perm, int32_t* lens_sorted, int32_t* n_alive_dev);
 int realise_engine_forward(realise_engine* e, void* stream, const realise_batch* batch);
+/* Token tables (evaluation / serving): the two branches of an evaluation forward that see no context, read by token id.
+ *   pho[id] = the row pho_gru hands to pho_model (tap "pho_gru"),  res[id] = the row the fusion reads (tap "res_h": after
+ *   resnet_layernorm, in the reference's feature order for both glyph encoders)
+ * each [rows = vocab][ld] in the engine's storage dtype (bf16, or fp32 for REALISE_F32 / REALISE_F32_BF16X3), caller-owned, 16-byte
+ * aligned, ld >= hidden and a multiple of 8.  A model has a table per side branch it has (the other pointer is NULL).
+ * realise_engine_fill_token_tables runs the engine's own pinyin GRU, glyph tower and resnet_layernorm - in evaluation form, at the plan
+ * of the batch's (B, S, Tp), nothing else - on the batch's src_idx / pho_* and stores row t at index src_idx[t] (range-checked) of each
+ * table: a row is produced by the kernel instantiations a full forward of that shape runs.  The operand copies must be current
+ * (realise_engine_refresh_shadows).  It needs no masks, targets or outputs in the batch.
+ * realise_engine_set_token_tables installs the tables (the struct is copied; NULL switches them off, as realise_engine_set_decode):
+ * every realise_engine_forward with training == 0 then runs neither the GRU nor the tower - pho_model's embedding LayerNorm reads
+ * pho[src_idx] and res_h is a copy of res[src_idx] (realise_token_rows) - and accepts a batch without pho_idx / pho_perm /
+ * pho_lens_sorted / n_alive*; a forward with training != 0 returns the argument error.  The tables are valid for the parameters,
+ * buffers and glyph table they were filled from: the caller switches them off when any of those changes.  The taps "pho_gru",
+ * "resnet.block*" and "glyph.*" then hold what an earlier forward left.  Workspace and shadow sizes do not change.
+ * Refused (argument error; set: nothing is installed, what was installed stays): rows != vocab, ld < hidden or ld % 8 != 0, hidden % 8
+ * != 0, a table for a branch the model lacks, a missing table for a branch it has, model_type 5 (its input is tgt_idx and its
+ * evaluation is one short pass) and a model without a side branch. */
+typedef struct { void* pho; void* res; int64_t ld; int32_t rows; } realise_token_tables;
+int realise_engine_fill_token_tables(realise_engine* e, void* stream, const realise_batch* batch, const realise_token_tables* t);
+int realise_engine_set_token_tables(realise_engine* e, const realise_token_tables* t);
 /* gradients of the loss computed by the last training forward are ACCUMULATED into the grads arena.
  * Runs buckets [first_bucket, last_bucket] of the backward pass (see realise_bucket_bounds) so a
  * caller can overlap the all-reduce of finished buckets; pass 0, -1 for the whole pass. */

@@ -106,6 +106,19 @@ class Decode(C.Structure):
                 ("label_logit", C.c_void_p), ("scratch", C.c_void_p), ("scratch_bytes", C.c_int64)]
 
 
+class TokenRows(C.Structure):
+    """realise_token_rows_args (include/realise_hip.h)"""
+    _fields_ = [("ids", C.c_void_p), ("T", C.c_int32), ("S", C.c_int32), ("H", C.c_int32),
+                ("pho_table", C.c_void_p), ("res_table", C.c_void_p), ("ld", C.c_int64),
+                ("pos", C.c_void_p), ("type0", C.c_void_p), ("gamma", C.c_void_p), ("beta", C.c_void_p), ("eps", C.c_float),
+                ("pho_out", C.c_void_p), ("ld_pho_out", C.c_int64), ("res_out", C.c_void_p), ("ld_res_out", C.c_int64)]
+
+
+class TokenTables(C.Structure):
+    """realise_token_tables (include/realise_hip.h)"""
+    _fields_ = [("pho", C.c_void_p), ("res", C.c_void_p), ("ld", C.c_int64), ("rows", C.c_int32)]
+
+
 # every symbol include/realise_hip.h declares: name -> (restype, argtypes)
 _P, _I, _L, _F, _U = C.c_void_p, C.c_int, C.c_int64, C.c_float, C.c_uint32
 SYMBOLS = {
@@ -185,6 +198,9 @@ SYMBOLS = {
     "realise_gemm_nt_decode": (_I, [_P, _I, _P, _L, _P, _L, _I, _I, _I, _P, _P, C.POINTER(Decode)]),
     "realise_engine_set_decode": (None, [_P, C.POINTER(Decode)]),
     "realise_engine_set_pred": (None, [_P, C.POINTER(Pred)]),
+    "realise_token_rows": (_I, [_P, _I, C.POINTER(TokenRows)]),
+    "realise_engine_fill_token_tables": (_I, [_P, _P, C.POINTER(Batch), C.POINTER(TokenTables)]),
+    "realise_engine_set_token_tables": (_I, [_P, C.POINTER(TokenTables)]),
     "realise_masked_ce_pred": (_I, [_P, _I, _P, _L, _P, _P, _I, _I, _P, _P, _P, _P, _P]),
     "realise_build_pho": (_I, [_P, _P, _I, _P, _P, _I, _I, _P, _P, _P, _P]),
     "realise_layout_count": (_I, [C.POINTER(Config)]),

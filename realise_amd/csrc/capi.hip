@@ -69,6 +69,19 @@ LnFwdArgs<T> to_ln_fwd(const void* x, const float* gamma, const float* beta, flo
   a.y = (T*)y; a.xhat = (T*)xhat; a.rstd = rstd; a.row_live = row_live;
   return a;
 }
+// the two gathers of an evaluation forward with token tables: every refusal here, before the first launch
+template <typename T> int token_rows_launch(hipStream_t st, const realise_token_rows_args* a) {
+  if (a->pho_table) {
+    LnFwdArgs<T> ln;
+    ln.rows = a->T; ln.H = a->H; ln.S = a->S; ln.in_mode = 3; ln.x = (const T*)a->pho_table; ln.ld_in = a->ld; ln.ids = a->ids;
+    ln.pos = a->pos; ln.type0 = a->type0; ln.gamma = a->gamma; ln.beta = a->beta; ln.eps = a->eps;
+    ln.y = (T*)a->pho_out; ln.ldy = a->ld_pho_out;
+    const int rc = ln_fwd<T>(st, ln);
+    if (rc != RL_OK) return rc;
+  }
+  if (a->res_table) return token_copy<T>(st, (const T*)a->res_table, a->ld, a->ids, a->T, a->H, (T*)a->res_out, a->ld_res_out);
+  return RL_OK;
+}
 template <typename T>
 LnBwdArgs<T> to_ln_bwd(const void* dy, const void* xhat, const float* rstd, const float* gamma, void* dx, float* dgamma, float* dbeta, int rows, int H,
                        void* dx_drop = nullptr, DropParams out_drop = DropParams(), float* slots = nullptr, const uint8_t* row_live = nullptr) {
@@ -252,6 +265,13 @@ int realise_layernorm_fwd_live(void* stream, const void* x, const float* gamma, 
 int realise_layernorm_fwd(void* stream, int dtype, const void* x, const float* gamma, const float* beta, float eps, void* y,
                           void* xhat, float* rstd, int rows, int H) {
   RL_BY_DTYPE(0, ln_fwd<E>((hipStream_t)stream, to_ln_fwd<E>(x, gamma, beta, eps, y, xhat, rstd, rows, H)));
+}
+int realise_token_rows(void* stream, int dtype, const realise_token_rows_args* a) {
+  if (!a || !a->ids || a->T <= 0 || a->S <= 0 || a->H < 8 || (a->H & 7) || a->H > 1024 || a->ld < a->H || (a->ld & 7)) return RL_ERR_ARG;
+  if (!a->pho_table && !a->res_table) return RL_ERR_ARG;
+  if (a->pho_table && (!a->pho_out || a->ld_pho_out < a->H || (a->ld_pho_out & 7) || !a->pos || !a->type0 || !a->gamma || !a->beta)) return RL_ERR_ARG;
+  if (a->res_table && (!a->res_out || a->ld_res_out < a->H || (a->ld_res_out & 7))) return RL_ERR_ARG;
+  RL_BY_DTYPE(0, token_rows_launch<E>((hipStream_t)stream, a));
 }
 int realise_layernorm_bwd(void* stream, int dtype, const void* dy, const void* xhat, const float* rstd, const float* gamma,
                           void* dx, float* dgamma, float* dbeta, int rows, int H) {
@@ -569,6 +589,10 @@ void realise_engine_set_id_flag(realise_engine* e, int32_t* flag) { if (e) e->im
 void realise_engine_set_loss_grad(realise_engine* e, const float* grad_dev) { if (e) e->impl->set_loss_grad(grad_dev); }
 void realise_engine_set_decode(realise_engine* e, const realise_decode* d) { if (e) e->impl->set_decode(d); }
 void realise_engine_set_pred(realise_engine* e, const realise_pred* d) { if (e) e->impl->set_pred(d); }
+int realise_engine_set_token_tables(realise_engine* e, const realise_token_tables* t) { return e ? e->impl->set_token_tables(t) : RL_ERR_ARG; }
+int realise_engine_fill_token_tables(realise_engine* e, void* stream, const realise_batch* batch, const realise_token_tables* t) {
+  return (e && batch && t) ? e->impl->fill_token_tables((hipStream_t)stream, *batch, *t) : RL_ERR_ARG;
+}
 int realise_engine_forward(realise_engine* e, void* stream, const realise_batch* batch) {
   return (e && batch) ? e->impl->forward((hipStream_t)stream, *batch) : RL_ERR_ARG;
 }

@@ -41,6 +41,8 @@ struct EngineBase {
   virtual void set_loss_grad(const float* grad_dev) = 0;
   virtual void set_decode(const realise_decode* d) = 0;      // NULL clears; copied
   virtual void set_pred(const realise_pred* d) = 0;          // NULL clears; copied
+  virtual int set_token_tables(const realise_token_tables* t) = 0;      // NULL switches off; copied; refusals leave what was installed
+  virtual int fill_token_tables(hipStream_t st, const realise_batch& b, const realise_token_tables& t) = 0;
   virtual int forward(hipStream_t st, const realise_batch& b) = 0;
   virtual int backward(hipStream_t st, int first, int last) = 0;
   virtual int backward_signalled(hipStream_t st, void* const* bucket_events, int n_events) = 0;

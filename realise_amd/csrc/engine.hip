@@ -802,12 +802,13 @@ template <typename T> struct Engine : EngineBase {
 
   // ---------------------------------------------------------------- BERT stack
   int stack_forward(hipStream_t st, int sid, const StackOff& so, const std::vector<LayerSh>& shs, StackAct& a,
-                    const int64_t* ids, const T* embeds, int pos_zero, const T** out) {
+                    const int64_t* ids, const T* embeds, int pos_zero, const T** out, const T* tok_table = nullptr, int64_t tok_ld = 0) {
     const int B = pl.B, S = pl.S, Tk = B * S;
     {
       LnFwdArgs<T> ln;
       ln.rows = Tk; ln.H = H; ln.S = S;
       ln.in_mode = ids ? 1 : 2; ln.x = embeds; ln.ids = ids;
+      if (tok_table != nullptr) { ln.in_mode = 3; ln.x = tok_table; ln.ld_in = tok_ld; ln.ids = last.src_idx; }      // embeds read by token id (token tables)
       ln.word = so.word >= 0 ? pp(so.word) : nullptr;
       ln.pos = pp(so.pos); ln.type0 = pp(so.type); ln.pos_zero = pos_zero;
       ln.gamma = pp(so.ln_g); ln.beta = pp(so.ln_b); ln.eps = cfg.ln_eps;
@@ -1409,11 +1410,71 @@ template <typename T> struct Engine : EngineBase {
     have_fwd = b.training && b.want_dlogits;
     return RL_OK;
   }
+  // ---------------------------------------------------------------- token tables (evaluation: pho_gru and res_h rows by token id)
+  realise_token_tables tok = realise_token_tables();      // both pointers NULL: none installed
+  bool tok_on() const { return tok.pho != nullptr || tok.res != nullptr; }
+  // what a table set must be for this model; set and fill refuse the same things
+  bool tables_ok(const realise_token_tables& t) const {
+    if (!vr.arch || (!vr.pho && !vr.res)) return false;                       // no side branch (SpellBert, the bare ablation), Pho2Pretrain
+    if (t.rows != V || t.ld < H || (t.ld & 7) || (H & 7)) return false;
+    return (t.pho != nullptr) == vr.pho && (t.res != nullptr) == vr.res;
+  }
+  int set_token_tables(const realise_token_tables* t) override {
+    if (t == nullptr) { tok = realise_token_tables(); return RL_OK; }
+    if (!tables_ok(*t)) return RL_ERR_ARG;
+    tok = *t;
+    return RL_OK;
+  }
+  // the glyph branch of a forward up to the row the fusion reads: tower over the distinct glyphs, resnet_layernorm per token -> pl.res_h
+  int res_rows_forward(hipStream_t st) {
+    const T* res = nullptr;
+    RL_TRY(resnet_forward(st, last.src_idx, &res));
+    LnFwdArgs<T> ln; ln.rows = pl.B * pl.S; ln.H = H; ln.x = res; ln.row_index = wp<int>(pl.gu_inv);      // token t reads its glyph's row
+    ln.gamma = pp(L.res_ln_g); ln.beta = pp(L.res_ln_b); ln.eps = cfg.ln_eps;
+    ln.y = wp<T>(pl.res_h); ln.xhat = bwd_follows() ? wp<T>(pl.res_xhat) : nullptr; ln.rstd = wp<float>(pl.res_rstd);
+    // a 2x2 top (CharResNet1): the rows arrive [p][c], the LayerNorm stores them in the reference's c * 4 + p feature order
+    if (L.tower.top_pixels() == 4) return ln_fwd_chw4<T>(st, ln);
+    return ln_fwd<T>(st, ln);
+  }
+  // host / device counts of the GRU's live rows per step, from the batch (forward() and fill_token_tables())
+  void take_alive(const realise_batch& b, int Tp) {
+    last_alive.assign(Tp, 0);
+    if (vr.pho) for (int t = 0; t < Tp; ++t) last_alive[t] = b.n_alive ? b.n_alive[t] : b.B * b.S;
+    alive_dev = (vr.pho && !b.n_alive) ? b.n_alive_dev : nullptr;
+  }
+  int fill_token_tables(hipStream_t st, const realise_batch& b, const realise_token_tables& t) override {
+    if (!sh || !ws || !tables_ok(t) || !b.src_idx) return RL_ERR_ARG;
+    if (b.B < 1 || b.S < 1 || b.S > cfg.max_pos) return RL_ERR_ARG;
+    const int Tp = vr.pho ? b.Tp : 1;
+    if (vr.pho && (Tp < 1 || !b.pho_idx || !b.pho_perm || !b.pho_lens_sorted || (!b.n_alive && !b.n_alive_dev))) return RL_ERR_ARG;
+    have_fwd = false; hs = HeadSaved(); have_glyph_fwd = false;      // the branch activations of an earlier forward are about to be overwritten
+    if (pl.B != b.B || pl.S != b.S || pl.Tp != Tp) RL_TRY(install_plan(st, make_plan(b.B, b.S, Tp)));
+    last = realise_batch();
+    last.B = b.B; last.S = b.S; last.Tp = Tp; last.training = 0;
+    last.pho_perm = b.pho_perm; last.pho_lens_sorted = b.pho_lens_sorted;
+    dead_ok = false; rows_live = false;
+    RL_TRY(sync_optimizer(st));
+    RL_TRY(wait_shadows(st));
+    take_alive(b, Tp);
+    const int Tk = b.B * b.S;
+    RL_TRY(sanitize_ids(st, b.src_idx, Tk, V, wp<int64_t>(pl.ids_clean), id_flag));
+    last.src_idx = wp<int64_t>(pl.ids_clean);
+    if (vr.pho) {
+      RL_TRY(sanitize_ids(st, b.pho_idx, (int64_t)Tk * Tp, cfg.pho_vocab, wp<int64_t>(pl.pho_clean), id_flag));
+      last.pho_idx = wp<int64_t>(pl.pho_clean);
+      RL_TRY(gru_forward(st));
+    }
+    if (vr.res) RL_TRY(res_rows_forward(st));
+    return token_scatter<T>(st, last.src_idx, Tk, H, vr.pho ? wp<T>(pl.gru_out) : nullptr, (T*)t.pho, vr.res ? wp<T>(pl.res_h) : nullptr,
+                            (T*)t.res, t.ld);
+  }
   int forward(hipStream_t st, const realise_batch& b) override {
     if (!sh || !ws) return RL_ERR_ARG;
     if (b.B < 1 || b.S < 1 || b.S > cfg.max_pos) return RL_ERR_ARG;       // (S > 128: the tiled attention kernels, attention.hip)
-    const int Tp = vr.pho ? b.Tp : 1;
-    if (vr.pho && (Tp < 1 || !b.pho_idx || !b.pho_perm || !b.pho_lens_sorted || (!b.n_alive && !b.n_alive_dev))) return RL_ERR_ARG;
+    if (tok_on() && b.training) return RL_ERR_ARG;                         // the tables stand for evaluation-form branches only
+    const bool by_id = tok_on();                                           // neither the GRU nor the tower runs: the batch needs no pinyin
+    const int Tp = vr.pho ? (by_id && b.Tp < 1 ? 1 : b.Tp) : 1;
+    if (vr.pho && !by_id && (Tp < 1 || !b.pho_idx || !b.pho_perm || !b.pho_lens_sorted || (!b.n_alive && !b.n_alive_dev))) return RL_ERR_ARG;
     have_fwd = false; hs = HeadSaved();      // whatever happens below, a backward finds nothing of the forward before this one
     HeadMode mode;
     RL_TRY(head_mode(b, &mode));
@@ -1425,18 +1486,16 @@ template <typename T> struct Engine : EngineBase {
     RL_TRY(wait_opt(st, 0));           // a pipelined optimizer sweep: its first piece holds everything the first kernels read
     have_glyph_fwd = false;            // the activations a glyph_backward would read are about to be overwritten
     dead_ok = false; rows_live = false;
-    last_alive.assign(Tp, 0);
     // host counts (the reference's contract: pho_lens is a host list) or, after realise_build_pho, device counts: every
     // step is then launched over all B*S rows and bounded on the device
-    if (vr.pho) for (int t = 0; t < Tp; ++t) last_alive[t] = b.n_alive ? b.n_alive[t] : b.B * b.S;
-    alive_dev = (vr.pho && !b.n_alive) ? b.n_alive_dev : nullptr;
+    if (by_id) { last_alive.assign(Tp, 0); alive_dev = nullptr; } else take_alive(b, Tp);
     last.n_alive = nullptr;
     const int Tk = b.B * b.S;
     RL_TRY(mask_to_additive(st, b.masks, wp<float>(pl.mask_add), Tk));
     // everything below (and the backward) reads range-checked copies of the ids: a bad id raises in the module, never faults here
     RL_TRY(sanitize_ids(st, b.src_idx, Tk, V, wp<int64_t>(pl.ids_clean), id_flag));
     last.src_idx = wp<int64_t>(pl.ids_clean);
-    if (vr.pho) {
+    if (vr.pho && !by_id) {
       RL_TRY(sanitize_ids(st, b.pho_idx, (int64_t)Tk * Tp, cfg.pho_vocab, wp<int64_t>(pl.pho_clean), id_flag));
       last.pho_idx = wp<int64_t>(pl.pho_clean);
     } else {
@@ -1479,19 +1538,15 @@ template <typename T> struct Engine : EngineBase {
     if (vr.arch) {
       if (vr.pho) {
         RL_TRY(wait_opt(s_pho, opt_groups));                        // (pipelined sweep: pinyin / output stacks and the GRU are one piece)
-        RL_TRY(gru_forward(s_pho));
+        if (!by_id) RL_TRY(gru_forward(s_pho));
         const T* pho_h = nullptr;
-        RL_TRY(stack_forward(s_pho, 1, L.pho, sh_pho, pl.pho, nullptr, wp<T>(pl.gru_out), 0, &pho_h));
+        // token tables: the embedding LayerNorm of pho_model reads the GRU rows by token id - no GRU step, no pass of its own
+        RL_TRY(stack_forward(s_pho, 1, L.pho, sh_pho, pl.pho, nullptr, wp<T>(pl.gru_out), 0, &pho_h, by_id ? (const T*)tok.pho : nullptr, tok.ld));
       }
       if (vr.res) {
-        const T* res = nullptr;
-        RL_TRY(resnet_forward(s_glyph, last.src_idx, &res));
-        LnFwdArgs<T> ln; ln.rows = Tk; ln.H = H; ln.x = res; ln.row_index = wp<int>(pl.gu_inv);      // token t reads its glyph's row
-        ln.gamma = pp(L.res_ln_g); ln.beta = pp(L.res_ln_b); ln.eps = cfg.ln_eps;
-        ln.y = wp<T>(pl.res_h); ln.xhat = bwd_follows() ? wp<T>(pl.res_xhat) : nullptr; ln.rstd = wp<float>(pl.res_rstd);
-        // a 2x2 top (CharResNet1): the rows arrive [p][c], the LayerNorm stores them in the reference's c * 4 + p feature order
-        if (L.tower.top_pixels() == 4) RL_TRY(ln_fwd_chw4<T>(s_glyph, ln));
-        else RL_TRY(ln_fwd<T>(s_glyph, ln));
+        // token tables: res_h is a copy of the table's rows - no glyph gather, tower or resnet_layernorm
+        if (by_id) RL_TRY(token_copy<T>(s_glyph, (const T*)tok.res, tok.ld, last.src_idx, Tk, H, wp<T>(pl.res_h), H));
+        else RL_TRY(res_rows_forward(s_glyph));
       }
       if (ovl && g_fwd_order == 1) { RL_TRY(stack_forward(st, 0, L.bert, sh_bert, pl.bert, last.src_idx, nullptr, 0, &bert_h)); top = bert_h; }
       if (ovl) RL_TRY(join(st));

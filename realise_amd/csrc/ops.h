@@ -35,8 +35,11 @@ int sanitize_ids(hipStream_t st, const int64_t* ids, int64_t n, int V, int64_t* 
 // ---- LayerNorm (K1, K4 tail, K10) ------------------------------------------------------------
 template <typename T> struct LnFwdArgs {
   int rows = 0, H = 0, S = 1;
-  int in_mode = 0;                 // 0: x ; 1: word[ids] + pos + type0 ; 2: x + pos + type0
+  int in_mode = 0;                 // 0: x ; 1: word[ids] + pos + type0 ; 2: x + pos + type0 ; 3: x[ids] + pos + type0 (x: a token table of
+                                   // pitch ld_in in the compute dtype; the arithmetic of mode 2 over the gathered rows, bit for bit)
   const T* x = nullptr;
+  int64_t ld_in = 0;               // in_mode 3: row pitch of the table in elements (0: H); a multiple of 8, rows 16-byte aligned
+  int64_t ldy = 0;                 // row pitch of y in elements (0: H); the one-wave-per-row kernel only (the fast path needs ldy == H)
   const int* row_index = nullptr;  // in_mode 0: read row row_index[r] of x instead of row r (glyph dedup gather)
   const int64_t* ids = nullptr;
   const float* word = nullptr;
@@ -56,6 +59,14 @@ template <typename T> struct LnFwdArgs {
   const uint8_t* row_live = nullptr;
 };
 template <typename T> int ln_fwd(hipStream_t st, const LnFwdArgs<T>& a);
+// Token tables (evaluation: a row that depends on nothing but the token id is read, not recomputed).  ids are int64 in [0, table rows):
+// the caller's to guarantee (the engine passes its range-checked copy).  H % 8 == 0, pitches multiples of 8 elements, 16-byte accesses.
+//   token_copy:    out[t] = table[ids[t]]                        (rows of H elements; out pitch ldo)
+//   token_scatter: pho_table[ids[t]] = pho_rows[t], res_table[ids[t]] = res_rows[t]   (either pair nullable; the rows have pitch H, both
+//                  tables pitch ld; tokens that share an id write the same bytes)
+template <typename T> int token_copy(hipStream_t st, const T* table, int64_t ld, const int64_t* ids, int rows, int H, T* out, int64_t ldo);
+template <typename T> int token_scatter(hipStream_t st, const int64_t* ids, int rows, int H, const T* pho_rows, T* pho_table,
+                                        const T* res_rows, T* res_table, int64_t ld);
 
 template <typename T> struct LnBwdArgs {
   int rows = 0, H = 0;

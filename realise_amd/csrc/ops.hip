@@ -22,15 +22,30 @@ int mask_to_additive(hipStream_t st, const int64_t* masks, float* out, int n) {
 // LayerNorm forward (BertEmbeddings modeling_bert.py:183-193, BertSelfOutput/BertOutput :273-277,
 // :339-343, resnet_layernorm models.py:838)
 // ---------------------------------------------------------------------------------------------
+// in_mode 3: columns c .. c + 3 of a token-table row with ONE 16-byte load per lane.  fp32: the four floats.  bf16: the 16-byte chunk of
+// eight columns that holds them (two neighbouring lanes read the same chunk and keep a half each), so a lane ends up with exactly the
+// columns - and the sums - of the 8-byte load of modes 0 / 2.
+template <typename T> __device__ __forceinline__ floatx4 load4_of16(const T* row, int c);
+template <> __device__ __forceinline__ floatx4 load4_of16<float>(const float* row, int c) { return *(const floatx4*)(row + c); }
+template <> __device__ __forceinline__ floatx4 load4_of16<bf16_t>(const bf16_t* row, int c) {
+  const uint4 u = *(const uint4*)(row + (c & ~7));
+  const uint32_t lo = (c & 4) ? u.z : u.x, hi = (c & 4) ? u.w : u.y;
+  floatx4 r;
+  r[0] = __uint_as_float(lo << 16); r[1] = __uint_as_float(lo & 0xffff0000u);
+  r[2] = __uint_as_float(hi << 16); r[3] = __uint_as_float(hi & 0xffff0000u);
+  return r;
+}
+
 template <typename T>
 __global__ void __launch_bounds__(256) ln_fwd_kernel(LnFwdArgs<T> a) {
   const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
   const int row = blockIdx.x * 4 + wave;
   if (row >= a.rows) return;
   const int H = a.H;
+  const int64_t ldy = a.ldy ? a.ldy : (int64_t)H;
   floatx4 v[LN_MAXV];
   float sum = 0.f;
-  const int64_t tok = (a.in_mode == 1) ? a.ids[row] : 0;
+  const int64_t tok = (a.in_mode == 1 || a.in_mode == 3) ? a.ids[row] : 0;
   const int prow = a.pos_zero ? 0 : (row % a.S);
 #pragma unroll
   for (int i = 0; i < LN_MAXV; ++i) {
@@ -39,6 +54,7 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(LnFwdArgs<T> a) {
     if (c < H) {
       floatx4 x;
       if (a.in_mode == 1) x = *(const floatx4*)(a.word + tok * H + c);
+      else if (a.in_mode == 3) x = load4_of16<T>(a.x + tok * (a.ld_in ? a.ld_in : (int64_t)H), c);
       else x = load4<T>(a.x + (int64_t)(a.row_index ? a.row_index[row] : row) * H + c);
       if (a.in_mode != 0) x += *(const floatx4*)(a.pos + (int64_t)prow * H + c) + *(const floatx4*)(a.type0 + c);
       v[i] = x;
@@ -71,7 +87,7 @@ __global__ void __launch_bounds__(256) ln_fwd_kernel(LnFwdArgs<T> a) {
       }
       y *= drop_mult4(a.drop.seed, a.drop.thresh, a.drop.scale, (uint32_t)row * (uint32_t)H + (uint32_t)c);       // H % 4 == 0
       if (a.xhat != nullptr) store4<T>(a.xhat + (int64_t)row * H + c, xh);
-      store4<T>(a.y + (int64_t)row * H + c, y);
+      store4<T>(a.y + (int64_t)row * ldy + c, y);
     }
   }
 }
@@ -175,7 +191,7 @@ void set_ln_bwd_blocks(int n) { if (g_ln_v2) g_ln_bwd_blocks_v2 = n > 0 ? n : 25
 
 template <typename T> int ln_fwd_fast(hipStream_t st, const LnFwdArgs<T>& a) { return -1; }
 template <> int ln_fwd_fast<bf16_t>(hipStream_t st, const LnFwdArgs<bf16_t>& a) {
-  if (!g_ln_fast || a.in_mode != 0 || a.row_index != nullptr || (a.H % 256) != 0 || a.H > 1024) return -1;
+  if (!g_ln_fast || a.in_mode != 0 || a.row_index != nullptr || (a.H % 256) != 0 || a.H > 1024 || (a.ldy != 0 && a.ldy != a.H)) return -1;
   constexpr int RP = 2;
   const int blocks = (a.rows + 4 * 2 * RP - 1) / (4 * 2 * RP);
 #define RL_LNF(NV) do { if (g_ln_v2) hipLaunchKernelGGL((ln_fwd16_kernel<NV, RP, true>), dim3(blocks), dim3(256), 0, st, a); \
@@ -193,12 +209,62 @@ template <> int ln_fwd_fast<bf16_t>(hipStream_t st, const LnFwdArgs<bf16_t>& a) 
 template <typename T> int ln_fwd(hipStream_t st, const LnFwdArgs<T>& a) {
   if (a.rows <= 0) return RL_OK;
   if ((a.H & 3) || a.H > LN_MAXV * 256) return RL_ERR_ARG;
+  if (a.in_mode == 3 && ((a.H & 7) || (a.ld_in & 7) || (a.ld_in != 0 && a.ld_in < a.H) || !a.ids || !a.x)) return RL_ERR_ARG;      // whole 16-byte chunks
   { const int rc = ln_fwd_fast<T>(st, a); if (rc >= 0) return rc; }
   hipLaunchKernelGGL((ln_fwd_kernel<T>), dim3((a.rows + 3) / 4), dim3(256), 0, st, a);
   return RL_LAUNCH_CHECK();
 }
 template int ln_fwd<bf16_t>(hipStream_t, const LnFwdArgs<bf16_t>&);
 template int ln_fwd<float>(hipStream_t, const LnFwdArgs<float>&);
+
+// ---------------------------------------------------------------------------------------------
+// Token tables: rows by token id, 16 bytes per lane and access, one wave per row and four rows per workgroup as ln_fwd_kernel
+// ---------------------------------------------------------------------------------------------
+template <typename T>
+__global__ void __launch_bounds__(256) token_copy_kernel(const T* __restrict__ table, int64_t ld, const int64_t* __restrict__ ids, int rows, int H,
+                                                         T* __restrict__ out, int64_t ldo) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + wave;
+  if (row >= rows) return;
+  constexpr int E = 16 / (int)sizeof(T);                 // elements per 16-byte chunk
+  const T* src = table + ids[row] * ld;
+  T* dst = out + (int64_t)row * ldo;
+  for (int c = lane * E; c < H; c += 64 * E) *(uint4*)(dst + c) = *(const uint4*)(src + c);
+}
+template <typename T> int token_copy(hipStream_t st, const T* table, int64_t ld, const int64_t* ids, int rows, int H, T* out, int64_t ldo) {
+  if (!table || !ids || !out || H < 8 || (H & 7) || (ld & 7) || (ldo & 7) || ld < H || ldo < H) return RL_ERR_ARG;
+  if (rows <= 0) return RL_OK;
+  hipLaunchKernelGGL((token_copy_kernel<T>), dim3((rows + 3) / 4), dim3(256), 0, st, table, ld, ids, rows, H, out, ldo);
+  return RL_LAUNCH_CHECK();
+}
+template int token_copy<bf16_t>(hipStream_t, const bf16_t*, int64_t, const int64_t*, int, int, bf16_t*, int64_t);
+template int token_copy<float>(hipStream_t, const float*, int64_t, const int64_t*, int, int, float*, int64_t);
+
+// blockIdx.y: 0 = the pinyin pair, 1 = the glyph pair (a missing pair returns at once)
+template <typename T>
+__global__ void __launch_bounds__(256) token_scatter_kernel(const int64_t* __restrict__ ids, int rows, int H, const T* __restrict__ rows0,
+                                                            T* __restrict__ table0, const T* __restrict__ rows1, T* __restrict__ table1, int64_t ld) {
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const int row = blockIdx.x * 4 + wave;
+  const T* src = blockIdx.y ? rows1 : rows0;
+  T* table = blockIdx.y ? table1 : table0;
+  if (row >= rows || src == nullptr || table == nullptr) return;
+  constexpr int E = 16 / (int)sizeof(T);
+  src += (int64_t)row * H;
+  T* dst = table + ids[row] * ld;
+  for (int c = lane * E; c < H; c += 64 * E) *(uint4*)(dst + c) = *(const uint4*)(src + c);
+}
+template <typename T> int token_scatter(hipStream_t st, const int64_t* ids, int rows, int H, const T* pho_rows, T* pho_table,
+                                        const T* res_rows, T* res_table, int64_t ld) {
+  const bool pho = pho_rows && pho_table, res = res_rows && res_table;
+  if (!ids || (!pho && !res) || H < 8 || (H & 7) || (ld & 7) || ld < H) return RL_ERR_ARG;
+  if (rows <= 0) return RL_OK;
+  hipLaunchKernelGGL((token_scatter_kernel<T>), dim3((rows + 3) / 4, 2), dim3(256), 0, st, ids, rows, H, pho ? pho_rows : nullptr,
+                     pho ? pho_table : nullptr, res ? res_rows : nullptr, res ? res_table : nullptr, ld);
+  return RL_LAUNCH_CHECK();
+}
+template int token_scatter<bf16_t>(hipStream_t, const int64_t*, int, int, const bf16_t*, bf16_t*, const bf16_t*, bf16_t*, int64_t);
+template int token_scatter<float>(hipStream_t, const int64_t*, int, int, const float*, float*, const float*, float*, int64_t);
 
 // ---------------------------------------------------------------------------------------------
 // LayerNorm backward: dx = rstd * (dy*g - mean(dy*g) - xhat * mean(dy*g*xhat)); dgamma/dbeta

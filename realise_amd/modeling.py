@@ -105,6 +105,7 @@ class RealiseModule(nn.Module):
         self.grad_sync = None               # optional object with bucket_ready(i) / finish(), set by the DDP wrapper
         self.signalled_backward = os.environ.get("REALISE_SIGNALLED_BACKWARD", "1") != "0"    # DDP: one-call backward + bucket events
         self._last = None
+        self._tok = None                    # token tables of build_token_tables() while they are valid
         # ---- arenas (CPU first, like the reference: Model(config) -> load -> .to(device)) ----
         self._arenas = [torch.zeros(max(self._sizes[0], 1), dtype=torch.float32),
                         torch.zeros(max(self._sizes[1], 1), dtype=torch.float32),
@@ -175,6 +176,7 @@ class RealiseModule(nn.Module):
         return self
 
     def _drop_engine(self):
+        self._tok = None                    # (the tables go with the engine they were installed in)
         if self._engine is not None:
             _capi.load().realise_engine_destroy(self._engine)
         self._engine = None
@@ -241,6 +243,7 @@ class RealiseModule(nn.Module):
         self._shadow_version = None
         self._linear_copies_current = False
         self._frozen_version = None
+        self.drop_token_tables()
         return torch.nn.modules.module._IncompatibleKeys(missing, unexpected)
 
     @classmethod
@@ -275,6 +278,7 @@ class RealiseModule(nn.Module):
         self._shadow_version = None
         self._linear_copies_current = False
         self._frozen_version = None
+        self.drop_token_tables()
 
     def build_glyce_embed(self, vocab_dir, font_path, font_size=32):
         """src/models.py:703-734 (single-font model, ``char_images.weight [V, 1024]``): render ``vocab.txt`` with one font,
@@ -476,6 +480,7 @@ class RealiseModule(nn.Module):
         self._linear_copies_current = bool(linear_copies_current)
         if frozen:
             self._frozen_version = None
+        self.drop_token_tables()
 
     def tap(self, name):
         """named internal activation of the last forward as a torch tensor (parity tests)"""
@@ -553,6 +558,7 @@ class RealiseModule(nn.Module):
         cb = _capi.Batch()
         cb.B, cb.S, cb.Tp = B, S, 1
         training = bool(self.training)
+        tok = self._live_token_tables(training)
         need_grad = training and tgt is not None and torch.is_grad_enabled()
         cb.training = 1 if training else 0
         cb.want_dlogits = 1 if need_grad else 0
@@ -562,7 +568,9 @@ class RealiseModule(nn.Module):
         cb.src_idx, cb.masks = src.data_ptr(), masks.data_ptr()
         cb.tgt_idx = tgt.data_ptr() if tgt is not None else None
         cb.loss_masks = loss_masks.data_ptr() if loss_masks is not None else None
-        with_pho = self.variant.pho
+        with_pho = self.variant.pho and tok is None       # valid token tables: the GRU does not run and the batch needs no pinyin
+        if tok is not None:
+            cb.Tp = tok["Tp"]                                 # the workspace key of the build (and of the device build_batch)
         if with_pho and "pho_idx" not in batch and getattr(self, "_pho_table", None) is not None:
             batch = self.build_batch_device(batch)
         if with_pho and "_pho_device" in batch:
@@ -664,6 +672,8 @@ class RealiseModule(nn.Module):
         B, S = src.shape
         self._ensure_engine(B, S, -1)
         training = bool(self.training if training is None else training)
+        if training:
+            self.drop_token_tables()         # batch statistics move BatchNorm's running buffers, which the glyph table rows were computed from
         out = torch.empty((B, S, self.config.hidden_size), dtype=_DTYPES[self.compute_dtype][1], device=self.device)
         self._fwd_gen += 1
         _capi.check(_capi.load().realise_engine_glyph_forward(self._engine, self._stream(), src.data_ptr(), B, S, 1 if training else 0,
@@ -689,6 +699,7 @@ class RealiseModule(nn.Module):
             raise ValueError("pinyin table has %d rows, vocabulary has %d" % (table.table.shape[0], self.vocab_size))
         self._pho_table = torch.from_numpy(table.table).to(self.device)
         self._pho_vlens = torch.from_numpy(table.lens).to(self.device)
+        self.drop_token_tables()
 
     def build_batch_device(self, batch):
         """models.py:797-804 on the device: adds ``pho_idx`` [B*S, 7] and the length-sorted bookkeeping of the GRU
@@ -709,6 +720,94 @@ class RealiseModule(nn.Module):
         batch["pho_idx"] = pho_idx
         batch["_pho_device"] = (perm, lens_sorted, alive)
         return batch
+
+    # ------------------------------------------------------------------ token tables (serving)
+    def _no_token_tables(self):
+        """why this model builds no token tables (None: it does)"""
+        if not self.variant.arch or not (self.variant.pho or self.variant.res):
+            return "%s has no side branch: nothing of its forward depends on the token id alone" % type(self).__name__
+        return None
+
+    @torch.no_grad()
+    def build_token_tables(self, B=None, S=None):
+        """Serving: compute, once per set of weights, the two rows of an evaluation forward that depend on nothing but the token id -
+        ``pho_gru``'s last hidden state (the pinyin is a function of the token: ``set_pinyin_table()`` first) and
+        ``resnet_layernorm(resnet(glyph[id]))`` on BatchNorm's running statistics - for every id of the vocabulary, as two ``[V, H]``
+        tables in the compute dtype's storage (a model with one side branch builds one).  While they are valid every evaluation-mode
+        ``forward``, ``decode(batch)`` and ``predict`` reads them instead of running the GRU and the glyph tower, and a batch needs no
+        ``pho_idx`` / ``pho_lens``.  Returns the bytes held.
+
+        The ids 0 .. V-1 go through the engine's own branch code in chunks of ``B * S`` (default: the shape of the last forward, else
+        64 x 128; the last chunk is padded with the last id), so a row is produced by the kernels a full forward of that shape runs.
+
+        The tables are dropped - forwards silently take the full path again, which is always correct - as soon as an evaluation forward
+        would re-derive the operand copies: a training-mode forward, ``static_weights`` False, a changed arena version,
+        ``mark_parameters_updated()``, ``load_state_dict``, ``set_glyph_table`` / ``build_glyce_embed*``, ``set_pinyin_table``, ``.to()``.
+        So a loop that serves sets ``static_weights = True`` first (``trainer.evaluate(token_tables=True)`` does).  With the tables in
+        use the taps ``pho_gru``, ``resnet.block*`` and ``glyph.*`` hold whatever an earlier forward left."""
+        why = self._no_token_tables()
+        if why:
+            raise RuntimeError("build_token_tables: " + why)
+        if self.device.type != "cuda":
+            raise _capi.RealiseHipError("build_token_tables needs a GPU: move the module with .to('cuda') (there is no CPU fallback)")
+        v = self.variant
+        if v.pho and getattr(self, "_pho_table", None) is None:
+            raise RuntimeError("build_token_tables: set_pinyin_table() first - the pinyin must be a function of the token")
+        if v.res:
+            self._glyph_param()              # (the glyph table is a parameter of every model with the branch: installed from construction)
+        if B is None or S is None:
+            B, S = self._ws_key[:2] if self._ws_key is not None else (64, 128)
+        B, S = int(B), int(S)
+        V, H = self.vocab_size, self.config.hidden_size
+        lib = _capi.load()
+        self._raise_on_bad_ids()
+        self.drop_token_tables()
+        Tp = int(self._pho_table.shape[1]) if v.pho else 1
+        self._ensure_engine(B, S, Tp)
+        self._fwd_gen += 1                   # the branch activations of the last forward are overwritten: no backward through it
+        tdt = _DTYPES[self.compute_dtype][1]
+        pho = torch.empty((V, H), dtype=tdt, device=self.device) if v.pho else None
+        res = torch.empty((V, H), dtype=tdt, device=self.device) if v.res else None
+        tt = _capi.TokenTables()
+        tt.pho, tt.res, tt.ld, tt.rows = (pho.data_ptr() if v.pho else None), (res.data_ptr() if v.res else None), H, V
+        st = self._stream()
+        for c0 in range(0, V, B * S):
+            ids = torch.arange(c0, c0 + B * S, dtype=torch.int64, device=self.device).clamp_(max=V - 1).view(B, S)
+            cb = _capi.Batch()
+            cb.B, cb.S, cb.Tp, cb.training, cb.src_idx = B, S, Tp, 0, ids.data_ptr()
+            if v.pho:
+                b = self.build_batch_device({"src_idx": ids})
+                perm_d, lens_d, alive_d = b["_pho_device"]
+                cb.pho_idx, cb.pho_perm, cb.pho_lens_sorted = b["pho_idx"].data_ptr(), perm_d.data_ptr(), lens_d.data_ptr()
+                cb.n_alive, cb.n_alive_dev = None, alive_d.data_ptr()
+            _capi.check(lib.realise_engine_fill_token_tables(self._engine, st, C.byref(cb), C.byref(tt)), "realise_engine_fill_token_tables")
+        _capi.check(lib.realise_engine_set_token_tables(self._engine, C.byref(tt)), "realise_engine_set_token_tables")
+        nbytes = sum(t.numel() * t.element_size() for t in (pho, res) if t is not None)
+        self._tok = dict(pho=pho, res=res, Tp=Tp, bytes=nbytes, shape=(B, S))
+        return nbytes
+
+    def drop_token_tables(self):
+        """free the token tables; forwards take the full path (no-op without tables)"""
+        if self.__dict__.get("_tok") is not None:
+            if self._engine is not None:
+                _capi.load().realise_engine_set_token_tables(self._engine, None)
+            self._tok = None
+
+    @property
+    def token_tables_valid(self):
+        """True while evaluation forwards read the tables of ``build_token_tables()``"""
+        return self.__dict__.get("_tok") is not None
+
+    def _live_token_tables(self, training):
+        """the tables if this forward may read them; dropped when it would re-derive the operand copies (``_ensure_engine``)"""
+        tok = self.__dict__.get("_tok")
+        if tok is None:
+            return None
+        ver = (self._arenas[0]._version, self._arenas[2]._version)
+        if training or not self.static_weights or self._shadow_version != ver or getattr(self, "_frozen_version", None) != ver[1]:
+            self.drop_token_tables()
+            return None
+        return tok
 
     @torch.no_grad()
     def decode(self, batch_or_logits):

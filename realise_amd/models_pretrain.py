@@ -96,6 +96,9 @@ class Pho2Pretrain(RealiseModule):
         batch["pho_lens"] = pho_lens
         return batch
 
+    def _no_token_tables(self):
+        return "Pho2Pretrain reads the pinyin of tgt_idx, not of src_idx, and its evaluation is one short pass: there is no serving loop to table"
+
     def _engine_batch(self, batch):
         """the batch as the engine reads it: src_idx = tgt_idx (models.py:1319), so the range check, the device-side pinyin gather and the
         labels all see the same ids"""

@@ -199,7 +199,7 @@ def train(model, items, *, batch_size=64, max_seq_length=128, epochs=1, lr=5e-5,
 
 @torch.no_grad()
 def evaluate(model, items, *, batch_size=64, max_seq_length=128, device="cuda", build_batch=None, tokenizer=None,
-             vocab_path=None, label_path=None, output_dir=None, prefix="", live_rows=False, fused_decode=False):
+             vocab_path=None, label_path=None, output_dir=None, prefix="", live_rows=False, fused_decode=False, token_tables=False):
     """run.py:239-280: mean eval loss and the arg-max ids.  The arg-max runs on the device (``model.decode``), so only
     [B, S] ids cross PCIe instead of the [B, S, 21128] logits.  With ``vocab_path`` + ``label_path`` + ``output_dir`` the
     predictions are also written as ``preds.txt`` / ``labels.txt`` and scored like the reference (``results`` dict).
@@ -207,7 +207,10 @@ def evaluate(model, items, *, batch_size=64, max_seq_length=128, device="cuda", 
     -12 % per forward at B = 64, S = 128) - the loss and the ids of the real tokens, all the scorer reads (it cuts at ``lengths``), are
     unchanged; the ids returned for padding positions are then arbitrary.
     ``fused_decode=True``: every batch goes through ``model.predict`` - the arg-max and the loss leave the classifier kernel itself and
-    no [B, S, V] logits tensor exists at any point; the default is the forward + ``decode`` path."""
+    no [B, S, V] logits tensor exists at any point; the default is the forward + ``decode`` path.
+    ``token_tables=True``: ``model.build_token_tables()`` once the weights are static (the model needs ``set_pinyin_table()`` where it
+    has a pinyin branch) - the pinyin GRU and the glyph tower then run once per vocabulary entry instead of once per batch - and
+    ``drop_token_tables()`` on the way out."""
     from .metric import Metric
     build_batch = build_batch or type(model).build_batch
     model.eval()
@@ -221,6 +224,8 @@ def evaluate(model, items, *, batch_size=64, max_seq_length=128, device="cuda", 
     if was_live is not None:
         model.eval_live_rows = bool(live_rows)
     try:
+        if token_tables:
+            model.build_token_tables(batch_size, max_seq_length)
         for batch in data_helper(items, batch_size, max_seq_length, build_batch, tokenizer, is_eval=True):
             if fused_decode:
                 pred = model.predict(batch)
@@ -236,6 +241,8 @@ def evaluate(model, items, *, batch_size=64, max_seq_length=128, device="cuda", 
                 batch["pred_idx"] = ids.numpy()
                 batches.append(batch)
     finally:
+        if token_tables:
+            model.drop_token_tables()
         if was_static is not None:
             model.static_weights = was_static
         if was_live is not None:

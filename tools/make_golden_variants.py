@@ -4,7 +4,7 @@ image_model_type 1 (arch3_img1_*, abla_img1_*, resnet1_*).
 
 TEST INFRASTRUCTURE; run only where the reference tree exists (oracle/_ref_import.py):
 
-    PYTHONDONTWRITEBYTECODE=1 python tools/make_golden_variants.py [abla] [arch4] [mlm] [resnet1] [concat] [pretrain] [--out DIR]
+    PYTHONDONTWRITEBYTECODE=1 python tools/make_golden_variants.py [abla] [arch4] [mlm] [resnet1] [concat] [pretrain] [tables] [--out DIR]
 
 Without a group name every group is generated.  Inputs are regenerated from seeds (realise_amd.init.init_state_dict_numpy(...,
 scheme="perturbed"), realise_amd.data.synthetic_batch, realise_amd.data.glyph_upstream_grad); the fixtures hold summaries in the
@@ -41,6 +41,15 @@ possible and the tests hold that block and the blocks upstream of it to a looser
   ascending row order, `hits` -, the active rows' top-1 / top-2 margins (`active_margin`), a strided sample of their logits
   (`active_logits`) and the taps `head_z`, `head_y`, `pho_out` (the pho stack's output).  EVERY active position must have a margin
   above 1e-4 or the generator stops: the tests compare the ids at all of them.  Losses of the committed fixtures are printed by the run.
+
+* tables: three EVALUATION cases for the token tables (RealiseModule.build_token_tables) - SpellBertPho2ResArch3 with three fonts, with
+  CharResNet1, and SpellBertPho2ResArch2 - whose batches come from realise_amd.data.synthetic_batch(..., pinyin_table=
+  synthetic_pinyin_table(seed=...)), so the pinyin is a function of the token, as the tables need.  Next to the usual summaries a
+  fixture holds strided samples of what the tables stand for: the GRU's last hidden state (`pho_gru`, h_n of m.pho_gru in token order)
+  and the resnet_layernorm output (`res_h`), both taken with forward hooks.  EVERY position must have a top-1 / top-2 margin above 1e-4
+  or the generator stops (pick another seed): the tests compare the ids at all of them.  Losses of the committed fixtures, as printed
+  (B = 2, S = 16, 2 layers, dropout 0, perturbed init; every position above the margin): arch3_tok_b2s16_eval 8.068518 (seed 71,
+  smallest margin 1.93e-03), arch3_img1_tok_b2s16_eval 6.632167 (seed 72, 2.85e-02), arch2_tok_b2s16_eval 10.081238 (seed 73, 3.47e-03).
 
 The tests compare arg-max ids above a top-1 / top-2 margin of 1e-4.  The arch4, mlm and concat tests expect that to be every position, the
 resnet1 tests at least 95 % of them: a case with more positions under the margin than its group allows stops the generator (pick
@@ -356,6 +365,49 @@ def case_pretrain(mods, BertConfig, out, c, n_layers=2):
     np.savez_compressed(os.path.join(out, c.name + ".npz"), **store)
 
 
+# ---- tables: evaluation cases whose pinyin is a function of the token.  name, model type, num_fonts, image_model_type, seed
+TableCase = collections.namedtuple("TableCase", "name model_type num_fonts image_model_type seed")
+TABLE_CASES = [
+    TableCase("arch3_tok_b2s16_eval", "arch3", 3, 0, 71),
+    TableCase("arch3_img1_tok_b2s16_eval", "arch3", 1, 1, 72),
+    TableCase("arch2_tok_b2s16_eval", "arch2", 1, 0, 73),
+]
+
+
+def case_tables(mods, BertConfig, out, c, B=2, S=16, n_layers=2):
+    from realise_amd.data import synthetic_pinyin_table
+    t0 = time.time()
+    cfg = RealiseConfig(num_hidden_layers=n_layers, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0, num_fonts=c.num_fonts,
+                        image_model_type=c.image_model_type)
+    sd_np = init_state_dict_numpy(cfg, c.model_type, seed=c.seed, scheme="perturbed")
+    batch = synthetic_batch(B, S, seed=c.seed, pinyin_table=synthetic_pinyin_table(cfg["vocab_size"], seed=c.seed))
+    m, _ = reference_model(mods, BertConfig, cfg, c.model_type)
+    load(m, sd_np, False)
+    taken = {}
+    hooks = [m.pho_gru.register_forward_hook(lambda mod, i, o: taken.__setitem__("pho_gru", o[1].detach().squeeze(0).clone())),
+             m.resnet_layernorm.register_forward_hook(lambda mod, i, o: taken.__setitem__("res_h", o.detach().clone()))]
+    with torch.no_grad():
+        loss, logits = m(batch)[:2]
+    for h in hooks:
+        h.remove()
+    store = {"meta/B": np.int64(B), "meta/S": np.int64(S), "meta/seed": np.int64(c.seed), "meta/n_layers": np.int64(n_layers),
+             "meta/train": np.int64(0), "meta/num_fonts": np.int64(c.num_fonts), "meta/image_model_type": np.int64(c.image_model_type)}
+    store["loss"] = np.float64(loss.item())
+    put(store, "logits", logits)
+    store["argmax"] = logits.argmax(-1).to(torch.int32).numpy()
+    top2 = logits.topk(2, dim=-1).values
+    store["margin"] = (top2[..., 0] - top2[..., 1]).to(torch.float32).numpy()
+    put(store, "pho_gru", taken["pho_gru"].reshape(B * S, -1))
+    put(store, "res_h", taken["res_h"].reshape(B * S, -1))
+    under = int((store["margin"] <= MARGIN).sum())
+    print("[%s] loss %.6f | smallest margin %.2e, <= %g at %d of %d | |pho_gru| max %.2f, |res_h| max %.2f | %.1fs"
+          % (c.name, loss.item(), float(store["margin"].min()), MARGIN, under, B * S, float(taken["pho_gru"].abs().max()),
+             float(taken["res_h"].abs().max()), time.time() - t0))
+    if under:
+        raise SystemExit("%s (seed %d): %d of %d positions at or under the arg-max margin %g; pick another seed" % (c.name, c.seed, under, B * S, MARGIN))
+    np.savez_compressed(os.path.join(out, c.name + ".npz"), **store)
+
+
 def state_dict_pretrain(mods, BertConfig, out):
     m, _ = reference_model(mods, BertConfig, RealiseConfig(num_hidden_layers=12, hidden_dropout_prob=0.0, attention_probs_dropout_prob=0.0),
                            "pho2-pretrain")
@@ -397,17 +449,21 @@ def state_dicts(mods, BertConfig, out, group):
 
 def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n\n")[0])
-    ap.add_argument("groups", nargs="*", help="which groups of fixtures to generate: %s (default: all)" % ", ".join(list(GROUPS) + ["pretrain"]))
+    ap.add_argument("groups", nargs="*", help="which groups of fixtures to generate: %s (default: all)" % ", ".join(list(GROUPS) + ["pretrain", "tables"]))
     ap.add_argument("--out", default=os.path.join(ROOT, "tests", "golden"), help="directory the fixtures are written to")
     args = ap.parse_args()
-    if set(args.groups) - set(GROUPS) - {"pretrain"}:
-        ap.error("unknown group %s" % sorted(set(args.groups) - set(GROUPS) - {"pretrain"}))
+    if set(args.groups) - set(GROUPS) - {"pretrain", "tables"}:
+        ap.error("unknown group %s" % sorted(set(args.groups) - set(GROUPS) - {"pretrain", "tables"}))
     torch.manual_seed(0)
     torch.set_num_threads(8)
     models, BertConfig = import_reference()
     import models_abla                                  # src/ is on the path after import_reference()
     mods = {"models": models, "abla": models_abla}
-    for group in args.groups or list(GROUPS) + ["pretrain"]:
+    for group in args.groups or list(GROUPS) + ["pretrain", "tables"]:
+        if group == "tables":
+            for c in TABLE_CASES:
+                case_tables(mods, BertConfig, args.out, c)
+            continue
         if group == "pretrain":
             state_dict_pretrain(mods, BertConfig, args.out)
             for c in PRETRAIN_CASES:
