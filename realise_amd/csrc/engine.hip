@@ -1347,7 +1347,7 @@ template <typename T> struct Engine : EngineBase {
       RL_TRY(ce_loss<T>(st, nullptr, Vp, b.tgt_idx, b.loss_masks, Tk, V, b.loss_out, wp<float>(pl.count), wp<T>(pl.dlogits),
                         wp<float>(pl.loss_internal), Vp, cc));
       T* xc = wp<T>(vr.mlm_head ? pl.head_xc : pl.cls_xc);
-      RL_TRY(gather_rows<T>(st, head_in, act, n_act, Tk, H, xc));
+      RL_TRY(gather_listed_rows<T>(st, head_in, act, n_act, Tk, H, xc));
       head_in = xc; n_rows = n_act;
     }
     const T* dec_in = head_in;
@@ -1400,10 +1400,10 @@ template <typename T> struct Engine : EngineBase {
                       b.want_dlogits ? wp<T>(pl.dlogits) : nullptr, wp<float>(pl.loss_internal), Vp, cc, ranking ? &pr : nullptr));
     hs.compact = compact; hs.dec_in = dec_in; hs.head_in = head_in;
     if (compact && !loss_rows) {      // the weight gradients read their input rows compacted; the MLM head's saved tensors stay where they are
-      RL_TRY(gather_rows<T>(st, dec_in, act, n_act, Tk, H, wp<T>(pl.cls_xc)));
+      RL_TRY(gather_listed_rows<T>(st, dec_in, act, n_act, Tk, H, wp<T>(pl.cls_xc)));
       hs.dec_in = wp<T>(pl.cls_xc);
       if (vr.mlm_head) {
-        RL_TRY(gather_rows<T>(st, head_in, act, n_act, Tk, H, wp<T>(pl.head_xc)));
+        RL_TRY(gather_listed_rows<T>(st, head_in, act, n_act, Tk, H, wp<T>(pl.head_xc)));
         hs.head_in = wp<T>(pl.head_xc); hs.row_map = act;
       }
     }

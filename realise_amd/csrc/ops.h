@@ -1,5 +1,6 @@
-// Memory-bound kernels of the path: embeddings, LayerNorm, BatchNorm, gate fusion, GRU gate
-// math, masked cross-entropy, dropout, bias / column reductions, weight shadows, optimizer.
+// Host interface of the memory-bound row kernels: argument structs, launchers and knobs, one section per source file that defines
+// them, in this order - layernorm.hip, tokens.hip, loss.hip, fusion.hip, gru.hip, batchnorm.hip, glyph_rows.hip, shadows.hip,
+// optim.hip.  The types and scratch sizes that several sections use come first.
 #pragma once
 #include "common.h"
 
@@ -7,8 +8,6 @@ namespace rl {
 
 struct DropParams { uint32_t seed = 0, thresh = 0; float scale = 1.0f; };
 
-// Device-side row bound + per-image multiplicity for the glyph branch, which runs once per DISTINCT token id of the
-// batch: effective rows = min(P, *rows_dev); weight(row) = counts[row / hw] (the number of tokens sharing that glyph).
 constexpr int COL_SLOT_FLOATS = 262144;   // >= (row chunks) x 2C for every launch shape of the column reductions
 constexpr int COL_SLOT_BYTES = COL_SLOT_FLOATS * 4;
 constexpr int LN_SLOT_FLOATS = 1024 * 2 * 1024;   // LayerNorm backward: one [dgamma | dbeta] record per workgroup (<= 1024 workgroups, H <= 1024)
@@ -17,6 +16,8 @@ constexpr int LN_SLOT_BYTES = LN_SLOT_FLOATS * 4;
 // store their taps parity class by parity class, conv_s2_class())
 struct TapOrder { int n = 0; int t[9] = {0, 0, 0, 0, 0, 0, 0, 0, 0}; };
 
+// Device-side row bound + per-image multiplicity for the glyph branch, which runs once per DISTINCT token id of the
+// batch: effective rows = min(P, *rows_dev); weight(row) = counts[row / hw] (the number of tokens sharing that glyph).
 struct RowBound {
   const int* rows_dev = nullptr;
   const float* counts = nullptr;
@@ -28,11 +29,7 @@ struct RowBound {
 __device__ __forceinline__ int rb_rows(const RowBound& b, int P) { return b.rows_dev ? min(P, *b.rows_dev) : P; }
 __device__ __forceinline__ float rb_weight(const RowBound& b, int row) { return b.counts ? b.counts[row / b.hw] : 1.0f; }
 
-int mask_to_additive(hipStream_t st, const int64_t* masks, float* out, int n);
-// out[i] = ids[i] if 0 <= ids[i] < V else 0, *flag = 1 when any id was out of range (flag nullable)
-int sanitize_ids(hipStream_t st, const int64_t* ids, int64_t n, int V, int64_t* out, int* flag);
-
-// ---- LayerNorm (K1, K4 tail, K10) ------------------------------------------------------------
+// ---- LayerNorm (K1, K4 tail, K10): layernorm.hip ---------------------------------------------
 template <typename T> struct LnFwdArgs {
   int rows = 0, H = 0, S = 1;
   int in_mode = 0;                 // 0: x ; 1: word[ids] + pos + type0 ; 2: x + pos + type0 ; 3: x[ids] + pos + type0 (x: a token table of
@@ -59,14 +56,6 @@ template <typename T> struct LnFwdArgs {
   const uint8_t* row_live = nullptr;
 };
 template <typename T> int ln_fwd(hipStream_t st, const LnFwdArgs<T>& a);
-// Token tables (evaluation: a row that depends on nothing but the token id is read, not recomputed).  ids are int64 in [0, table rows):
-// the caller's to guarantee (the engine passes its range-checked copy).  H % 8 == 0, pitches multiples of 8 elements, 16-byte accesses.
-//   token_copy:    out[t] = table[ids[t]]                        (rows of H elements; out pitch ldo)
-//   token_scatter: pho_table[ids[t]] = pho_rows[t], res_table[ids[t]] = res_rows[t]   (either pair nullable; the rows have pitch H, both
-//                  tables pitch ld; tokens that share an id write the same bytes)
-template <typename T> int token_copy(hipStream_t st, const T* table, int64_t ld, const int64_t* ids, int rows, int H, T* out, int64_t ldo);
-template <typename T> int token_scatter(hipStream_t st, const int64_t* ids, int rows, int H, const T* pho_rows, T* pho_table,
-                                        const T* res_rows, T* res_table, int64_t ld);
 
 template <typename T> struct LnBwdArgs {
   int rows = 0, H = 0;
@@ -86,14 +75,6 @@ template <typename T> struct LnBwdArgs {
   int* deferred_records = nullptr; // non-null: do NOT launch the fold; *deferred_records = number of records written to `slots` (0: none, the
                                    // gradients were accumulated directly) - the caller folds several sites in one launch (ln_fold_multi)
 };
-// Rows of a [B, S] token batch whose gradients can be non-zero: row (b, s) is live iff s < 1 + the last position of sentence b with
-// masks == 1 or loss_masks == 1 (everything after it is padding that no query attends to and no loss term reads: every backward
-// activation row there is an exact zero).  row_live[B * S] bytes; tiles64 / tiles32 / tiles16 (nullable): ascending indices of the
-// 64- / 32- / 16-row blocks of the token rows that hold a live row, n_tiles[0..2] their counts (the live-block lists of the
-// weight-gradient reductions).  rows (nullable): the live rows themselves, ascending, n_tiles[3] of them (round 6: the row-granular
-// list of the layer GEMMs).
-int row_liveness(hipStream_t st, const int64_t* masks, const int64_t* loss_masks, int B, int S, uint8_t* row_live, int* tiles64, int* tiles32,
-                 int* tiles16, int* n_tiles, int* rlen, int* rows = nullptr);       // rlen[b] = live rows of sentence b (the attention backward's bound)
 template <typename T> int ln_bwd(hipStream_t st, const LnBwdArgs<T>& a);
 // dgamma / dbeta += fixed-order sum of the per-workgroup records of up to LN_FOLD_MAX LayerNorm sites, one launch
 constexpr int LN_FOLD_MAX = 8;
@@ -123,15 +104,31 @@ void set_ln_fast(int on);            // 1 (default): bf16 rows of 256 / 512 / 76
 void set_ln_v2(int on);              // 1 (default, round 5): DPP row reductions + ln_bwd16v2_kernel; 0: the round-4 kernels
 void set_ln_bwd_blocks(int n);       // workgroups of the fast LayerNorm backward (default 512)
 
+// ---- tokens (masks, live rows, embedding backward, token tables, dropout): tokens.hip ----------
+int mask_to_additive(hipStream_t st, const int64_t* masks, float* out, int n);
+// Rows of a [B, S] token batch whose gradients can be non-zero: row (b, s) is live iff s < 1 + the last position of sentence b with
+// masks == 1 or loss_masks == 1 (everything after it is padding that no query attends to and no loss term reads: every backward
+// activation row there is an exact zero).  row_live[B * S] bytes; tiles64 / tiles32 / tiles16 (nullable): ascending indices of the
+// 64- / 32- / 16-row blocks of the token rows that hold a live row, n_tiles[0..2] their counts (the live-block lists of the
+// weight-gradient reductions).  rows (nullable): the live rows themselves, ascending, n_tiles[3] of them (round 6: the row-granular
+// list of the layer GEMMs).
+int row_liveness(hipStream_t st, const int64_t* masks, const int64_t* loss_masks, int B, int S, uint8_t* row_live, int* tiles64, int* tiles32,
+                 int* tiles16, int* n_tiles, int* rlen, int* rows = nullptr);       // rlen[b] = live rows of sentence b (the attention backward's bound)
 // scatter d(embedding sum) to the word / position / type tables
 template <typename T>
 int embed_bwd(hipStream_t st, const T* de, const int64_t* ids, int B, int S, int H, float* word_grad, float* pos_grad,
               int pos_zero, float* type_grad);
-
-template <typename T> int bias_grad(hipStream_t st, const T* dy, int64_t ld, int rows, int N, float* out, const int* rows_dev = nullptr);
+// Token tables (evaluation: a row that depends on nothing but the token id is read, not recomputed).  ids are int64 in [0, table rows):
+// the caller's to guarantee (the engine passes its range-checked copy).  H % 8 == 0, pitches multiples of 8 elements, 16-byte accesses.
+//   token_copy:    out[t] = table[ids[t]]                        (rows of H elements; out pitch ldo)
+//   token_scatter: pho_table[ids[t]] = pho_rows[t], res_table[ids[t]] = res_rows[t]   (either pair nullable; the rows have pitch H, both
+//                  tables pitch ld; tokens that share an id write the same bytes)
+template <typename T> int token_copy(hipStream_t st, const T* table, int64_t ld, const int64_t* ids, int rows, int H, T* out, int64_t ldo);
+template <typename T> int token_scatter(hipStream_t st, const int64_t* ids, int rows, int H, const T* pho_rows, T* pho_table,
+                                        const T* res_rows, T* res_table, int64_t ld);
 template <typename T> int dropout_apply(hipStream_t st, const T* x, T* y, int rows, int H, DropParams d);
 
-// ---- masked cross-entropy (K13) ---------------------------------------------------------------
+// ---- loss (masked cross-entropy K13, compacted-row movers, arg-max, decode merge / loss): loss.hip ----
 // loss_out[0] = mean over rows with loss_mask==1 of CE(logits[row], labels[row]); dlogits (optional)
 // = d loss / d logits.  count_buf: 1 float scratch.  Rows whose label is -100 (CrossEntropyLoss's ignore_index) are skipped in
 // the mean; any other label outside [0, V) turns the loss into NaN.  row_loss (optional, `rows` floats): per-row terms folded in
@@ -153,21 +150,27 @@ struct CePred { int64_t* pred = nullptr; int64_t* labels_out = nullptr; int32_t*
 template <typename T>
 int ce_loss(hipStream_t st, const T* logits, int64_t ld, const int64_t* labels, const int64_t* loss_mask, int rows, int V,
             float* loss_out, float* count_buf, T* dlogits, float* row_loss = nullptr, int64_t ld_dl = 0, const CeCompact& cc = CeCompact(),
-            const CePred* pr = nullptr);
+            const CePred* pr = nullptr);      // ld_dl: row pitch of dlogits (0: ld)
 void set_ce_fast(int on);           // bf16 masked cross-entropy with the logits row held in registers (default 1)
-// out[j] = in[idx[j]], j < *n_dev (rows of H elements); out[row] = inv[row] >= 0 ? in[inv[row]] * dropout mask : 0
-template <typename T> int gather_rows(hipStream_t st, const T* in, const int* idx, const int* n_dev, int max_rows, int H, T* out);
+// the rows named by a device-side list: out[j] = in[idx[j]], j < *n_dev <= max_rows (rows of H elements; the launch covers max_rows)
+template <typename T> int gather_listed_rows(hipStream_t st, const T* in, const int* idx, const int* n_dev, int max_rows, int H, T* out);
+// the way back: out[row] = inv[row] >= 0 ? in[inv[row]] * dropout mask : 0
 // scale_dev (nullable): a device scalar multiplied into every stored value - the incoming loss gradient, never read on the host
 template <typename T> int scatter_rows_drop(hipStream_t st, const T* in, const int* inv, int rows, int H, T* out, DropParams d, const float* scale_dev = nullptr);
 template <typename T> int scale_by_dev(hipStream_t st, T* x, int64_t n, const float* scale_dev);
 template <typename T> int scatter_rows_drop_slab(hipStream_t st, const float* slab, int nsplit, int64_t stride, const int* inv, int rows, int H, T* out,
-                                                 DropParams d, const float* scale_dev = nullptr);      // rows of a split-K GEMM's fp32 planes, folded in plane order   // ld_dl: row pitch of dlogits (0: ld)
+                                                 DropParams d, const float* scale_dev = nullptr);      // rows of a split-K GEMM's fp32 planes, folded in plane order
 
-// ---- eval decode (run.py:262-263): ids[row] = argmax_v logits[row][v], first maximum wins (numpy / torch semantics), a NaN
+// eval decode (run.py:262-263): ids[row] = argmax_v logits[row][v], first maximum wins (numpy / torch semantics), a NaN
 // counts as the maximum.  Only the ids leave the device (32 KB instead of the 692 MB fp32 logits of run.py:262).
 template <typename T> int argmax_rows(hipStream_t st, const T* logits, int64_t ld, int rows, int V, int64_t* ids);
+// Decode GEMM, second half (gemm_nt_decode): folds the nslab records of every row (DecodeParams, gemm.h), slabs ascending, into
+// ids / values / probs [M, k] and lse [M]; kc = candidates per record (1 or 4), k <= kc.
+int decode_merge(hipStream_t st, const float* rec, int kc, int nslab, int M, int k, int64_t* ids, float* values, float* probs, float* lse);
+// masked mean of lse - label_logit over the rows that enter the loss (models.py:862-869: loss_mask == 1, label != -100); one workgroup, fixed order
+int decode_loss(hipStream_t st, const float* lse, const float* label_logit, const int64_t* labels, const int64_t* loss_mask, int rows, float* loss_out);
 
-// ---- gate fusion (K11) --------------------------------------------------------------------------
+// ---- fusion (gate K11, sum): fusion.hip -----------------------------------------------------------
 template <typename T> struct GateArgs {
   int B = 0, S = 0, H = 0;
   const T* bert = nullptr; const T* pho = nullptr; const T* res = nullptr;
@@ -201,6 +204,8 @@ template <typename T> int sum_fuse_bwd(hipStream_t st, const T* dfused, T* dbert
                                        const uint8_t* row_live = nullptr);      // row_live: padding rows (0) get exact zeros
 
 // ---- pinyin GRU (K6) ------------------------------------------------------------------------------
+// out[i] = ids[i] if 0 <= ids[i] < V else 0, *flag = 1 when any id was out of range (flag nullable)
+int sanitize_ids(hipStream_t st, const int64_t* ids, int64_t n, int V, int64_t* out, int* flag);
 template <typename T> struct GruStepArgs {
   int n_alive = 0, H = 0, Tp = 0, t = 0;
   const int* n_alive_dev = nullptr; // optional device-side count: rows >= *n_alive_dev are skipped (n_alive is then the launch bound)
@@ -266,6 +271,7 @@ int bn_bwd_reduce2(hipStream_t st, const bf16_t* dy, const bf16_t* relu_src, con
 int bn_bwd_apply2(hipStream_t st, const bf16_t* dy, const bf16_t* relu_src, const bf16_t* xa, const float* mean_a, const float* rstd_a,
                   const float* gamma_a, bf16_t* dxa, float* dgamma_a, float* dbeta_a, const bf16_t* xb, const float* mean_b, const float* rstd_b,
                   const float* gamma_b, bf16_t* dxb, float* dgamma_b, float* dbeta_b, const float* sums4, int P, int C, RowBound rb, int n_stat);
+template <typename T> int bias_grad(hipStream_t st, const T* dy, int64_t ld, int rows, int N, float* out, const int* rows_dev = nullptr);
 template <typename T> int col_sum(hipStream_t st, const T* x, int P, int C, float* out, RowBound rb = RowBound(), float scale = 1.0f);   // scale != 1 needs rb.slots
 template <typename T> int col_sumsq_centered(hipStream_t st, const T* x, int P, int C, const float* mean, float* out, RowBound rb = RowBound());
 // train-mode finalize: stats -> (mean, rstd, scale, shift), running-stat update (unbiased var, momentum)
@@ -310,7 +316,7 @@ int bn_backward(hipStream_t st, const T* dy, const T* relu_src, int P, int C, in
 // g = dy * (relu_src > 0)
 template <typename T> int relu_bwd(hipStream_t st, const T* dy, const T* relu_src, T* g, int64_t n);
 
-// ---- glyph dedup (the ResNet input depends only on the token id) ------------------------------------
+// ---- glyph rows (dedup: the ResNet input depends only on the token id; the _chw4 flatten): glyph_rows.hip ----
 // ids[T] -> uniq_ids[<=T] (order of first occurrence), counts[slot], inv[t] = slot of token t, and bounds[0] = U,
 // bounds[1+k] = U * hw[k] for k < nhw.  first_scratch: V ints, flag_scratch: T ints.
 struct HwList { int n = 0; int v[8] = {0, 0, 0, 0, 0, 0, 0, 0}; };
@@ -336,11 +342,6 @@ template <typename T> int segment_sum_chw4(hipStream_t st, const T* x, const int
 // ---- weight shadows (operand copies in the compute dtype) ----------------------------------------
 template <typename T> int cast_copy(hipStream_t st, const float* src, T* dst, int64_t n);
 template <typename T> int cast_to_f32(hipStream_t st, const T* src, float* dst, int64_t n);     // 16-byte aligned pointers
-// Decode GEMM, second half (gemm_nt_decode): folds the nslab records of every row (DecodeParams, gemm.h), slabs ascending, into
-// ids / values / probs [M, k] and lse [M]; kc = candidates per record (1 or 4), k <= kc.
-int decode_merge(hipStream_t st, const float* rec, int kc, int nslab, int M, int k, int64_t* ids, float* values, float* probs, float* lse);
-// masked mean of lse - label_logit over the rows that enter the loss (models.py:862-869: loss_mask == 1, label != -100); one workgroup, fixed order
-int decode_loss(hipStream_t st, const float* lse, const float* label_logit, const int64_t* labels, const int64_t* loss_mask, int rows, float* loss_out);
 // src fp32 [R][C] -> dst [R][C] (optional) and dstT [C][R] (optional)
 template <typename T> int cast_transpose(hipStream_t st, const float* src, int R, int C, T* dst, T* dstT);
 // many matrices in ONE launch (the per-step refresh of every Linear weight's W and W^T operand copies): `descs` is a
